@@ -6,6 +6,10 @@ model (frozen 12-layer LongNet backbone + Modal Adapter), KL distillation loss, 
 all-reduce started from inside the backward (N > 1), AdamW.  Inputs are synthetic and resident in HBM before the
 timed region.  One JSON line on rank 0.
 
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, ...); --dump-outputs DIR also
+writes what the last timed step computed as DIR/<name>.npy.  --full adds everything else the line can carry: the per-kernel
+table and rooflines from an eager instrumented pass, the measured MFMA peak, the secondary legs and the CPU baseline.
+
 `python bench.py --gpus N` with no WORLD_SIZE in the environment starts the N ranks itself: N fresh child processes
 (one per GPU, rendezvous on 127.0.0.1) are spawned BEFORE this process touches the GPU; under torchrun (RANK /
 WORLD_SIZE set) the process is one of the ranks.
@@ -70,7 +74,42 @@ def parse_args():
     ap.add_argument("--config", default="gigapath", choices=["gigapath", "titan"],
                     help="gigapath: BASELINE config 2 (the headline metric); titan: BASELINE config 4 (TITAN backbone configuration, "
                          "--patches foreground cells, --ragged: mixed bag lengths) -- a separate JSON line, never the headline")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the eager instrumented pass after the timed steps (per-kernel table, "
+                         "rooflines, measured MFMA peak, the token side as one graph), the secondary legs and the CPU baseline.  Without "
+                         "it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): loss, logits, "
+                         "trainable parameters and, for the fused TrainStep, its unscaled gradients; a flat buffer of more than "
+                         f"{DUMP_MAX_VALUES} values is written at a fixed, seeded sample of indices")
+    args = ap.parse_args()
+    if args.kernel_times:
+        args.full = True          # the table is printed from the instrumented pass
+    return args
+
+
+DUMP_MAX_VALUES = 6 * 1024 * 1024         # per array: 24 MB of float32 (every dump stays below 64 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every tensor as out_dir/<name>.npy in float32.  An array of more than DUMP_MAX_VALUES values is flattened and
+    written at DUMP_MAX_VALUES sorted indices drawn with a fixed seed (the same set on every run and every build of this length)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_VALUES, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
+def trainstep_outputs(ts):
+    """What a caller of TrainStep.step / step_graphed receives from its last step: the loss, the logits of the task passes, the
+    updated trainable parameters (flat buffer) and the step's gradients unscaled (TrainStep.unscaled_grads on the flat buffer)."""
+    store = ts.engine.store
+    return {"loss": ts.loss, "logits": ts.last_logits, "params": store.flat, "grads": store.flat_grad / ts.scale}
 
 
 def launch_ranks(args) -> int:
@@ -292,7 +331,7 @@ def titan_cpu_baseline(vit_cpu, N, depth, passes, max_seconds=20.0):
                       f"fwd+bwd at N={N}, 1 pass: {t:.2f} s; step = {n} block passes ({passes} tasks x {depth} blocks) -> {n * t:.1f} s/slide"}
 
 
-def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_baseline=True):
+def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_baseline=True, dump=None):
     """BASELINE config 4: TITAN backbone configuration (model_configs/modaltune_titan_config.json), ~4k foreground cells, mixed bag
     lengths.  The TITAN snapshot is not in the reference tree: the backbone is a random-init ViT of TITAN's published geometry
     (768-d, 6 blocks, 12 heads x 64, MLP ratio 4, 2-D ALiBi, one-query attentional pooling: tests/golden/titan_standin.py) running
@@ -354,18 +393,38 @@ def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_base
     run(steps, first=nwarm)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, trainstep_outputs(ts))
     loss = float(ts.loss)
-    prof_steps = len(slides)
     replays = ts.graph_replays
+    T = cfg.num_tokens
+    used = [cells_per[i % len(slides)] for i in range(nwarm, nwarm + steps)]
+    step_flops = sum(flops_per_titan_step(c, T)["step"] for c in used) / len(used)
+    value = steps / dt
+    out = {
+        "metric": "slides/sec (train step), TITAN backbone configuration, ~4k foreground cells", "value": value, "unit": "slides/s",
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * dt / steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
+        "config": {"workload": f"BASELINE config 4: TITAN-geometry ViT (768-d, 6 blocks, 12 heads x 64, MLP 3072, 2-D ALiBi from one fp16 distance table per slide, attentional pooling; "
+                               f"random init, stand-in for the absent MahmoodLab/TITAN snapshot: backbone parity UNPINNED) + Modal Adapter, "
+                               f"{T - 1} gene tokens + 1 task token, 3 task passes batched, fp16 operands / fp32 accumulate, "
+                               + ("train mode (DropPath 0.2 on the Extractor FFN, gene-encoder dropouts), " if not args.no_dropout else "dropout off, ") +
+                               f"foreground cells per slide: " + "/".join(str(c) for c in cells_per) + (" in rotation (mixed bag lengths)" if ragged else ""),
+                   "cells": cells_per, "tokens": T, "parallelism": "dp1", "backbone_impl": eng.backbone.kind, "self_check": report},
+        "loss": loss, "step_tflops": step_flops / 1e12, "step_mfma_frac": step_flops * value / 1e12 / PEAK_F16_MFMA_TFLOPS,
+        "launch": ("hipGraph replay per (patches, tokens) geometry -- the gridding kernels and the token-count read-back stay eager; a bag length "
+                   "that has not been seen three times runs the eager schedule" if graphed else "eager"), "graph_replays": replays,
+        "pass_groups": {"by_tokens": {str(k): {"groups": bool(v), **ts.split_trials.get(k, {})} for k, v in sorted(ts.split_decisions.items())},
+                        "how": "each recurring geometry captured both ways at capture time, the faster kept (TrainStep._trial_split)"},
+    }
+    if not args.full:
+        return out
+    prof_steps = len(slides)
     ops.TIMER = {}
     run(prof_steps, first=0, eager=True)
     torch.cuda.synchronize()
     timer, ops.TIMER = ops.TIMER, None
     summ = ops.timer_summary(timer)
-    T = cfg.num_tokens
-    used = [cells_per[i % len(slides)] for i in range(nwarm, nwarm + steps)]
-    step_flops = sum(flops_per_titan_step(c, T)["step"] for c in used) / len(used)
-    value = steps / dt
     # dominant kernel: the dK / dV kernel of the dense attention backward, one launch per block per step over the 3 passes;
     # algorithmic FLOPs per launch = S, dP, dV, dK = 2 x the forward's two products, averaged over the profiled bag lengths
     n_l, ms = summ["dense_attn_bwd_kv"]
@@ -382,17 +441,7 @@ def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_base
             a_ = fl / (m_ / n * 1e-3) / 1e12
             table.append({"kernel": key, "bound": "mfma", "achieved": round(a_, 1), "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
                           "frac": round(a_ / PEAK_F16_MFMA_TFLOPS, 4), "avg_launch_ms": round(m_ / n, 4), "ms_per_step": round(m_ / prof_steps, 3)})
-    out = {
-        "metric": "slides/sec (train step), TITAN backbone configuration, ~4k foreground cells", "value": value, "unit": "slides/s",
-        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * dt / steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
-        "config": {"workload": f"BASELINE config 4: TITAN-geometry ViT (768-d, 6 blocks, 12 heads x 64, MLP 3072, 2-D ALiBi from one fp16 distance table per slide, attentional pooling; "
-                               f"random init, stand-in for the absent MahmoodLab/TITAN snapshot: backbone parity UNPINNED) + Modal Adapter, "
-                               f"{T - 1} gene tokens + 1 task token, 3 task passes batched, fp16 operands / fp32 accumulate, "
-                               + ("train mode (DropPath 0.2 on the Extractor FFN, gene-encoder dropouts), " if not args.no_dropout else "dropout off, ") +
-                               f"foreground cells per slide: " + "/".join(str(c) for c in cells_per) + (" in rotation (mixed bag lengths)" if ragged else ""),
-                   "cells": cells_per, "tokens": T, "parallelism": "dp1", "backbone_impl": eng.backbone.kind, "self_check": report},
-        "loss": loss, "step_tflops": step_flops / 1e12, "step_mfma_frac": step_flops * value / 1e12 / PEAK_F16_MFMA_TFLOPS,
+    out.update({
         "roofline": {"kernel": "dense_attn_bwd_kv_kernel", "bound": "mfma", "achieved": achieved, "peak": PEAK_F16_MFMA_TFLOPS, "unit": "TFLOP/s",
                      "frac": achieved / PEAK_F16_MFMA_TFLOPS, "traffic": traffic,
                      "traffic_source": (f"{traffic_file}: rocprofv3 --pmc passes at N = 4097 tokens x 3 passes (tools/dense_microbench.py), "
@@ -400,12 +449,8 @@ def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_base
                      "avg_launch_ms": ms / n_l, "flops_per_launch": kv_flops,
                      "measured": f"HIP events around each launch, eager instrumented pass over the {prof_steps} bag lengths after the timed region"},
         "roofline_kernels": table,
-        "launch": ("hipGraph replay per (patches, tokens) geometry -- the gridding kernels and the token-count read-back stay eager; a bag length "
-                   "that has not been seen three times runs the eager schedule" if graphed else "eager"), "graph_replays": replays,
         "kernel_ms_per_step": {k: round(v[1] / prof_steps, 3) for k, v in sorted(summ.items(), key=lambda kv: -kv[1][1])[:14]},
-        "pass_groups": {"by_tokens": {str(k): {"groups": bool(v), **ts.split_trials.get(k, {})} for k, v in sorted(ts.split_decisions.items())},
-                        "how": "each recurring geometry captured both ways at capture time, the faster kept (TrainStep._trial_split)"},
-    }
+    })
     if args.kernel_times:
         fam = {}
         for k, (n, m_) in summ.items():
@@ -419,7 +464,7 @@ def run_titan(args, steps=None, warmup=None, patches=None, ragged=None, cpu_base
     return out
 
 
-def run_module(args, steps=None, warmup=None, optim=None):
+def run_module(args, steps=None, warmup=None, optim=None, dump=None):
     """The boundary north_star names, driven exactly as the reference trainer drives it (train_modaltune.py:123-149,172-177,
     195-240): Aggregator.create -> per step the frozen torch projector, three model(...) calls (one per task id), torch's
     KL-divergence loss under autocast, GradScaler.scale(loss).backward(), GradScaler.step(torch.optim.AdamW), update, zero_grad."""
@@ -482,7 +527,7 @@ def run_module(args, steps=None, warmup=None, optim=None):
         scaler.step(opt)
         scaler.update()
         opt.zero_grad()
-        last["loss"] = loss.detach()
+        last["loss"], last["logits"] = loss.detach(), logit.detach()
 
     # warm-up: one slide teaches the module the task-id pattern, then the batched pass is seen twice on the eager bridge, twice on the
     # priming visits of module_graph.ModuleReplay and captured on the next one -- the timed region is the steady state (replays)
@@ -498,6 +543,9 @@ def run_module(args, steps=None, warmup=None, optim=None):
     host_dt = time.perf_counter() - t0          # when the host had ENQUEUED the last step (no sync inside the loop: below dt when the GPU is the bound)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump:      # (the trainable parameters in model.parameters() order, concatenated)
+        dump_outputs(dump, {"loss": last["loss"], "logits": last["logits"],
+                            "params": torch.cat([p.detach().reshape(-1) for p in params[0]["params"]])})
     T = cfg.num_tokens
     fl = flops_per_slide_step(L, T)
     value = steps / dt
@@ -705,9 +753,9 @@ def main():
     if args.cpu_baseline_child:
         return cpu_baseline_child(args.cpu_baseline_child, args.pathways)
     if args.config == "titan":
-        return print(json.dumps(run_titan(args)))
+        return print(json.dumps(run_titan(args, dump=args.dump_outputs)))
     if args.api == "module":
-        return print(json.dumps(run_module(args)))
+        return print(json.dumps(run_module(args, dump=args.dump_outputs)))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
 
@@ -871,6 +919,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dt_own = dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainstep_outputs(ts))
     if comm is not None:
         ev, ts.comm_events = ts.comm_events, None
         for kind, key in (("grad", "comm_exposed_ms"), ("param", "param_gather_exposed_ms")):
@@ -879,57 +929,61 @@ def main():
             comm[key.replace("_ms", "_events")] = len(ms)
     loss = float(ts.loss)
     replays, eager_steps = ts.graph_replays, ts.eager_steps
-    # per-kernel durations: HIP events on the launch stream around every launch of an eager, instrumented pass of the
-    # same step (events cannot be recorded inside a replayed graph); not part of the timed region above
-    # The timed region above runs the task passes of a long bag as two concurrent groups (TrainStep.split_passes): kernels of the two
-    # groups overlap there, so a per-launch duration would be that of a kernel sharing the chip.  The per-kernel table and the roofline
-    # are taken on the BATCHED schedule (one B = 3 pass, every kernel alone on the chip): comparable with rounds 1-4 and with
-    # `rocprofv3 --kernel-trace --stats` of `MT_SPLIT_PASSES=0 python3 bench.py` (profiles/).
     pass_groups = {"on": bool(ts._split_now(L)), "groups": [list(g) for g in ts._groups], "min_patches": ts.split_min_patches,
                    "decided_by": ("trial at capture time (ms per replayed step, both schedules captured; training state restored behind it): " + json.dumps(ts.split_trials[L])) if L in ts.split_trials
-                   else "threshold", "kernel_table": "batched schedule (one kernel at a time)"}
-    split_was, ts.split_passes = ts.split_passes, False
-    if pass_groups["on"]:
-        run(2, graphed=False, first=nwarm + args.steps)          # (the batched geometry's workspace and gradient arena: untimed)
-    prof_steps = min(args.steps, 3)
-    ops.TIMER = {}
-    run(prof_steps, graphed=False, first=nwarm + args.steps)
-    barrier()
-    timer, ops.TIMER = ops.TIMER, None
-    skipped = nwarm + args.steps + prof_steps + (2 if pass_groups["on"] else 0) + extra_steps - int(ts.step_dev)
-    # the token side on its own: every token-side launch of ONE step recorded in order, captured as a hipGraph on the same buffers and
-    # replayed -- what the ~220 small dependent launches cost INSIDE the replayed step (HIP events around each launch of the eager pass
-    # above add the event overhead to every one of them: that table's `token_side` row is an upper bound)
-    token_graph = None
-    if not dp_on and not args.ragged:
-        try:
-            ops.RECORD, ops.RECORD_KEEP[:] = [], []
-            run(1, graphed=False, first=nwarm + args.steps + prof_steps)
-            rec, ops.RECORD = ops.RECORD, None
-            torch.cuda.synchronize()
-            gs = torch.cuda.Stream()
-            with torch.cuda.stream(gs):
-                tg = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(tg, stream=gs):
-                    for fn, a, k in rec:
-                        fn(*a, **k)
-                tg.replay(); torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(gs)
-                for _ in range(10):
-                    tg.replay()
-                e1.record(gs); torch.cuda.synchronize()
-            token_graph = {"launches": len(rec), "ms": e0.elapsed_time(e1) / 10,
-                           "how": "all token-side launches of one step (LayerNorms and fp32 products of <= 1024 rows, adds, copies, DropPath rows, "
-                                  "T x T attention, pathway networks, loss head) re-issued in order inside one hipGraph on the step's own buffers, "
-                                  "10 replays"}
-            del tg, rec
-        except Exception as e:       # a measurement aid must never cost the headline line
-            token_graph = {"error": f"{type(e).__name__}: {e}"}
-        finally:
-            ops.RECORD = None
-            ops.RECORD_KEEP[:] = []
-    ts.split_passes = split_was
+                   else "threshold"}
+    prof_steps, timer, token_graph = 0, None, None
+    if args.full:
+        # per-kernel durations: HIP events on the launch stream around every launch of an eager, instrumented pass of the
+        # same step (events cannot be recorded inside a replayed graph); not part of the timed region above
+        # The timed region above runs the task passes of a long bag as two concurrent groups (TrainStep.split_passes): kernels of the two
+        # groups overlap there, so a per-launch duration would be that of a kernel sharing the chip.  The per-kernel table and the roofline
+        # are taken on the BATCHED schedule (one B = 3 pass, every kernel alone on the chip): comparable with rounds 1-4 and with
+        # `rocprofv3 --kernel-trace --stats` of `MT_SPLIT_PASSES=0 python3 bench.py` (profiles/).
+        pass_groups["kernel_table"] = "batched schedule (one kernel at a time)"
+        split_was, ts.split_passes = ts.split_passes, False
+        if pass_groups["on"]:
+            run(2, graphed=False, first=nwarm + args.steps)          # (the batched geometry's workspace and gradient arena: untimed)
+        prof_steps = min(args.steps, 3)
+        ops.TIMER = {}
+        run(prof_steps, graphed=False, first=nwarm + args.steps)
+        barrier()
+        timer, ops.TIMER = ops.TIMER, None
+        skipped = nwarm + args.steps + prof_steps + (2 if pass_groups["on"] else 0) + extra_steps - int(ts.step_dev)
+        # the token side on its own: every token-side launch of ONE step recorded in order, captured as a hipGraph on the same buffers and
+        # replayed -- what the ~220 small dependent launches cost INSIDE the replayed step (HIP events around each launch of the eager pass
+        # above add the event overhead to every one of them: that table's `token_side` row is an upper bound)
+        if not dp_on and not args.ragged:
+            try:
+                ops.RECORD, ops.RECORD_KEEP[:] = [], []
+                run(1, graphed=False, first=nwarm + args.steps + prof_steps)
+                rec, ops.RECORD = ops.RECORD, None
+                torch.cuda.synchronize()
+                gs = torch.cuda.Stream()
+                with torch.cuda.stream(gs):
+                    tg = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(tg, stream=gs):
+                        for fn, a, k in rec:
+                            fn(*a, **k)
+                    tg.replay(); torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(gs)
+                    for _ in range(10):
+                        tg.replay()
+                    e1.record(gs); torch.cuda.synchronize()
+                token_graph = {"launches": len(rec), "ms": e0.elapsed_time(e1) / 10,
+                               "how": "all token-side launches of one step (LayerNorms and fp32 products of <= 1024 rows, adds, copies, DropPath rows, "
+                                      "T x T attention, pathway networks, loss head) re-issued in order inside one hipGraph on the step's own buffers, "
+                                      "10 replays"}
+                del tg, rec
+            except Exception as e:       # a measurement aid must never cost the headline line
+                token_graph = {"error": f"{type(e).__name__}: {e}"}
+            finally:
+                ops.RECORD = None
+                ops.RECORD_KEEP[:] = []
+        ts.split_passes = split_was
+    else:
+        skipped = nwarm + args.steps + extra_steps - int(ts.step_dev)
     if dp_on:
         host = args.backend != "nccl"
         tt = torch.tensor([dt, comm["comm_exposed_ms"], comm["param_gather_exposed_ms"]], device="cpu" if host else dev, dtype=torch.float64)
@@ -946,32 +1000,6 @@ def main():
         T = cfg.num_tokens
         fl = flops_per_slide_step(L, T)
         value = args.steps * world / dt
-        summ = ops.timer_summary(timer)
-        tot_ms = sum(v[1] for v in summ.values())
-        if args.kernel_times:
-            for k, (n, ms) in sorted(summ.items(), key=lambda kv: -kv[1][1]):
-                print(f"  {k:32s} launches/step {n / prof_steps:7.1f}  ms/step {ms / prof_steps:9.3f}  ({100 * ms / tot_ms:5.1f} %)",
-                      file=sys.stderr)
-        # roofline of the dominant kernel (largest share of the step): the dK/dV kernel of the dilated-attention backward,
-        # one launch per layer per step over all 5 branches and all 3 task passes.  Algorithmic FLOPs per launch: the four
-        # products it owns (S = Q K^T, dP = dO V^T, dV = P^T dO, dK = dS^T Q) = 2 x the forward's two products
-        # (SURVEY §8d counts the whole flash backward as 2.5 x forward; the dQ kernel carries the remaining 0.5 x).
-        n_l, ms = summ["dilated_attn_bwd_kv"]
-        launch_flops = 2.0 * 3 * fl["attn_layer"]
-        achieved = launch_flops / (ms / n_l * 1e-3) / 1e12
-        exec_flops = 2.0 * 3 * fl["attn_layer_executed"]      # zero-padded tiles are skipped, not computed
-        traffic, traffic_file = recorded_traffic("dilated_attn_bwd_kv_kernel", L, T) if not args.ragged else (None, None)
-        table = kernel_rooflines(summ, prof_steps, fl, L, T) if not args.ragged else []
-        meas = ops.measured_mfma_peak_tflops()
-        peak_meas = {"value": meas, "unit": "TFLOP/s", "vendor_peak": PEAK_F16_MFMA_TFLOPS,
-                     "pool_typical": 1760.0, "box_speed_vs_pool_typical": round(meas / 1760.0, 3),
-                     "box_note": "the same bare MFMA loop measured 1750-1783 TFLOP/s on most boxes of this pool in rounds 4-6 and 1630-1670 on its slow "
-                                 "ones, where every MFMA-bound kernel (and ms_per_step) is 6-8 % slower with identical binaries (DESIGN section 5): compare "
-                                 "lines of different boxes through roofline_frac_of_measured / step_frac_of_measured",
-                     "roofline_frac_of_measured": achieved / meas, "step_frac_of_measured": fl["step"] * value / world / 1e12 / meas,
-                     "how": "bare v_mfma_f32_32x32x16_f16 loop, 4 independent accumulators, pseudo-random register operands, 1024 workgroups x 4 "
-                            "waves, best of 3 (mt_mfma_probe); `roofline.frac` stays priced against the 2.5 PF/s vendor figure"}
-        worst = min((r for r in table if r["ms_per_step"] >= 0.4), key=lambda r: r["frac"], default=None)
         out = {
             "metric": "slides/sec (train step) at 10k patches x 1536-d", "value": value, "unit": "slides/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -991,32 +1019,62 @@ def main():
                                            "(MT_DP_REHEARSE=1); `value` is NOT a scaling point"} if args.dp_rehearsal else {})},
             "loss": loss, "skipped_steps": skipped,
             "step_tflops": fl["step"] / 1e12, "step_mfma_frac": fl["step"] * value / world / 1e12 / PEAK_F16_MFMA_TFLOPS,
-            "roofline": {"kernel": "dilated_attn_bwd_kv_kernel", "bound": "mfma", "achieved": achieved, "peak": PEAK_F16_MFMA_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / PEAK_F16_MFMA_TFLOPS,
-                         "frac_basis": "algorithmic FLOPs (SURVEY §8d: the reference computes on zero-padded segments); the kernel "
-                                       "skips the padding -- mfma_frac_executed is the fraction of peak the MFMA pipe itself runs at",
-                         "traffic": traffic,
-                         "avg_launch_ms": ms / n_l, "flops_per_launch": launch_flops,
-                         "flops_executed_per_launch": exec_flops,
-                         "mfma_frac_executed": exec_flops / (ms / n_l * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
-                         "traffic_source": (f"{traffic_file}: rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE in separate runs), "
-                                            "bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) KiB (gfx950 tallies 128-B read requests at 64 B)"
-                                            if traffic is not None else None),
-                         "measured": f"HIP events around each launch, eager instrumented pass of {prof_steps} steps after the timed region"
-                                     + (", on the batched schedule (one B = 3 pass: each kernel alone on the chip; the timed region overlaps two pass groups)"
-                                        if pass_groups["on"] else "")},
-            "mfma_peak_measured": peak_meas,
-            "roofline_worst": worst,
-            "roofline_kernels": table,
             "launch": "eager" if (args.eager or args.ragged) else "hipGraph replay",
-            "graph_replays": replays, "eager_steps": eager_steps, "comm": comm, "token_side_in_graph": token_graph,
-            "kernel_ms_per_step": {k: round(v[1] / prof_steps, 3) for k, v in sorted(summ.items(), key=lambda kv: -kv[1][1])[:12]},
+            "graph_replays": replays, "eager_steps": eager_steps, "comm": comm,
         }
+        if args.full:
+            summ = ops.timer_summary(timer)
+            tot_ms = sum(v[1] for v in summ.values())
+            if args.kernel_times:
+                for k, (n, ms) in sorted(summ.items(), key=lambda kv: -kv[1][1]):
+                    print(f"  {k:32s} launches/step {n / prof_steps:7.1f}  ms/step {ms / prof_steps:9.3f}  ({100 * ms / tot_ms:5.1f} %)",
+                          file=sys.stderr)
+            # roofline of the dominant kernel (largest share of the step): the dK/dV kernel of the dilated-attention backward,
+            # one launch per layer per step over all 5 branches and all 3 task passes.  Algorithmic FLOPs per launch: the four
+            # products it owns (S = Q K^T, dP = dO V^T, dV = P^T dO, dK = dS^T Q) = 2 x the forward's two products
+            # (SURVEY §8d counts the whole flash backward as 2.5 x forward; the dQ kernel carries the remaining 0.5 x).
+            n_l, ms = summ["dilated_attn_bwd_kv"]
+            launch_flops = 2.0 * 3 * fl["attn_layer"]
+            achieved = launch_flops / (ms / n_l * 1e-3) / 1e12
+            exec_flops = 2.0 * 3 * fl["attn_layer_executed"]      # zero-padded tiles are skipped, not computed
+            traffic, traffic_file = recorded_traffic("dilated_attn_bwd_kv_kernel", L, T) if not args.ragged else (None, None)
+            table = kernel_rooflines(summ, prof_steps, fl, L, T) if not args.ragged else []
+            meas = ops.measured_mfma_peak_tflops()
+            peak_meas = {"value": meas, "unit": "TFLOP/s", "vendor_peak": PEAK_F16_MFMA_TFLOPS,
+                         "pool_typical": 1760.0, "box_speed_vs_pool_typical": round(meas / 1760.0, 3),
+                         "box_note": "the same bare MFMA loop measured 1750-1783 TFLOP/s on most boxes of this pool in rounds 4-6 and 1630-1670 on its slow "
+                                     "ones, where every MFMA-bound kernel (and ms_per_step) is 6-8 % slower with identical binaries (DESIGN section 5): compare "
+                                     "lines of different boxes through roofline_frac_of_measured / step_frac_of_measured",
+                         "roofline_frac_of_measured": achieved / meas, "step_frac_of_measured": fl["step"] * value / world / 1e12 / meas,
+                         "how": "bare v_mfma_f32_32x32x16_f16 loop, 4 independent accumulators, pseudo-random register operands, 1024 workgroups x 4 "
+                                "waves, best of 3 (mt_mfma_probe); `roofline.frac` stays priced against the 2.5 PF/s vendor figure"}
+            worst = min((r for r in table if r["ms_per_step"] >= 0.4), key=lambda r: r["frac"], default=None)
+            out.update({
+                "roofline": {"kernel": "dilated_attn_bwd_kv_kernel", "bound": "mfma", "achieved": achieved, "peak": PEAK_F16_MFMA_TFLOPS,
+                             "unit": "TFLOP/s", "frac": achieved / PEAK_F16_MFMA_TFLOPS,
+                             "frac_basis": "algorithmic FLOPs (SURVEY §8d: the reference computes on zero-padded segments); the kernel "
+                                           "skips the padding -- mfma_frac_executed is the fraction of peak the MFMA pipe itself runs at",
+                             "traffic": traffic,
+                             "avg_launch_ms": ms / n_l, "flops_per_launch": launch_flops,
+                             "flops_executed_per_launch": exec_flops,
+                             "mfma_frac_executed": exec_flops / (ms / n_l * 1e-3) / 1e12 / PEAK_F16_MFMA_TFLOPS,
+                             "traffic_source": (f"{traffic_file}: rocprofv3 --pmc passes (FETCH_SIZE and WRITE_SIZE in separate runs), "
+                                                "bytes per launch = (2 x FETCH_SIZE + WRITE_SIZE) KiB (gfx950 tallies 128-B read requests at 64 B)"
+                                                if traffic is not None else None),
+                             "measured": f"HIP events around each launch, eager instrumented pass of {prof_steps} steps after the timed region"
+                                         + (", on the batched schedule (one B = 3 pass: each kernel alone on the chip; the timed region overlaps two pass groups)"
+                                            if pass_groups["on"] else "")},
+                "mfma_peak_measured": peak_meas,
+                "roofline_worst": worst,
+                "roofline_kernels": table,
+                "token_side_in_graph": token_graph,
+                "kernel_ms_per_step": {k: round(v[1] / prof_steps, 3) for k, v in sorted(summ.items(), key=lambda kv: -kv[1][1])[:12]},
+            })
         from modaltune_amd import _lib
         bi = _lib.build_info()       # which binary this line timed: the sha256 of (csrc/*, include/*, flags) it was built from
         out["build_id"], out["build_id_matches_tree"], out["lib"] = bi["build_id"], bi["build_id_matches_tree"], bi["lib"]
         default_line = world == 1 and not (args.ragged or args.eager or args.dp_rehearsal)
-        if default_line and not args.no_legs:
+        if args.full and default_line and not args.no_legs:
             # secondary configurations as short sub-records of the SAME driver-observed line (each <= ~10 s; never the headline)
             out["pcie_inclusive"] = _leg(lambda: leg_pcie(ts, eng, sizes, L, value))
             if pass_groups["on"]:
@@ -1036,7 +1094,7 @@ def main():
             out["module_api"] = _leg(module_leg)
             torch.cuda.empty_cache()
             out["titan"] = _leg(lambda: _brief(run_titan(args, steps=16, warmup=8, patches=4096, ragged=True, cpu_baseline=False)))
-        if world == 1 and not args.no_cpu_baseline and not args.dp_rehearsal:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dp_rehearsal:
             out["cpu_baseline"] = cpu_baseline_leg(L, "real" if args.pathways == 331 else args.pathways)
             out["cpu_baseline_reference"] = CPU_REFERENCE
         print(json.dumps(out))

@@ -13,6 +13,18 @@ from modaltune_amd.config import ModelConfig, segment_lengths
 from oracle import modaltune_oracle as O
 
 F64 = torch.float64
+# MKL splits the oracle's f64 reductions by the intra-op thread count, so the rounding of a deep step depends on the host's
+# core count (model_L512_d12 logits against the fixture: 1.5e-10 at 8 threads, 6.8e-10 at 1 or 4, 1.03e-9 at 16).  Every host
+# runs this module with the same count: the one that matches the fixtures' own rounding best.
+ORACLE_THREADS = 8
+
+
+@pytest.fixture(autouse=True)
+def _oracle_threads():
+    n = torch.get_num_threads()
+    torch.set_num_threads(ORACLE_THREADS)
+    yield
+    torch.set_num_threads(n)
 
 
 def _sd(cfg, sizes, seed, dtype=F64):
