@@ -368,6 +368,17 @@ int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int 
 int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B,
                      int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream);
 
+/* Attention maps of the adapter attentions (forward only): the head-averaged softmax that nn.MultiheadAttention returns with
+ * need_weights=True, recomputed from the operands and the LSE the forward kept -- the scores are rounded as the forward rounds
+ * them, so each head's rows sum to 1 against that LSE.
+ * Extractor: q fp32 [B,T,192], kv fp16 [B*L,384], lse [B,T,12] of mt_extract_attn_fwd -> w fp32 [B,T,L]. */
+int mt_extract_attn_probs(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, float* w, mt_stream_t stream);
+/* Injector: q fp16 [M,192], k fp32 [B,T,192], lse [M,12] of mt_inject_attn_fwd -> w fp32 [M,T] (M = B * rows_per_pass). */
+int mt_inject_attn_probs(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, float* w,
+                         mt_stream_t stream);
+/* Prompt self-attention: out fp32 [B,T,T] = mean over the heads of mt_token_mha_fwd's probs [B,heads,T,T]. */
+int mt_token_probs_mean(const float* probs, int B, int heads, int T, float* out, mt_stream_t stream);
+
 /* ------------------------------------------------------------ elementwise -------------------------- */
 /* y = fp16(x); with `drop` (rows of D elements): y = fp16(drop(x)) -- the masked gradient of a dropped residual branch */
 int mt_cast_f32_to_f16(const float* x, mt_half* y, long n, const MtDropout* drop, int D, mt_stream_t stream);

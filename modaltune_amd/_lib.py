@@ -106,6 +106,9 @@ SIGNATURES = {
     "mt_extract_attn_bwd": [P, P, P, P, P, I, I, I, P, P, P],
     "mt_token_mha_fwd": [P, P, P, I, I, I, I, P, P, P],
     "mt_token_mha_bwd": [P, P, P, P, P, I, I, I, I, P, P, P, P],
+    "mt_extract_attn_probs": [P, P, P, I, I, I, P, P],
+    "mt_inject_attn_probs": [P, I, I, P, P, I, P, P],
+    "mt_token_probs_mean": [P, I, I, I, P, P],
     "mt_cast_f32_to_f16": [P, P, L, DR, I, P],
     "mt_rng_advance": [P, P],
     "mt_dropout_f32": [P, L, RM, P, I, I, DR, P],

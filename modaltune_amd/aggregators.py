@@ -498,6 +498,30 @@ class LongNetGeneAdapter(Aggregator):
     def _apply_bridge(self, x, coords, genes, onehots, need, clinical, token):
         return _ModelFn.apply(self, x, coords, genes, onehots, need, clinical, token, *self._trainable.values())
 
+    def attention_maps(self, x, coords, genes, task_ids=(0, 1, 2), clinical=None, sites=None) -> Dict[str, Any]:
+        """The adapter attention maps of one slide (README Figure 3 of the reference): {"logits" [len(task_ids), output_dim],
+        "tokens": what each of the T modal tokens is (config.token_legend), "maps": {site: map}} with the sites named by the
+        reference's module paths (config.attention_sites; `sites` None = all of them): injector [B, L, T], extractor [B, T, L],
+        prompt self-attention [B, T, T], one row per task id.
+
+        In the reference these are what forward hooks on the nn.MultiheadAttention modules read as output[1] after model.eval():
+        the eval forward is what runs here, under no_grad and without Dropout / DropPath, whatever `model.training` says.  It is
+        the forward-only engine path of evaluate.EmbeddingExtractor(attention=...); evaluate.attention_to_grid draws a map on
+        the slide."""
+        from .config import token_legend
+        from .evaluate import EmbeddingExtractor
+        if not self.is_multi:
+            task_ids = (0,)                      # (one model call, no task token)
+        key = (tuple(int(t) for t in task_ids), tuple(sites) if sites is not None else None)
+        ex = getattr(self, "_maps_extractor", None)
+        if ex is None or ex[0] != key:
+            ex = self._maps_extractor = (key, EmbeddingExtractor(self.engine, key[0], graphed=False,
+                                                                 attention=list(sites) if sites is not None else True))
+        self._sync_weight_caches()
+        with torch.no_grad():
+            logits, maps = ex[1](x, coords, self._gene_list(genes), clinical if self.CLINICAL else None)
+        return {"logits": logits, "tokens": token_legend(self.cfg), "maps": maps}
+
 
 @Aggregator.register("longnetvit_gene_clinical_adapter")
 class LongNetGeneSimpleClinicalAdapter(LongNetGeneAdapter):

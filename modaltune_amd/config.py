@@ -195,6 +195,29 @@ def coords_to_rowcol(coords: np.ndarray, tile: float = 256.0) -> Tuple[np.ndarra
     return g[..., 0].astype(np.int64), g[..., 1].astype(np.int64)
 
 
+def attention_sites(cfg: ModelConfig) -> List[str]:
+    """Module paths of the adapter attentions in the reference model, in its named_modules() order: every nn.MultiheadAttention
+    whose `need_weights` output a forward hook can read (injector / extractor: adapter_modules.py:225-229, prompt self-attention:
+    adapter_modules.py:87; block layout longvit_adapter.py:93-129, adapter_modules.py:425-456)."""
+    n = len(cfg.interaction_indexes)
+    out = []
+    for i in range(n):
+        out.append(f"interactions.{i}.injector.attn.multihead_attn")
+        out.append(f"interactions.{i}.extractor.attn.multihead_attn")
+        if i == n - 1 and cfg.use_extra_extractor:
+            out += [f"interactions.{i}.extra_extractors.{j}.attn.multihead_attn" for j in range(2)]
+    if cfg.use_prompt_sa:           # prompt_selfattention.0 is an identity (longvit_adapter.py:111-129)
+        out += [f"prompt_selfattention.{i}.self_attn" for i in range(1, n)]
+    return out
+
+
+def token_legend(cfg: ModelConfig) -> List[str]:
+    """What each of the T modal tokens is, in the order the reference concatenates them (longvit_adapter.py:258-266; the clinical
+    variant puts its token first, 568-580): ["clinical"?, "task"?, "gene_cls"?, "gene:0", ..., "gene:{final_groups - 1}"]."""
+    return ((["clinical"] if cfg.clinical else []) + (["task"] if cfg.is_multi else []) + (["gene_cls"] if cfg.has_gene_cls else [])
+            + [f"gene:{g}" for g in range(cfg.gene.final_groups)])
+
+
 def sincos_1d_table(ngrids: int, dim: int) -> np.ndarray:
     """1-D sin-cos table [ngrids, dim] in float64 -> float32, following pos_embed.py:62-81.
 

@@ -643,6 +643,151 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------- attention maps (forward only) ---
+// The head-averaged softmax of each adapter attention (nn.MultiheadAttention's `need_weights` output), recomputed in one streaming
+// pass from what the forward already keeps: the fp16 operands and the row log-sum-exp.  The scores are rounded exactly as the
+// forward rounds them, so every row of every head sums to one against the saved LSE.
+constexpr int PBR = 128;          // keys (extractor) / patch rows (injector) per workgroup: 4 waves x 32
+
+// Extractor: w[b, t, l] = 1/12 sum_h exp(s_bthl - lse_bth), s = fp16(q / 4) . fp16(k) (extract_attn_fwd's rounding).
+// grid (ceil(L / 128), B); wave = 32 keys (key = lane & 31).  Per head one 32x32x16 MFMA per 32-token block with -lse as the
+// initial accumulator (extract_attn_bwd phase 1); the exp is summed over the heads in registers and every element is stored
+// once (a store instruction writes two 128-byte rows).  LDS: -lse [12][TB] and fp16(q / 4) [12][TB][KP], all reads 16 bytes wide.
+__global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
+                                                                 const float* __restrict__ lse, int T, int L, float* __restrict__ w) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int ntb = (T + 31) / 32, TB = ntb * 32;
+  float* nls = smem;                                      // [12][TB]      -lse; -1e30 past T
+  h16* qsh = reinterpret_cast<h16*>(nls + AH * TB);       // [12][TB][KP]  q / 4 (fp16); zero past T
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
+  for (int i = tid; i < TB * AE; i += 256) {
+    const int t = i / AE, e = i % AE;
+    qsh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? q[((long)b * T + t) * AE + e] * ASCALE : 0.f);
+  }
+  for (int i = tid; i < TB * AH; i += 256) {
+    const int t = i / AH, h = i % AH;
+    nls[h * TB + t] = t < T ? -lse[((long)b * T + t) * AH + h] : -1.0e30f;
+  }
+  __syncthreads();
+  const int key = blockIdx.x * PBR + wave * 32 + l31;
+  const bool valid = key < L;
+  const h16* row = kv + ((long)b * L + (valid ? key : 0)) * (2 * AE) + 8 * hh;
+  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x16 acc[TMAX / 32];
+#pragma unroll
+  for (int tb = 0; tb < TMAX / 32; ++tb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
+  for (int h = 0; h < AH; ++h) {
+    const h16x8 kf = valid ? ldg8(row + h * AD) : zero8;     // B operand: K^T[d = 8 hh + j][key]
+#pragma unroll
+    for (int tb = 0; tb < TMAX / 32; ++tb) {
+      if (tb < ntb) {
+        f32x16 sc;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh
+          const f32x4 l4 = *reinterpret_cast<const f32x4*>(&nls[h * TB + tb * 32 + 8 * g4 + 4 * hh]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sc[4 * g4 + e] = l4[e];
+        }
+        const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(h * TB + tb * 32 + l31) * KP + 8 * hh]);
+        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf, sc, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(sc[i]);
+      }
+    }
+  }
+  if (valid) {
+    const float inv = 1.0f / AH;
+#pragma unroll
+    for (int tb = 0; tb < TMAX / 32; ++tb) {
+      if (tb < ntb) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          if (t < T) w[((long)b * T + t) * L + key] = acc[tb][i] * inv;
+        }
+      }
+    }
+  }
+}
+
+// Injector: w[m, t] = 1/12 sum_h exp(s_mht / 4 - lse_mh), s = fp16(k) . q (inject_attn_fwd's rounding; its lse is natural-log).
+// grid (ceil(rows_per_pass / 128), B); wave = 32 patch rows (row = lane & 31).  Per head S^T = K . Q^T, one 32x32x16 MFMA per
+// 32-token block (K rows from an fp16 LDS image of all 12 heads, 16-byte reads).  The [128 rows][T] tile then goes through LDS
+// (4-byte writes, a barrier, 4-byte reads; odd row stride) and leaves as one contiguous, coalesced run of the [M, T] output.
+MT_DEVINL int probs_stride(int T) { return T | 1; }
+__global__ __launch_bounds__(256) void inject_attn_probs_kernel(const h16* __restrict__ q, int rows_per_pass, const float* __restrict__ k,
+                                                                const float* __restrict__ lse, int T, float* __restrict__ w) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int ntb = (T + 31) / 32, TB = ntb * 32;
+  h16* ksh = reinterpret_cast<h16*>(smem);                // [12][TB][KP]  fp16(k); zero past T
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
+  for (int i = tid; i < TB * AE; i += 256) {
+    const int t = i / AE, e = i % AE;
+    ksh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? k[((long)b * T + t) * AE + e] : 0.f);
+  }
+  __syncthreads();
+  const int r0 = blockIdx.x * PBR, rl = wave * 32 + l31;
+  const bool valid = r0 + rl < rows_per_pass;
+  const long m = (long)b * rows_per_pass + (valid ? r0 + rl : 0);
+  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f32x16 acc[TMAX / 32];
+#pragma unroll
+  for (int tb = 0; tb < TMAX / 32; ++tb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
+  for (int h = 0; h < AH; ++h) {
+    const h16x8 qf = valid ? ldg8(q + m * AE + h * AD + 8 * hh) : zero8;     // B operand: Q^T[d = 8 hh + j][row]
+    const float nl = valid ? -lse[m * AH + h] : 0.f;
+#pragma unroll
+    for (int tb = 0; tb < TMAX / 32; ++tb) {
+      if (tb < ntb) {
+        f32x16 sc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) sc[i] = 0.f;
+        const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(h * TB + tb * 32 + l31) * KP + 8 * hh]);
+        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, sc, 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(fmaf(sc[i], ASCALE, nl));
+      }
+    }
+  }
+  __syncthreads();                  // every wave is done with the K image: its storage takes the output tile
+  const int S = probs_stride(T);
+  float* osh = smem;                // [128][S]
+  const float inv = 1.0f / AH;
+  if (valid) {
+#pragma unroll
+    for (int tb = 0; tb < TMAX / 32; ++tb) {
+      if (tb < ntb) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh, column = the lane's row
+          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          if (t < T) osh[rl * S + t] = acc[tb][i] * inv;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int n = min(PBR, rows_per_pass - r0) * T;
+  float* dst = w + ((long)b * rows_per_pass + r0) * T;
+  for (int e = tid; e < n; e += 256) dst[e] = osh[(e / T) * S + e % T];
+}
+
+// Prompt self-attention: out[b, i, j] = mean over the heads of token_mha_fwd's probs [B, heads, T, T].
+__global__ void token_probs_mean_kernel(const float* __restrict__ probs, int B, int heads, int T, float* __restrict__ out) {
+  const long n = (long)T * T;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)B * n) return;
+  const long b = e / n, r = e % n;
+  float s = 0.f;
+  for (int h = 0; h < heads; ++h) s += probs[(b * heads + h) * n + r];
+  out[e] = s / (float)heads;
+}
+
 }  // namespace
 
 extern "C" int mt_inject_attn_fwd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T,
@@ -743,6 +888,48 @@ extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, 
   else
     hipLaunchKernelGGL(token_mha_bwd_kernel<false>, dim3(heads, B), dim3(512), shm, (hipStream_t)stream, q, k, v, probs, dout, T, E,
                        heads, dq, dk, dv);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_extract_attn_probs(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, float* w,
+                                     mt_stream_t stream) {
+  if (!q || !kv || !lse || !w || B < 1 || T < 1 || T > TMAX || L < 1) return MT_ERR_BAD_ARG;
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t shm = sizeof(float) * AH * TBk + sizeof(h16) * (size_t)AH * TBk * KP;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)extract_attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(extract_attn_probs_kernel, dim3(cdiv(L, PBR), B), dim3(256), shm, (hipStream_t)stream, q, (const h16*)kv, lse,
+                     T, L, w);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_inject_attn_probs(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, float* w,
+                                    mt_stream_t stream) {
+  if (!q || !k || !lse || !w || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX) return MT_ERR_BAD_ARG;
+  const int B = M / rows_per_pass;
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t kimg = sizeof(h16) * (size_t)AH * TBk * KP, otile = sizeof(float) * (size_t)PBR * (T | 1);
+  const size_t shm = kimg > otile ? kimg : otile;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)inject_attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(inject_attn_probs_kernel, dim3(cdiv(rows_per_pass, PBR), B), dim3(256), shm, (hipStream_t)stream, (const h16*)q,
+                     rows_per_pass, k, lse, T, w);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_token_probs_mean(const float* probs, int B, int heads, int T, float* out, mt_stream_t stream) {
+  if (!probs || !out || B < 1 || heads < 1 || T < 1 || T > TMAX) return MT_ERR_BAD_ARG;
+  const long n = (long)B * T * T;
+  hipLaunchKernelGGL(token_probs_mean_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, probs, B, heads, T, out);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from ._lib import rowmap
-from .config import ModelConfig, branch_table, coords_to_rowcol, segment_lengths, sincos_1d_table, DILATED_RATIOS
+from .config import ModelConfig, attention_sites, branch_table, coords_to_rowcol, segment_lengths, sincos_1d_table, DILATED_RATIOS
 from .synth import param_specs
 from .tape import Param, Tape, Var
 
@@ -179,6 +179,7 @@ class Engine:
         self._pin_next = 0
         self.collect_taps = False      # tests: keep cls / token states after every interaction block
         self.taps: Dict[str, torch.Tensor] = {}
+        self._maps: Dict[str, torch.Tensor] = {}      # attention maps requested by the forward in progress (site -> destination)
         self.T = cfg.num_tokens
         self._mean_w = torch.full((max(self.T, 2),), 1.0 / max(1, cfg.gene.final_groups), device=self.device)
         # pathway networks (gene_networks.{i}.{0,1}.0.*): offset tables into the flat parameter / gradient buffers
@@ -415,7 +416,7 @@ class Engine:
     def forward(self, x: torch.Tensor, coords, genes: Sequence[torch.Tensor], task_onehots: torch.Tensor,
                 need_grad: bool = True, fresh: bool = False, staged: bool = False, geometry=None,
                 clinical: Optional[torch.Tensor] = None, share: Optional[dict] = None, tape: Optional[Tape] = None,
-                site_group: int = 0, ws_slot: int = 0) -> torch.Tensor:
+                site_group: int = 0, ws_slot: int = 0, attn_maps: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
         """x [L, in_chans] (or [1,L,in]); coords [L,2] (host or device); genes: list of [1, n_i]; task_onehots [B, num_tasks].
         Returns logits [B, output_dim] (fp32, device).  fresh=True gives this call its own tape and workspace so that
         several forwards can precede one backward (the reference calls the model 3x before loss.backward(), TM:175-177);
@@ -423,7 +424,9 @@ class Engine:
         stage_inputs() into this geometry's workspace (hipGraph replay path: no host work inside the step).
         share (fresh calls of the module API): a dict owned by the caller for the calls of ONE slide -- the first call leaves the
         task-independent patch embedding in it (`x0`: input cast + patch-embed GEMM + positional term, LVA:232-242), the later
-        ones take it from there instead of recomputing it (the reference recomputes it for every task id)."""
+        ones take it from there instead of recomputing it (the reference recomputes it for every task id).
+        attn_maps (forward-only calls): {site: destination} for some of attention_sites(cfg) -- each named adapter attention writes
+        its head-averaged softmax there right behind its attention core (shapes: attention_map_shapes)."""
         cfg, dev, t = self.cfg, self.device, self.store.tensors
         if self.store.sync is not None:
             self.store.sync()         # parameters complete on this rank before anything reads them (no-op when nothing is pending)
@@ -440,6 +443,7 @@ class Engine:
                              "datasets never produce an empty one, data_utils/datasets.py:213-285)")
         N, D, Fd, E, T = L + 1, cfg.embed_dim, cfg.ffn_dim, cfg.adapter_dim, self.T
         M, Mp = B * N, B * L
+        self._maps = self._check_maps(attn_maps, B, L, need_grad) if attn_maps else {}
         ws = self._workspace(B, L, fresh=fresh, slot=ws_slot)
         # fresh: this call owns its tape (several forwards alive at once); the engine's long-lived tape -- whose gradient
         # arena captured graphs point into -- is put back before returning
@@ -536,6 +540,7 @@ class Engine:
         self._logits = logits
         self.last_call = (tape, logits)
         self.tape = self._main_tape
+        self._maps = {}
         return logits.data
 
     def prepare_shared(self, x, coords, share: dict):
@@ -552,6 +557,36 @@ class Engine:
         self.stage_inputs(x, coords, ws)
         Engine._embed_patches(self, None, None, ws, True, L)
         share["x0"], share["_x0_keep"] = ws["x0"], ws
+
+    # -- attention maps (forward only): the `need_weights` output of the reference's adapter attentions
+    def attention_map_shapes(self, B: int, L: int) -> Dict[str, tuple]:
+        """site -> shape of its map for B task passes over L patches: injector [B, L, T] (patch rows over tokens), extractor
+        [B, T, L] (tokens over patch rows), prompt self-attention [B, T, T]."""
+        if hasattr(self, "forward_slide"):
+            raise NotImplementedError("attention maps of the TITAN configuration are not supported: its adapters attend over gridded "
+                                      "cells, and drawing them on the slide needs the cell-to-coordinate map")
+        T = self.T
+        return {s: (B, T, T) if s.startswith("prompt_") else (B, L, T) if ".injector." in s else (B, T, L)
+                for s in attention_sites(self.cfg)}
+
+    def new_attention_maps(self, sites: Sequence[str], B: int, L: int) -> Dict[str, torch.Tensor]:
+        """Fresh destinations {site: fp32 tensor} for a forward(attn_maps=...) request."""
+        shapes = self.attention_map_shapes(B, L)
+        bad = [s for s in sites if s not in shapes]
+        if bad:
+            raise ValueError(f"unknown attention site(s) {bad}; this model has {list(shapes)}")
+        return {s: torch.empty(shapes[s], dtype=F32, device=self.device) for s in sites}
+
+    def _check_maps(self, maps: Dict[str, torch.Tensor], B: int, L: int, need_grad: bool) -> Dict[str, torch.Tensor]:
+        if need_grad:
+            raise ValueError("attention maps come from the forward-only (eval) pass: request them with need_grad=False")
+        shapes = self.attention_map_shapes(B, L)
+        for s, w in maps.items():
+            if s not in shapes:
+                raise ValueError(f"unknown attention site {s!r}; this model has {list(shapes)}")
+            if tuple(w.shape) != shapes[s] or w.dtype != F32 or not w.is_contiguous() or w.device.type != self.device.type:
+                raise ValueError(f"{s}: expected a contiguous fp32 {shapes[s]} tensor on {self.device}, got {w.dtype} {tuple(w.shape)}")
+        return maps
 
     # -- overridable pieces of the image side (modaltune_amd/titan.py plugs the TITAN backbone in here)
     def _attention_plan(self, N: int, B: int):
@@ -785,7 +820,7 @@ class Engine:
         Wq, Wk, Wv, bq, bk, bv = self._mha_in(pref + "self_attn.")
         q1, k, v = tape.linear_group([(kin, P(pref + "q_proj.weight"), P(pref + "q_proj.bias")), (kin, Wk, bk), (tn, Wv, bv)])
         q = tape.linear(q1, Wq, bq)
-        a = tape.token_mha(q, k, v, self.cfg.num_heads)
+        a = tape.token_mha(q, k, v, self.cfg.num_heads, mean_probs=self._maps.get(pref + "self_attn"))
         o = tape.linear(a, P(pref + "self_attn.out_proj.weight"), P(pref + "self_attn.out_proj.bias"))
         return tape.linear(o, P(pref + "output_proj.weight"), P(pref + "output_proj.bias"), resid=c)
 
@@ -814,6 +849,9 @@ class Engine:
         a = torch.empty(Mp, E, dtype=H16, device=dev)
         alse = torch.empty(Mp, 12, dtype=F32, device=dev)
         ops.inject_attn_fwd(q2, k.data, v.data, a, Mp, L, T, lse=alse)
+        wmap = self._maps.get(ap + "multihead_attn")
+        if wmap is not None:
+            ops.inject_attn_probs(q2, k.data, alse, wmap, Mp, L, T)
         o1 = torch.empty(Mp, E, dtype=H16, device=dev)
         ops.gemm_nt(a, w16[ap + "out_in"].w, o1, Mp, E, E, bias=t[ap + "multihead_attn.out_proj.bias"])
         ops.gemm_nt(o1, w16[ap + "output_proj"].w, hin, Mp, D, E, cmap=pm, epilogue=ops.EPI_INJECT, bias=t[ap + "output_proj.bias"],
@@ -963,6 +1001,9 @@ class Engine:
         pa = tape.new(B * 12 * nsplit * T * 16)
         pml = tape.new(B * 12 * nsplit * T * 2)
         ops.extract_attn_fwd(q2.data, kv, out.data, lse, pa, pml, B, T, L, nsplit)
+        wmap = self._maps.get(ap + "multihead_attn")
+        if wmap is not None:
+            ops.extract_attn_probs(q2.data, kv, lse, wmap, B, T, L)
 
         def bwd_core():
             if out.grad is None:

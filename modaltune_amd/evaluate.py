@@ -15,6 +15,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .config import attention_sites, coords_to_rowcol
 from .engine import Engine, F32
 
 
@@ -34,11 +35,24 @@ class EmbeddingExtractor:
     """Forward-only pass over slides with static buffers + hipGraph replay per bag geometry: an LRU of captured geometries, a
     geometry is captured once it has come back `capture_after` times (real data has a new bag length almost every slide: those run
     the eager schedule).  TITAN configuration: the gridding and its one host read-back (the token count) run eagerly into static
-    buffers, the capture starts at the token gather and is keyed on (patches, TOKENS) -- as TrainStep.step_graphed does."""
+    buffers, the capture starts at the token gather and is keyed on (patches, TOKENS) -- as TrainStep.step_graphed does.
+
+    attention: None (default: logits only), True (every site of config.attention_sites) or a list of site names -- the reference's
+    module paths of the adapter attentions.  With a request, a call returns (logits, {site: map}): the head-averaged attention
+    weights that a forward hook on those nn.MultiheadAttention modules reads as output[1] in the reference, computed by the same
+    forward (batched, two pass groups or graph replay alike) right behind each attention core.  Not for TITAN models."""
 
     def __init__(self, engine: Engine, task_ids: Sequence[int] = (0, 1, 2), graphed: bool = True, graph_cache_size: int = 8,
-                 capture_after: int = 1):
+                 capture_after: int = 1, attention=None):
         self.engine, self.dev, self.graphed = engine, engine.device, graphed
+        self.sites: Optional[Tuple[str, ...]] = None
+        if attention is not None and attention is not False:
+            engine.attention_map_shapes(1, 1)                   # (raises NotImplementedError for the TITAN engine)
+            every = attention_sites(engine.cfg)
+            self.sites = tuple(every) if attention is True else tuple(attention)
+            bad = [s for s in self.sites if s not in every]
+            if bad or not self.sites:
+                raise ValueError(f"unknown attention site(s) {bad}; this model has {every}")
         nt = max(1, engine.cfg.multi_task)
         self.onehots = torch.eye(nt, dtype=F32, device=self.dev)[list(task_ids)].contiguous()
         self.graph_cache_size, self.capture_after = int(graph_cache_size), int(capture_after)
@@ -65,6 +79,7 @@ class EmbeddingExtractor:
         eng._embed_patches(None, None, ws0, True, L)
         share = {"x0": ws0["x0"]}
         out = torch.empty(B, eng.cfg.output_dim, dtype=F32, device=self.dev)
+        maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None      # (each group writes its rows)
         main = torch.cuda.current_stream()
         fork = torch.cuda.Event()
         fork.record(main)
@@ -73,11 +88,19 @@ class EmbeddingExtractor:
             st.wait_event(fork)
             with torch.cuda.stream(st):
                 lg = eng.forward(None, None, self._sgenes, self.onehots[lo:hi], need_grad=False, staged=True, geometry=(hi - lo, L),
-                                 clinical=self._sclin, share=share, tape=self._tapes[gi], site_group=gi + 1)
+                                 clinical=self._sclin, share=share, tape=self._tapes[gi], site_group=gi + 1,
+                                 attn_maps={s: w[lo:hi] for s, w in maps.items()} if maps else None)
                 out[lo:hi].copy_(lg)
         for st in self._streams:
             main.wait_stream(st)
-        return out
+        return (out, maps) if maps else out
+
+    def _forward_batched(self, B: int, L: int):
+        eng = self.engine
+        maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None
+        lg = eng.forward(None, None, self._sgenes, self.onehots, need_grad=False, staged=True, geometry=(B, L), clinical=self._sclin,
+                         attn_maps=maps)
+        return (lg, maps) if maps else lg
 
     @property
     def _graph(self):
@@ -86,9 +109,10 @@ class EmbeddingExtractor:
         return live[-1] if live else None
 
     @torch.no_grad()
-    def __call__(self, x, coords, genes: Sequence[torch.Tensor], clinical=None) -> torch.Tensor:
+    def __call__(self, x, coords, genes: Sequence[torch.Tensor], clinical=None):
         """Logits (= the slide embeddings the probes consume) [len(task_ids), output_dim], on the device (a fresh
-        tensor per call: replays write a static buffer that is copied out)."""
+        tensor per call: replays write a static buffer that is copied out).  With an attention request: (logits, {site: map}),
+        the maps fresh tensors as well."""
         eng = self.engine
         titan = hasattr(eng, "forward_slide")
         if not eng._caches_ready:
@@ -103,7 +127,9 @@ class EmbeddingExtractor:
             if titan:
                 return eng.forward_slide(x, coords, list(genes), self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=False,
                                          clinical=clinical)
-            return eng.forward(x, coords, list(genes), self.onehots, need_grad=False, clinical=clinical)
+            maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None
+            lg = eng.forward(x, coords, list(genes), self.onehots, need_grad=False, clinical=clinical, attn_maps=maps)
+            return (lg, maps) if maps else lg
         gflat = genes.reshape(-1) if torch.is_tensor(genes) else torch.cat([g.reshape(-1) for g in genes])
         if titan:
             Lv = eng.stage_slide(x, coords, self.patch_size_lv0)      # eager gridding + the one read-back -> token count
@@ -127,7 +153,7 @@ class EmbeddingExtractor:
             self._sclin.copy_(clinical.reshape(1, -1), non_blocking=True)
         # the engine's generation is part of the key: a workspace that grew under another user of the engine (the trainer
         # shares the B = 3 storage), rebuilt weight caches (load_state_dict) or a stochastic toggle retire the captures
-        key = (L, Lv, eng.generation)
+        key = (L, Lv, eng.generation, self.sites)           # (the maps are static outputs of the capture, like the logits)
         for k in [k for k in self._cache if k[2] != eng.generation]:
             del self._cache[k]
         if titan:
@@ -136,8 +162,7 @@ class EmbeddingExtractor:
         elif split:
             run = lambda: self._forward_groups(B, L)
         else:
-            run = lambda: eng.forward(None, None, self._sgenes, self.onehots, need_grad=False, staged=True, geometry=(B, L),
-                                      clinical=self._sclin)
+            run = lambda: self._forward_batched(B, L)
         ent = self._cache.get(key)
         if ent is None:
             seen = self._visits.get(key, 0)
@@ -159,7 +184,33 @@ class EmbeddingExtractor:
             self._cache.move_to_end(key)
         ent["graph"].replay()
         self.graph_replays += 1
+        if self.sites:
+            lg, maps = ent["out"]
+            return lg.clone(), {s: w.clone() for s, w in maps.items()}
         return ent["out"].clone()
+
+
+def attention_to_grid(weights, coords, tile: float = 256.0) -> np.ndarray:
+    """One attention map over the patches of a slide (weights [L]: a row of an extractor map, or an injector map's column for one
+    token) laid out on the slide's patch grid: cell (row, col) = config.coords_to_rowcol(coords, tile) -- the grid the positional
+    embedding uses (slide_encoder.py:198-211) -- with NaN where there is no patch, and the mean where several patches share a cell.
+    Returns a float64 array [max row + 1, max col + 1] (host only; plt.imshow draws it as the heatmap)."""
+    w = weights.detach().double().cpu().numpy() if torch.is_tensor(weights) else np.asarray(weights, dtype=np.float64)
+    c = coords.detach().cpu().numpy() if torch.is_tensor(coords) else np.asarray(coords)
+    w, c = w.reshape(-1), c.reshape(-1, 2)
+    if w.shape[0] != c.shape[0]:
+        raise ValueError(f"{w.shape[0]} weights for {c.shape[0]} patch coordinates")
+    if w.shape[0] == 0:
+        return np.zeros((0, 0))
+    r, col = coords_to_rowcol(c, float(tile))
+    if int(min(r.min(), col.min())) < 0:
+        raise ValueError("negative patch coordinates")
+    shape = (int(r.max()) + 1, int(col.max()) + 1)
+    tot, cnt = np.zeros(shape), np.zeros(shape)
+    np.add.at(tot, (r, col), w)
+    np.add.at(cnt, (r, col), 1.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(cnt > 0, tot / cnt, np.nan)
 
 
 def get_features(extractor: EmbeddingExtractor, slides: Iterable[Dict]) -> Tuple[np.ndarray, List]:

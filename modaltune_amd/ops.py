@@ -357,6 +357,24 @@ def token_mha_bwd(q, k, v, probs, dout, dq, dk, dv, B, T, E, heads):
                                        _s()), "token_mha_bwd")
 
 
+def extract_attn_probs(q, kv, lse, w, B, T, L):
+    """w [B, T, L] fp32: head-averaged attention of the extractor's token queries over the patch rows (lse of extract_attn_fwd)."""
+    _need(w, torch.float32, "w")
+    check(_lib.load().mt_extract_attn_probs(_p(q), _p(kv), _p(lse), B, T, L, _p(w), _s()), "extract_attn_probs")
+
+
+def inject_attn_probs(q, k, lse, w, M, rows_per_pass, T):
+    """w [M, T] fp32: head-averaged attention of the injector's patch rows over the tokens (lse of inject_attn_fwd)."""
+    _need(w, torch.float32, "w")
+    check(_lib.load().mt_inject_attn_probs(_p(q), M, rows_per_pass, _p(k), _p(lse), T, _p(w), _s()), "inject_attn_probs")
+
+
+def token_probs_mean(probs, out, B, heads, T):
+    """out [B, T, T] fp32: token_mha_fwd's probs [B, heads, T, T] averaged over the heads."""
+    _need(out, torch.float32, "out")
+    check(_lib.load().mt_token_probs_mean(_p(probs), B, heads, T, _p(out), _s()), "token_probs_mean")
+
+
 def cast_f32_to_f16(x, y, n=None, drop=None, D=0):
     check(_lib.load().mt_cast_f32_to_f16(_p(x), _p(y), n if n is not None else x.numel(), _dr(drop), D, _s()), "cast")
 

@@ -339,11 +339,14 @@ class Tape:
         self.record(bwd)
         return y
 
-    def token_mha(self, q: Var, k: Var, v: Var, heads: int) -> Var:
+    def token_mha(self, q: Var, k: Var, v: Var, heads: int, mean_probs: Optional[torch.Tensor] = None) -> Var:
+        """mean_probs [B, T, T] (optional): receives the head-averaged attention weights (the engine's attention maps)."""
         Bb, T, E = q.data.shape
         out = Var(self.new(Bb, T, E))
         probs = self.new(Bb, heads, T, T)
         ops.token_mha_fwd(q.data, k.data, v.data, out.data, probs, Bb, T, E, heads)
+        if mean_probs is not None:
+            ops.token_probs_mean(probs, mean_probs, Bb, heads, T)
 
         def bwd():
             if out.grad is None:
