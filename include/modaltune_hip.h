@@ -433,7 +433,8 @@ int mt_adamw_step(float* p, const float* g, float* m, float* v, long n, double l
                   const float* scale, int* found_inf, const float* lr_dev /* device scalar: the schedule's current
                   learning rate (overrides lr; a captured graph replays with whatever it holds -- the reference steps
                   GradualWarmupScheduler + CosineAnnealingLR every epoch, TM:151-154,242) or NULL */, mt_stream_t stream);
-/* GradScaler.update on device (TM:237): *found_inf ? scale *= backoff : (every `interval` clean steps scale *= growth) */
+/* GradScaler.update on device (TM:237): *found_inf ? scale *= backoff : (every `interval` clean steps scale *= growth,
+ * unless the product is not finite: then the scale stays, as in torch._amp_update_scale_); *found_inf is cleared */
 int mt_scaler_update(float* scale, int* growth_tracker, int* found_inf, int* step_dev /* ++ on a clean step, or NULL */,
                      float growth, float backoff, int interval, mt_stream_t stream);
 int mt_check_finite(const float* g, long n, int* found_inf, mt_stream_t stream);
@@ -445,7 +446,8 @@ int mt_mfma_probe(float* sink, int workgroups, int iters, mt_stream_t stream);
 /* ---------------------------------------------------------- module bridge / input boundary --------- */
 /* s[0] = target / max|x|, s[1] = 1 / s[0] (both 1 when the maximum is 0 or not finite): device-side rescale of the
  * gradient torch hands to the nn.Module bridge (loss.backward(), TM:235) into the fp16 range of the activation-gradient
- * stream, without a host read-back. */
+ * stream, without a host read-back.  s[0] is clamped to [2^-126, 2^126] (a maximum below ~target / FLT_MAX would otherwise
+ * give s[0] = inf, s[1] = 0): s[0] and s[1] are finite, positive normal numbers for every input. */
 int mt_absmax_scale(const float* x, long n, float target, float* s, mt_stream_t stream);
 /* y[i] = a[i] + (*alpha) * b[i] with alpha a DEVICE scalar (a may be NULL: y = (*alpha) * b) */
 int mt_axpy_dev(const float* a, const float* b, const float* alpha, float* y, long n, mt_stream_t stream);

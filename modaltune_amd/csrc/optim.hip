@@ -101,13 +101,18 @@ __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restric
   for (int j = threadIdx.x; j < O; j += 256) y[(long)blockIdx.x * O + j] = xr[j] * inv;
 }
 
-// torch.cuda.amp.GradScaler.update (TM:107,237): backoff 0.5 on overflow, x2 after `interval` clean steps.
+// torch.cuda.amp.GradScaler.update (TM:107,237): backoff 0.5 on overflow, x2 after `interval` clean steps.  As in
+// torch._amp_update_scale_, a growth whose product is not finite keeps the old scale (the tracker still restarts).
 __global__ void scaler_update_kernel(float* scale, int* tracker, int* found_inf, int* step_dev, float growth, float backoff, int interval) {
   if (threadIdx.x || blockIdx.x) return;
   if (*found_inf) { *scale *= backoff; *tracker = 0; }
   else {
     if (step_dev) ++(*step_dev);
-    if (++(*tracker) >= interval) { *scale *= growth; *tracker = 0; }
+    if (++(*tracker) >= interval) {
+      const float grown = *scale * growth;
+      if (isfinite(grown)) *scale = grown;
+      *tracker = 0;
+    }
   }
   *found_inf = 0;
 }
@@ -115,6 +120,9 @@ __global__ void scaler_update_kernel(float* scale, int* tracker, int* found_inf,
 
 // s[0] = target / max|x| (1 when the maximum is 0 or not finite), s[1] = 1 / s[0]: the device-side loss-scale of the
 // nn.Module bridge (no host read-back of the incoming gradient's range).  One workgroup; n is a few hundred.
+// s[0] is CLAMPED to [2^-126, 2^126]: a maximum below ~target / FLT_MAX (a nearly converged loss) would make target / max|x|
+// +inf and s[1] zero (0 * inf = NaN gradients); at the clamp the factor is a power of two, both s[0] and s[1] are normal
+// numbers and scaling by them is exact.  So s[0] and s[1] are finite and positive for every input.
 __global__ __launch_bounds__(256) void absmax_scale_kernel(const float* __restrict__ x, long n, float target, float* __restrict__ s) {
   __shared__ float red[256];
   float m = 0.f;
@@ -124,7 +132,7 @@ __global__ __launch_bounds__(256) void absmax_scale_kernel(const float* __restri
   for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + k]); __syncthreads(); }
   if (threadIdx.x == 0) {
     const float a = red[0];
-    const float sc = (a > 0.f && a <= 3.0e38f) ? target / a : 1.0f;
+    const float sc = (a > 0.f && a <= 3.0e38f) ? fminf(fmaxf(target / a, 0x1p-126f), 0x1p126f) : 1.0f;
     s[0] = sc; s[1] = 1.0f / sc;
   }
 }

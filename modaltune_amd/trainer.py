@@ -44,6 +44,9 @@ class TrainStep:
         self.m = torch.zeros(n, dtype=F32, device=self.dev)
         self.v = torch.zeros(n, dtype=F32, device=self.dev)
         self.scale = torch.full((1,), float(init_scale), dtype=F32, device=self.dev)
+        # the loss scale the gradients now in the flat buffer were produced with (copied on the device where the loss reads
+        # `scale`: the scaler update behind an update=True step moves `scale` on to the NEXT step's value)
+        self.grad_scale = torch.full((1,), float(init_scale), dtype=F32, device=self.dev)
         self.tracker = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.found_inf = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self.growth_interval = growth_interval
@@ -268,6 +271,7 @@ class TrainStep:
             share = {"x0": ws0["x0"]}
         R, O = target.shape
         logits_all = torch.empty(R, O, dtype=F32, device=self.dev)
+        self.grad_scale.copy_(self.scale)
         main = torch.cuda.current_stream()
         fork = torch.cuda.Event()
         fork.record(main)
@@ -386,6 +390,7 @@ class TrainStep:
                                  clinical=clinical)
         self.last_logits = logits
         R, O = target.shape
+        self.grad_scale.copy_(self.scale)
         if logits.shape[0] == R:
             dlogits = torch.empty_like(logits)
             ops.distill_loss(logits, target, self.loss, dlogits, R, O, 1.0, self.scale)
@@ -667,7 +672,9 @@ class TrainStep:
         return v
 
     def unscaled_grads(self) -> Dict[str, torch.Tensor]:
-        s = float(self.scale)
+        """The last step's gradients divided by the loss scale THEY carry (`grad_scale`) -- not by `scale`, which after an
+        update=True step that backed off or grew is already the next step's.  After a skipped step they are not finite."""
+        s = float(self.grad_scale)
         return {k: g / s for k, g in self.engine.store.grads.items()}
 
 

@@ -55,6 +55,65 @@ def trainstep(rank, world, out):
              split=int(ts._pass_streams is not None), sharded=int(ts.reducer.sharded), backend=dist.get_backend())
 
 
+OVERFLOW_STEPS, OVERFLOW_AT = 6, 2          # the third step (index 2: a replay of the captured graphs) is the poisoned one
+
+
+def overflow(rank, world, out):
+    """OVERFLOW_STEPS data-parallel steps; at step index OVERFLOW_AT the LAST rank only feeds its slide with a NaN feature row (with
+    two ranks: rank 1; the one-rank rehearsal poisons its only rank).  Every rank must skip that step, back off identically and stay
+    bit-identical.  Recorded after every step: digests of the flat weights, of both moments and of the fp16 weight caches, the scale,
+    the growth tracker, the step count and the flag.  The moments of the sharded last bucket are updated by the rank that owns the
+    shard only, so the ranks are compared on the moments outside it (`m_common` / `v_common`); the full-buffer digests serve each
+    rank's own skip signature."""
+    import hashlib
+    from modaltune_amd.engine import Engine
+    from modaltune_amd.trainer import TrainStep
+    sizes = synth.toy_group_sizes()
+    cfg = _cfg()
+    eng = Engine(cfg, sizes, "cuda")
+    eng.load_state_dict(synth.synth_state_dict(cfg, sizes, SEED))
+    dp.broadcast_params_(eng.store.flat)
+    ts = TrainStep(eng, lr=1e-3, capture_after=1)
+    ts.set_projector(synth.projector_state(SEED))
+    x, coords, genes, text = _slide(rank, sizes)
+    x_bad = x.clone()
+    rows = x_bad.view(-1, x_bad.shape[-1])
+    rows[rows.shape[0] // 2, :] = float("nan")
+    n = eng.store.n_flat
+    common = torch.ones(n, dtype=torch.bool, device="cuda")
+    for o, s, _ in ts.reducer._rs:
+        common[o:o + world * s] = False
+
+    def digest(*tensors):
+        h = hashlib.sha1()
+        for t in tensors:
+            h.update(t.detach().contiguous().cpu().numpy().tobytes())
+        return h.hexdigest()
+
+    rec = {k: [] for k in ("loss", "flat", "m", "v", "m_common", "v_common", "caches", "scale", "tracker", "step_dev", "found_inf", "finite")}
+    for i in range(OVERFLOW_STEPS):
+        poisoned = i == OVERFLOW_AT and rank == world - 1
+        rec["loss"].append(float(ts.step_graphed(x_bad if poisoned else x, coords, genes, text)))
+        if eng.store.sync is not None:
+            eng.store.sync()             # the sharded parameter all-gather of this step
+        torch.cuda.synchronize()
+        rec["flat"].append(digest(eng.store.flat))
+        rec["m"].append(digest(ts.m))
+        rec["v"].append(digest(ts.v))
+        rec["m_common"].append(digest(ts.m[common]))
+        rec["v_common"].append(digest(ts.v[common]))
+        rec["caches"].append(digest(*[t for w in eng._train16.values() for t in (w.w, w.wt) if t is not None]))
+        rec["scale"].append(float(ts.scale))
+        rec["tracker"].append(int(ts.tracker))
+        rec["step_dev"].append(int(ts.step_dev))
+        rec["found_inf"].append(int(ts.found_inf))
+        rec["finite"].append(int(bool(torch.isfinite(eng.store.flat).all()) and bool(torch.isfinite(ts.m).all()) and bool(torch.isfinite(ts.v).all())))
+    eng.check_inputs()
+    np.savez(out, final_flat=eng.store.flat.cpu().numpy(), replays=ts.graph_replays, sharded=int(ts.reducer.sharded),
+             split=int(ts._pass_streams is not None), common=int(common.sum()), n_flat=n, backend=dist.get_backend(),
+             **{k: np.array(v) for k, v in rec.items()})
+
+
 def seqpar_calls(rank, world, out):
     """The two collectives of modaltune_amd.seqpar on the process group as it is (device tensors as they are on `nccl`): with one rank
     both are identities -- what is checked is that RCCL accepts the calls (flat fp16 views, split sizes) and returns the payload."""
@@ -194,6 +253,7 @@ if __name__ == "__main__":
         torch.cuda.set_device(0)
         dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        {"trainstep": trainstep, "ddp_module": ddp_module, "ragged": ragged, "titan": titan, "seqpar_calls": seqpar_calls}[mode](rank, world, out)
+        {"trainstep": trainstep, "ddp_module": ddp_module, "ragged": ragged, "titan": titan, "seqpar_calls": seqpar_calls,
+         "overflow": overflow}[mode](rank, world, out)
     finally:
         dist.destroy_process_group()

@@ -232,6 +232,84 @@ def _check_trainstep(results, nseg=4):
     assert moved.mean() > 0.5e-3                                                   # (the weights did move)
 
 
+def _check_overflow(results):
+    """dp_worker.overflow: the last rank's slide carries a NaN feature row at step index OVERFLOW_AT.  The all-reduced sums (and the
+    MAX-reduced flag of the sharded bucket) make EVERY rank skip: bit-identical ranks after every step, the skip signature on each rank,
+    5 counted steps, and final weights equal to a single-process run of the five clean averaged steps (_check_trainstep's bars)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dp_worker as W
+    from modaltune_amd import synth
+    from modaltune_amd.engine import Engine
+    from modaltune_amd.trainer import TrainStep
+    world, at, steps = len(results), W.OVERFLOW_AT, W.OVERFLOW_STEPS
+    clean = steps - 1
+    for r in results:
+        assert int(r["replays"]) == steps - 1 and int(r["sharded"]) == 1 and 0 < int(r["common"]) < int(r["n_flat"])
+        assert list(r["step_dev"]) == [min(i + 1, at) if i <= at else i for i in range(steps)], list(r["step_dev"])
+        assert int(r["step_dev"][-1]) == clean == 5
+        # the skip signature
+        for k in ("flat", "m", "v", "caches"):
+            assert str(r[k][at]) == str(r[k][at - 1]), (k, "moved on the skipped step")
+            assert str(r[k][at + 1]) != str(r[k][at]), (k, "did not move on the step behind it")
+        assert float(r["scale"][at - 1]) == 2.0 ** 15 and float(r["scale"][at]) == 2.0 ** 14 and float(r["scale"][-1]) == 2.0 ** 14
+        assert int(r["tracker"][at]) == 0 and list(r["tracker"]) == [i + 1 if i < at else i - at for i in range(steps)], list(r["tracker"])
+        assert not r["found_inf"].any() and r["finite"].all()
+        assert np.isfinite(np.delete(r["loss"], at)).all()
+    assert np.isnan(results[-1]["loss"][at])                                      # the poisoned rank's own loss
+    if world > 1:
+        assert np.isfinite(results[0]["loss"][at])                                # ... and the other rank's slide was clean
+        for k in ("flat", "m_common", "v_common", "caches", "scale", "tracker", "step_dev"):
+            assert [str(a) for a in results[0][k]] == [str(a) for a in results[1][k]], (k, "the ranks diverged")
+        assert np.array_equal(results[0]["final_flat"], results[1]["final_flat"])
+    # single-process reference: the five clean steps on the ranks' summed gradients, AdamW with grad_mult = 1 / world
+    sizes = synth.toy_group_sizes()
+    cfg = W._cfg()
+    eng = Engine(cfg, sizes, "cuda")
+    eng.load_state_dict(synth.synth_state_dict(cfg, sizes, W.SEED))
+    ts = TrainStep(eng, lr=1e-3)
+    ts.set_projector(synth.projector_state(W.SEED))
+    slides = [W._slide(r, sizes) for r in range(world)]
+    for _ in range(clean):
+        acc = torch.zeros_like(eng.store.flat_grad)
+        for x, coords, genes, text in slides:
+            ts.step(x, coords, genes, text, update=False)
+            acc += eng.store.flat_grad
+        eng.store.flat_grad.copy_(acc)
+        ts._adam_and_refresh(world)
+    torch.cuda.synchronize()
+    assert int(ts.step_dev) == clean
+    ref = eng.store.flat.cpu().numpy()
+    d = np.abs(results[0]["final_flat"] - ref)
+    assert d.max() <= 2.0 * clean * 1e-3 + 1e-7
+    assert np.mean(d > 0.05 * 1e-3) < 0.02, (np.mean(d > 0.05 * 1e-3), d.max())
+    assert np.abs(ref - synth_flat(eng, cfg, sizes, W.SEED)).mean() > 0.5e-3        # (the weights did move)
+
+
+@pytest.mark.parametrize("split", [False, True])
+def test_two_rank_overflow_on_one_rank_skips_the_step_on_both(tmp_path, split):
+    """One rank's slide overflows, the other's does not (default schedule, and the pass groups forced on)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    res = _run_ranks("overflow", tmp_path, extra_env={"MT_SPLIT_PASSES": "force"} if split else None)
+    assert all(int(r["split"]) == int(split) for r in res)
+    _check_overflow(res)
+
+
+def test_one_rank_rccl_rehearsal_of_the_overflow_step(tmp_path):
+    """The same over a one-rank RCCL communicator (MT_DP_REHEARSE=1): the found_inf MAX all-reduce, the reduce-scatter of a NaN
+    gradient and the parameter all-gather behind a skipped AdamW run over RCCL."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    res = _run_ranks("overflow", tmp_path, world=1, backend="nccl", extra_env={"MT_DP_REHEARSE": "1"})
+    assert str(res[0]["backend"]) == "nccl"
+    _check_overflow(res)
+
+
+def test_two_rank_overflow_over_rccl(tmp_path):
+    _need_gpus(2)
+    _check_overflow(_run_ranks("overflow", tmp_path, backend="nccl"))
+
+
 def synth_flat(eng, cfg, sizes, seed):
     """The initial flat trainable buffer (state_dict order, 16-byte aligned slots)."""
     from modaltune_amd import synth

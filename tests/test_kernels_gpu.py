@@ -800,6 +800,229 @@ def test_distill_loss_and_adamw(ops):
     assert int(found) == 1 and torch.equal(p, before)
 
 
+# the same found_inf pattern drives the scaler and the optimiser tests: back-off, growth exactly at the interval, two skips in a row
+SKIP_PATTERN = [0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0]
+GRID_CAP_ADAMW = 4096 * 1024              # mt_adamw_step / mt_axpy_dev: 4096 workgroups x 256 threads, 4 elements each before the stride
+GRID_CAP_FINITE = 2048 * 1024             # mt_check_finite: 2048 workgroups
+
+
+@pytest.mark.parametrize("with_step", [True, False])
+@pytest.mark.parametrize("pattern,interval,tracker0", [(SKIP_PATTERN, 3, 0), ([0, 1, 0, 0, 1, 1, 0, 0], 1, 0),
+                                                       ([0, 0, 1, 0, 0, 0, 0], 2000, 0), ([0, 0, 0, 1, 0], 2000, 1997)])
+def test_scaler_update_matches_torch_amp_update_scale(ops, pattern, interval, tracker0, with_step):
+    """mt_scaler_update against torch._amp_update_scale_ on CPU tensors, call by call: scale and growth tracker `==` (every value is a
+    power of two), step_dev = number of clean calls so far, found_inf cleared by every call.  (tracker0 = 1997 at interval 2000: the
+    growth at exactly `interval` clean steps without 2000 launches.)"""
+    scale = torch.full((1,), 2.0 ** 15, device=DEV)
+    tracker = torch.full((1,), tracker0, dtype=torch.int32, device=DEV)
+    found = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = torch.zeros(1, dtype=torch.int32, device=DEV) if with_step else None
+    rs, rt = torch.full((1,), 2.0 ** 15), torch.full((1,), tracker0, dtype=torch.int32)
+    clean, seen = 0, set()
+    for i, f in enumerate(pattern):
+        found.fill_(f)
+        ops.scaler_update(scale, tracker, found, step, 2.0, 0.5, interval)
+        torch._amp_update_scale_(rs, rt, torch.tensor([float(f)]), 2.0, 0.5, interval)
+        clean += 1 - f
+        seen.add(float(rs))
+        assert float(scale) == float(rs) and int(tracker) == int(rt), (i, float(scale), float(rs), int(tracker), int(rt))
+        assert int(found) == 0, i
+        if with_step:
+            assert int(step) == clean, (i, int(step), clean)
+    assert len(seen) >= 2                         # (the pattern did move the scale)
+
+
+@pytest.mark.parametrize("scale0,found_inf", [(2.0 ** 127, 0), (2.0 ** -149, 1), (2.0 ** 126, 0), (2.0 ** -148, 1)])
+def test_scaler_update_at_the_edges_of_the_fp32_range(ops, scale0, found_inf):
+    """A growth due at 2^127 (the product is not finite: torch keeps the old scale and restarts the tracker) and a back-off due at the
+    smallest subnormal, with their neighbours one step inside the range: whatever torch._amp_update_scale_ does on the CPU."""
+    scale = torch.tensor([scale0], dtype=torch.float32).to(DEV)
+    tracker = torch.full((1,), 2, dtype=torch.int32, device=DEV)
+    found = torch.full((1,), found_inf, dtype=torch.int32, device=DEV)
+    step = torch.zeros(1, dtype=torch.int32, device=DEV)
+    rs, rt = torch.tensor([scale0], dtype=torch.float32), torch.full((1,), 2, dtype=torch.int32)
+    assert float(rs) == scale0
+    ops.scaler_update(scale, tracker, found, step, 2.0, 0.5, 3)
+    torch._amp_update_scale_(rs, rt, torch.tensor([float(found_inf)]), 2.0, 0.5, 3)
+    assert float(scale.cpu()) == float(rs) and math.isfinite(float(scale.cpu())), (float(scale.cpu()), float(rs))
+    assert int(tracker) == int(rt) == 0 and int(found) == 0 and int(step) == 1 - found_inf
+
+
+@pytest.mark.parametrize("n", [10007, GRID_CAP_ADAMW + 1029])
+def test_adamw_step_device_state_over_a_sequence_with_skips(ops, n):
+    """mt_adamw_step as the train step drives it -- step count, learning rate and loss scale on the device, grad_mult 0.5, the flag from
+    mt_check_finite, mt_scaler_update behind it (so the scale the gradients carry changes along the way) -- over SKIP_PATTERN: a call
+    whose gradient holds an inf / a NaN leaves p, m AND v bit-identical, and the sequence equals the fp64 oracle applied on the clean
+    steps only, numbered by the clean-step count.  lr = 1e-3: a bias correction formed from a wrong step number moves p by ~1e-4
+    relative, the bound is the neighbouring test's 1e-6.  The larger n runs the kernel's grid-stride loop."""
+    from oracle import modaltune_oracle as O
+    g = rng(31)
+    lr = 1e-3
+    p0 = torch.randn(n, generator=g)
+    p, m, v = p0.to(DEV).clone(), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+    scale = torch.tensor([8.0], device=DEV)
+    tracker = torch.zeros(1, dtype=torch.int32, device=DEV)
+    found = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step_dev = torch.zeros(1, dtype=torch.int32, device=DEV)
+    lr_dev = torch.full((1,), lr, device=DEV)
+    lr_ref = float(lr_dev.cpu())                 # (the fp32 value the kernel reads)
+    pr, mr, vr = p0.double(), torch.zeros(n).double(), torch.zeros(n).double()
+    bad_values = [float("inf"), float("nan"), float("-inf")]
+    bad_at = [n - 1, n // 2, 0]
+    clean = skipped = 0
+    for i, f in enumerate(SKIP_PATTERN):
+        gr = torch.randn(n, generator=g)
+        s = float(scale)
+        gd = (gr * s).to(DEV)                     # (s is a power of two: the scaled gradient is exact)
+        if f:
+            gd[bad_at[skipped % 3]] = bad_values[skipped % 3]
+            skipped += 1
+        before = (p.clone(), m.clone(), v.clone(), int(step_dev))
+        ops.check_finite(gd, n, found)
+        ops.adamw_step(p, gd, m, v, n, 123.0, 0.9, 0.999, 1e-8, 0.01, 0, scale, found, grad_mult=0.5, step_dev=step_dev, lr_dev=lr_dev)
+        torch.cuda.synchronize()
+        assert int(found) == f, i
+        if f:
+            assert torch.equal(p, before[0]) and torch.equal(m, before[1]) and torch.equal(v, before[2]), i
+        else:
+            clean += 1
+            pr, mr, vr = O.adamw_update(pr, 0.5 * gr.double(), mr, vr, clean, lr_ref)
+        ops.scaler_update(scale, tracker, found, step_dev, 2.0, 0.5, 3)
+        assert int(step_dev) == clean == before[3] + (1 - f) and int(found) == 0, i
+    assert clean == SKIP_PATTERN.count(0) and float(scale) != 8.0
+    assert rel(p, pr) < 1e-6 and rel(m, mr) < 1e-6 and rel(v, vr) < 1e-6, (rel(p, pr), rel(m, mr), rel(v, vr))
+    assert rel(p, p0) > 1e-4                     # (the clean steps did move the parameters)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 10007, GRID_CAP_FINITE + 77])
+def test_check_finite_positions_values_and_sticky_flag(ops, n):
+    """mt_check_finite: one inf / -inf / NaN at the first index, the last index, the first element of the last partial wave and (the
+    model-sized n) at an index only the grid-stride loop reaches; +-FLT_MAX and subnormals are finite; the flag is ORed, never
+    cleared."""
+    fmax = float(np.finfo(np.float32).max)
+    x = torch.randn(n, generator=rng(n))
+    specials = [fmax, -fmax, 1e-40, -1e-40, 2.0 ** -149, float(np.finfo(np.float32).tiny)]
+    for j, sv in enumerate(specials):
+        x[(j * 7919 + n - 1) % n] = sv
+    if n > 1:
+        x[n - 1], x[0] = -fmax, 2.0 ** -149
+    assert bool(torch.isfinite(x).all())
+    xd = x.to(DEV)
+    found = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.check_finite(xd, n, found)
+    assert int(found) == 0
+    positions = {0, n - 1, (n - 1) // 64 * 64}
+    if n > GRID_CAP_FINITE:
+        positions |= {GRID_CAP_FINITE, GRID_CAP_FINITE + 64, n - 70}
+    for pos in sorted(positions):
+        for bad in (float("inf"), float("-inf"), float("nan")):
+            keep = xd[pos].clone()
+            xd[pos] = bad
+            found.zero_()
+            ops.check_finite(xd, n, found)
+            assert int(found) == 1, (pos, bad)
+            xd[pos] = keep
+            ops.check_finite(xd, n, found)         # a clean vector behind a dirty one: the flag stays
+            assert int(found) == 1, (pos, bad, "sticky")
+    found.zero_()
+    ops.check_finite(xd, n, found)
+    assert int(found) == 0 and torch.equal(xd.cpu(), x)
+    found.fill_(1)
+    ops.check_finite(xd, n, found)
+    assert int(found) == 1
+
+
+def _ulp32(a):
+    return np.spacing(np.abs(np.asarray(a, dtype=np.float32))).astype(np.float64)
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 768])
+def test_absmax_scale_and_axpy_dev(ops, n):
+    """mt_absmax_scale + mt_axpy_dev, the device-side loss scale of the nn.Module bridge (which passes 3 x 256 values).  Ordinary
+    inputs: s[0] = target / max|x| (float64 reference rounded to fp32, 1 ulp), s[1] == 1 / s[0].  EVERY input -- zeros, inf, NaN, maxima
+    down to a subnormal -- gives finite positive s[0] and s[1], and scaling a finite non-zero input by s[0] and then by s[1] returns it
+    within 2 ulp wherever the scaled value is a normal fp32 number."""
+    target = 1024.0
+    tiny, fmax = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+    s = torch.zeros(2, device=DEV)
+
+    def run(x):
+        xd = x.to(DEV)
+        s.fill_(-7.0)
+        ops.absmax_scale(xd, s, target)
+        y, z = torch.full((n,), 9.0, device=DEV), torch.full((n,), 9.0, device=DEV)
+        ops.axpy_dev(None, xd, s[0:1], y)
+        ops.axpy_dev(None, y, s[1:2], z)
+        torch.cuda.synchronize()
+        s0, s1 = s.cpu().numpy().astype(np.float32)
+        assert np.isfinite(s0) and np.isfinite(s1) and s0 > 0 and s1 > 0, (s0, s1)
+        return s0, s1, y.cpu().numpy(), z.cpu().numpy()
+
+    def roundtrip(x, s0, z):
+        xn = x.numpy()
+        scaled = np.abs(xn.astype(np.float64) * float(s0))
+        ok = (xn != 0) & (scaled >= tiny) & (scaled <= fmax)       # the float64 reference: the scaled value is a normal fp32 number
+        assert ok.any()
+        err = np.abs(z.astype(np.float64) - xn.astype(np.float64))
+        assert (err[ok] <= 2 * _ulp32(xn)[ok]).all(), float((err[ok] / _ulp32(xn)[ok]).max())
+
+    base = torch.rand(n, generator=rng(n)) * 0.9 + 0.05
+    base = base * torch.where(torch.rand(n, generator=rng(n + 1)) < 0.5, -1.0, 1.0)
+    for pos in sorted({0, n - 1, n // 2}):
+        for top in (3.75, -3.75, 1.0e5, -7.0e-6, 65504.0 * 3):
+            x = base * abs(top) * 0.99
+            x[pos] = top
+            s0, s1, y, z = run(x)
+            ref = np.float32(target / abs(float(np.float32(top))))
+            assert abs(float(s0) - float(ref)) <= float(_ulp32(ref)), (pos, top, s0, ref)
+            assert s1 == np.float32(1.0) / s0, (pos, top, s0, s1)
+            assert np.abs(y).max() <= target * (1 + 2.0 ** -22) and abs(abs(y[pos]) - target) <= target * 2.0 ** -22
+            roundtrip(x, s0, z)
+    # the header's special cases: s[0] = s[1] = 1
+    for special in (0.0, float("inf"), float("-inf"), float("nan")):
+        x = base.clone() if special != 0.0 else torch.zeros(n)
+        x[n // 2] = special
+        s0, s1, y, z = run(x)
+        assert s0 == 1.0 and s1 == 1.0, (special, s0, s1)
+    # tiny maxima: target / max|x| itself is not a finite fp32 number below ~3e-36
+    for top in (1e-30, 1e-37, 1e-40, -1e-40, 2.0 ** -149):
+        x = (base.double() * abs(top)).float()
+        x[n - 1] = top
+        assert float(x.abs().max()) > 0
+        s0, s1, y, z = run(x)
+        assert np.isfinite(y).all() and np.isfinite(z).all() and not np.isnan(z).any(), top
+        roundtrip(x, s0, z)
+        if abs(top) <= 1e-37:                      # clamped to a power of two: exact both ways
+            assert np.array_equal(z, x.numpy()), top
+    # huge maximum: the factor stays a normal number as well
+    x = base * 1e30
+    x[0] = -2.5e38
+    s0, s1, y, z = run(x)
+    assert abs(float(s0) - float(np.float32(target / 2.5e38))) <= float(_ulp32(np.float32(target / 2.5e38))) and s1 == np.float32(1.0) / s0
+    roundtrip(x, s0, z)
+
+
+@pytest.mark.parametrize("n", [1, 257, 10007, GRID_CAP_ADAMW + 515])
+def test_axpy_dev_with_an_addend_and_above_the_grid_cap(ops, n):
+    """y = a + (*alpha) * b against float64, alpha on the device; the last n runs the grid-stride loop.  Bound: one rounding of the
+    product and one of the sum (or a single one, if the compiler contracts them): |err| <= 2^-23 (|a| + |alpha b|)."""
+    g = rng(77)
+    a, b = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    for alpha in (-0.37, 2.0 ** -10, 3.0e4):
+        al = torch.tensor([alpha], dtype=torch.float32)
+        y = torch.full((n,), float("nan"), device=DEV)
+        ops.axpy_dev(a.to(DEV), b.to(DEV), al.to(DEV), y)
+        torch.cuda.synchronize()
+        prod = float(al) * b.double()
+        ref = a.double() + prod
+        err = (y.cpu().double() - ref).abs()
+        assert bool((err <= 2.0 ** -23 * (a.double().abs() + prod.abs())).all()), float(err.max())
+        y2 = torch.full((n,), float("nan"), device=DEV)
+        ops.axpy_dev(None, b.to(DEV), al.to(DEV), y2)
+        torch.cuda.synchronize()
+        assert torch.equal(y2.cpu(), (float(al) * b.double()).float())
+
+
 def test_elementwise(ops):
     g = rng(21)
     n = 4099
