@@ -344,6 +344,20 @@ int mt_extract_attn_fwd(const float* q, const mt_half* kv, int B, int T, int L, 
 int mt_extract_attn_bwd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
                         int B, int T, int L, float* dq, mt_half* dkv, mt_stream_t stream);
 
+/* Width-aware twins of the four cores above: `heads` heads of dim `head_dim` (16, 32 or 64; anything else returns
+ * MT_ERR_UNSUPPORTED), E = heads * head_dim wherever 192 stands above (kv [B*L, 2E]), lse [M,heads] / [B,T,heads], the
+ * extractor partials part_acc [B*heads*nsplit*T*head_dim] and part_ml [B*heads*nsplit*T*2] floats.  The entry points above
+ * are these with (12, 16). */
+int mt_inject_attn_fwd_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T, int heads,
+                          int head_dim, mt_half* a, float* lse, mt_stream_t stream);
+int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
+                          int rows_per_pass, const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq,
+                          float* dk, float* dv, mt_stream_t stream);
+int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
+                           float* lse, float* part_acc, float* part_ml, int nsplit, mt_stream_t stream);
+int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
+                           int B, int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, mt_stream_t stream);
+
 /* Pathway networks of the gene encoder, all G pathways in one launch (gene_encoder.py:97-131,194-207: per pathway
  * SNN_Block(n_i -> latent), SNN_Block(latent -> latent), ELU, AlphaDropout off):
  *   z[i] = ELU(W2_i ELU(W1_i g_i + b1_i) + b2_i).
@@ -362,7 +376,8 @@ int mt_gene_snn_bwd(const float* params, float* grads, const long* offs, const i
                     const float* genes, int G, int latent, int passes, const float* a1, const float* a2, const float* dz,
                     const MtDropout* alpha_drop, mt_stream_t stream);
 
-/* Small dense multi-head attention over tokens (prompt self-attention AM:87): q,k,v fp32 [B,T,E], heads h. */
+/* Small dense multi-head attention over tokens (prompt self-attention AM:87): q,k,v fp32 [B,T,E], heads h; the head dim
+ * E / h must be 16, 32 or 64 (MT_ERR_UNSUPPORTED otherwise). */
 int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,
                      float* probs, mt_stream_t stream);
 int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B,
@@ -376,6 +391,11 @@ int mt_extract_attn_probs(const float* q, const mt_half* kv, const float* lse, i
 /* Injector: q fp16 [M,192], k fp32 [B,T,192], lse [M,12] of mt_inject_attn_fwd -> w fp32 [M,T] (M = B * rows_per_pass). */
 int mt_inject_attn_probs(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, float* w,
                          mt_stream_t stream);
+/* The two above for `heads` heads of dim `head_dim` (16 / 32 / 64), E = heads * head_dim, lse [.., heads]. */
+int mt_extract_attn_probs_hd(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, int heads,
+                             int head_dim, float* w, mt_stream_t stream);
+int mt_inject_attn_probs_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, int heads,
+                            int head_dim, float* w, mt_stream_t stream);
 /* Prompt self-attention: out fp32 [B,T,T] = mean over the heads of mt_token_mha_fwd's probs [B,heads,T,T]. */
 int mt_token_probs_mean(const float* probs, int B, int heads, int T, float* out, mt_stream_t stream);
 

@@ -104,10 +104,16 @@ SIGNATURES = {
     "mt_inject_attn_bwd": [P, P, P, P, I, I, P, P, I, P, P, P, P],
     "mt_extract_attn_fwd": [P, P, I, I, I, P, P, P, P, I, P],
     "mt_extract_attn_bwd": [P, P, P, P, P, I, I, I, P, P, P],
+    "mt_inject_attn_fwd_hd": [P, I, I, P, P, I, I, I, P, P, P],
+    "mt_inject_attn_bwd_hd": [P, P, P, P, I, I, P, P, I, I, I, P, P, P, P],
+    "mt_extract_attn_fwd_hd": [P, P, I, I, I, I, I, P, P, P, P, I, P],
+    "mt_extract_attn_bwd_hd": [P, P, P, P, P, I, I, I, I, I, P, P, P],
     "mt_token_mha_fwd": [P, P, P, I, I, I, I, P, P, P],
     "mt_token_mha_bwd": [P, P, P, P, P, I, I, I, I, P, P, P, P],
     "mt_extract_attn_probs": [P, P, P, I, I, I, P, P],
     "mt_inject_attn_probs": [P, I, I, P, P, I, P, P],
+    "mt_extract_attn_probs_hd": [P, P, P, I, I, I, I, I, P, P],
+    "mt_inject_attn_probs_hd": [P, I, I, P, P, I, I, I, P, P],
     "mt_token_probs_mean": [P, I, I, I, P, P],
     "mt_cast_f32_to_f16": [P, P, L, DR, I, P],
     "mt_rng_advance": [P, P],

@@ -85,6 +85,10 @@ class ModelConfig:
         return int(self.embed_dim * self.cffn_ratio)
 
     @property
+    def adapter_head_dim(self) -> int:     # nn.MultiheadAttention(E, num_heads): E // num_heads (adapter_modules.py:164)
+        return self.adapter_dim // self.num_heads
+
+    @property
     def ffn_dim(self) -> int:
         return int(self.embed_dim * self.mlp_ratio)
 
@@ -117,10 +121,26 @@ class ModelConfig:
             raise ValueError("add_prompt_feature=False: the reference's own forward fails on this configuration (`outcome` is only bound "
                              "inside `if self.add_prompt_feature`, longvit_adapter.py:315-346): there is no behaviour to reproduce")
         if not self.with_cffn:
-            raise NotImplementedError("with_cffn=False widens the adapter attention to 768 (12 heads x 64): the adapter kernels are built "
-                                      "for cffn_ratio 0.25 (12 x 16), as in both shipped ModalTune configurations")
+            raise NotImplementedError("with_cffn=False widens the adapter attention to 768 (12 heads x 64) and drops the Extractor FFN: at "
+                                      "E == embed_dim nn.MultiheadAttention packs its projections into one in_proj_weight, another "
+                                      "parameter layout than the one built here (adapter widths below 768: see cffn_ratio / num_heads)")
         if not self.freeze_vit:
             raise NotImplementedError("freeze_vit=False: the backbone's weight gradients are not computed (selective backward)")
+        # adapter width (adapter_modules.py:153-164): E = int(768 * cffn_ratio), nn.MultiheadAttention(E, num_heads, kdim=vdim=768)
+        E, nh = self.adapter_dim, int(self.num_heads)
+        if E >= self.embed_dim:
+            raise NotImplementedError(f"cffn_ratio={self.cffn_ratio} gives the adapter width E = {E} >= embed_dim {self.embed_dim}: with "
+                                      "E == kdim nn.MultiheadAttention packs q / k / v into one in_proj_weight (another state-dict "
+                                      "layout); the adapter is built for E < 768")
+        if E < 64 or E % 64:
+            raise ValueError(f"cffn_ratio={self.cffn_ratio} gives the adapter width E = int(768 * cffn_ratio) = {E}: E must be a positive "
+                             "multiple of 64 (the projection GEMMs run on K % 64 == 0)")
+        if nh < 1 or E % nh:
+            raise ValueError(f"num_heads={self.num_heads} does not divide the adapter width E = {E} (embed_dim must be divisible by "
+                             "num_heads, as nn.MultiheadAttention asserts)")
+        if E // nh not in (16, 32, 64):
+            raise NotImplementedError(f"num_heads={nh} at adapter width E = {E} is a head dim of {E // nh}: the adapter attention kernels "
+                                      "are built for head dims 16, 32 and 64")
         last = self.first_interaction_layer - 1
         if last < -1:
             raise ValueError("interaction_indexes must start at a layer >= 0")
@@ -232,10 +252,10 @@ def sincos_1d_table(ngrids: int, dim: int) -> np.ndarray:
     return np.concatenate([np.sin(out), np.cos(out)], axis=1).astype(np.float32)
 
 
-def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int = 3) -> Dict[str, float]:
-    """Algorithmic FLOPs: 2mnk GEMMs, 4*nq*nk*d attention, no recompute counted."""
+def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int = 3, E: int = 192) -> Dict[str, float]:
+    """Algorithmic FLOPs: 2mnk GEMMs, 4*nq*nk*d attention, no recompute counted.  E: adapter width (cfg.adapter_dim)."""
     seg = seg or segment_lengths()
-    N, D, F, H, d, E = L + 1, 768, 3072, 16, 48, 192
+    N, D, F, H, d = L + 1, 768, 3072, 16, 48
     patch = 2.0 * L * 1536 * D
     gemm_layer = 2.0 * N * (4 * D * D + 2 * D * F)
     attn_layer = sum(b.nseg * H * b.n * b.n * d * 4.0 for b in branch_table(N, seg))
@@ -258,12 +278,13 @@ def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int =
             "attn_layer": attn_layer, "attn_layer_executed": attn_exec, "adapter": adapter, "patch": patch}
 
 
-def flops_per_titan_step(Lv: int, T: int, depth: int = 6, D: int = 768, F: int = 3072, C: int = 768, tasks: int = 3) -> Dict[str, float]:
+def flops_per_titan_step(Lv: int, T: int, depth: int = 6, D: int = 768, F: int = 3072, C: int = 768, tasks: int = 3,
+                         E: int = 192) -> Dict[str, float]:
     """Algorithmic FLOPs of one TITAN-configuration slide step with Lv foreground cells (same counting rules as
     flops_per_slide_step: 2mnk GEMMs, 4 nq nk d attention, frozen blocks dX-only in the backward, flash backward = 2.5 x
     forward, adapters 2 x): dense ViT blocks qkv + proj + fc1 + fc2 (TA:359-361), patch-embedding MLP once per slide, attentional
     pooling K|V projection (TA:401-402), Injector x3 / Extractor x5 as in the LongNet path."""
-    N, E = Lv + 1, 192
+    N = Lv + 1
     patch = 2.0 * Lv * (C * D + D * D)
     gemm_layer = 2.0 * N * (4 * D * D + 2 * D * F)
     attn_layer = 4.0 * N * N * D

@@ -1,4 +1,4 @@
-// Modal-Adapter attention cores (12 heads x 16, E = 192):
+// Modal-Adapter attention cores (heads x HD, HD in {16, 32, 64}, E = heads * HD; 12 x 16 = 192 in both shipped configurations):
 //   inject  : every patch row attends over the T <= 128 modal tokens of its pass       (AM:225-229 in AM:359-369)
 //   extract : the T modal tokens attend over the L patch rows of their pass (split-L)   (AM:225-229 in AM:321-335)
 //   token   : T x T self-attention among the modal tokens                               (AM:87)
@@ -8,8 +8,47 @@
 
 namespace {
 
-constexpr int AH = 12, AD = 16, AE = 192, TMAX = 128;
-constexpr float ASCALE = 0.25f;   // 1/sqrt(16)
+constexpr int TMAX = 128;
+
+// The cores are templated on the head dim HD and on HC, the head count when it is known at compile time (12: the shipped
+// configuration, whose <16, 12> instantiations are the code this file held before the template) or 0 (`heads` is a kernel argument).
+// What follows from HD:
+//   NC  16-wide chunks of the head dim: a score block S = Q . K^T is a chain of NC v_mfma_f32_32x32x16_f16 on ONE accumulator
+//       (a single accumulation chain of this instruction needs no interleaving);
+//   NA  32-row output tiles of a transposed product with HD rows (O^T = V^T . P^T, dQ^T, dK^T, dV^T, phase-2 columns): one
+//       accumulator at 16 (half of it unused) and 32, two at 64;  NG of its four 4-row groups per lane hold real rows;
+//   KP  halves per row of a row-read fp16 image ([token][HD], 16-byte reads): HD + 8, i.e. 12 / 20 / 36 dwords = 4 x odd, so the sixteen
+//       rows of a ds_read_b128 lane group start on sixteen different 16-byte slots of the 64-bank row;
+//   TPV halves per row of a transposed image [HD][tokens] (8-byte reads, banked per 32-lane half): 68 dwords at HD = 16 (sixteen distinct
+//       rows, 4 banks apart), 66 dwords at HD >= 32 (thirty-two distinct rows, 2 banks apart: each 8-byte read on its own bank pair);
+//   VP  halves per row of the extractor forward's wave-private V block [32 keys][HD] (ds_read_b64_tr_b16: a 32-lane half reads four key
+//       rows x 16 dwords): 12 dwords at 16; 16 dwords at 32 and 48 at 64, so the four rows land on the four quarters of the bank row.
+template <int HD>
+struct AdDim {
+  static_assert(HD == 16 || HD == 32 || HD == 64, "adapter head dim");
+  static constexpr int NC = HD / 16, NA = (HD + 31) / 32, NG = HD == 16 ? 2 : 4;
+  static constexpr int KP = HD + 8;
+  static constexpr int TPV = HD == 16 ? TMAX + 8 : TMAX + 4;
+  static constexpr int VP = HD == 16 ? 24 : HD == 32 ? 32 : 96;
+  static constexpr float SCALE = HD == 16 ? 0.25f : HD == 32 ? 0.17677669529663687f : 0.125f;   // 1/sqrt(HD)
+};
+// q / sqrt(HD) as an fp16 MFMA operand (extractor forward, backward and maps, which must agree to the bit): the fp32 product, rounded
+// to fp16.  1/sqrt(32) is no power of two, and under -ffp-contract the compiler folds product and conversion into one v_fma_mixlo_f16,
+// which rounds the EXACT product once -- about one value in 2^13 comes out one fp16 ulp away from fp32-then-fp16, enough to move a
+// map entry by 3e-4 against a recomputation from the operands.  The empty asm pins the fp32 product at HD = 32 (16 and 64 scale by a
+// power of two: exact either way, code unchanged).
+template <int HD>
+MT_DEVINL h16 scaled_h16(float x) {
+  float p = x * AdDim<HD>::SCALE;
+  if constexpr (HD == 32) asm volatile("" : "+v"(p));
+  return (h16)p;
+}
+#define AD_DIMS                                                                                                          \
+  using Dm = AdDim<HD>;                                                                                                  \
+  constexpr int AD = HD, NC = Dm::NC, NA = Dm::NA, NG = Dm::NG, KP = Dm::KP, TPV = Dm::TPV;                              \
+  constexpr float ASCALE = Dm::SCALE;                                                                                    \
+  (void)NC; (void)NA; (void)NG; (void)KP; (void)TPV; (void)ASCALE;                                                       \
+  const int AH = HC ? HC : heads, AE = AH * AD
 
 MT_DEVINL void load16(const h16* p, float* out) {
   const h16x8 a = ldg8(p), b = ldg8(p + 8);
@@ -24,17 +63,17 @@ MT_DEVINL void store16(h16* p, const float* v) {
 }
 
 // ---------------------------------------------------------------- injector -----------------------
-// forward on MFMA: grid (ceil(rows/128), 12 heads, B passes); wave = 32 patch rows (row = lane & 31).  With d = 16 one
-// v_mfma_f32_32x32x16_f16 is a whole 32-token x 32-row score block: S^T = K . Q^T (K rows from an fp16 LDS image, Q^T
+// forward on MFMA: grid (ceil(rows/128), heads, B passes); wave = 32 patch rows (row = lane & 31).  With d = 16 one
+// v_mfma_f32_32x32x16_f16 is a whole 32-token x 32-row score block (a chain of 2 / 4 at d = 32 / 64): S^T = K . Q^T (K rows from an fp16 LDS image, Q^T
 // straight from global memory), softmax lane-local (row = lane, tokens in registers + one cross-half shuffle),
 // O^T += V^T . P^T with P^T taken from the score accumulators (V^T from a transposed fp16 LDS image).
-constexpr int KP = 24;            // halves per row of the row-read K image (48 B: conflict-free 16-lane ds_read_b128 groups)
-constexpr int TPV = TMAX + 8;     // halves per row of the transposed [16][tokens] images (272 B)
 MT_DEVINL h16x8 cat8h(h16x4 lo, h16x4 hi) { return (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
 
+template <int HD, int HC>
 __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restrict__ q, int rows_per_pass, const float* __restrict__ k,
-                                                              const float* __restrict__ v, int T, h16* __restrict__ a,
+                                                              const float* __restrict__ v, int T, int heads, h16* __restrict__ a,
                                                               float* __restrict__ lse) {
+  AD_DIMS;
   __shared__ __attribute__((aligned(16))) h16 ksh[TMAX * KP];     // K[t][d]
   __shared__ __attribute__((aligned(16))) h16 vT[AD * TPV];       // V^T[d][t]
   const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
@@ -51,7 +90,10 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
   const bool valid = r < rows_per_pass;
   const long m = (long)b * rows_per_pass + (valid ? r : 0);
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  const h16x8 qf = valid ? ldg8(q + m * AE + h * AD + 8 * hh) : zero8;     // B operand: Q^T[d = 8 hh + j][row]
+  const int drow = HD == 16 ? (l31 & 15) : l31;                              // row of a [HD][.] transposed image this lane reads
+  h16x8 qf[NC];                                                               // B operands: Q^T[d = 16 c + 8 hh + j][row]
+#pragma unroll
+  for (int c = 0; c < NC; ++c) qf[c] = valid ? ldg8(q + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
   f32x16 sc[TMAX / 32];
   float mx = -1.0e30f;
 #pragma unroll
@@ -59,8 +101,11 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
     if (tb < ntb) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) sc[tb][i] = 0.f;
-      const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 8 * hh]);
-      sc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, sc[tb], 0, 0, 0);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+        sc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc[tb], 0, 0, 0);
+      }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens: (i&3) + 8 (i>>2) + 4 hh
         if (tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh >= T) sc[tb][i] = -1.0e30f;
@@ -70,9 +115,11 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
   }
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   const float c = ASCALE * 1.4426950408889634f;
-  f32x16 acc;
+  f32x16 acc[NA];
 #pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int j = 0; j < NA; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
   float l = 0.f;
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
@@ -86,47 +133,58 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
           l += pv;
           pf[e] = (h16)pv;
         }
-        // A operand: V^T[d = lane & 15][token 16 s2 + 8 (e>>2) + 4 hh + (e&3)] (the accumulator-order k permutation)
-        const h16* vr = &vT[(l31 & 15) * TPV + tb * 32 + 16 * s2 + 4 * hh];
-        const h16x8 vf = cat8h(*reinterpret_cast<const h16x4*>(vr), *reinterpret_cast<const h16x4*>(vr + 8));
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, acc, 0, 0, 0);
+        // A operand: V^T[d = 32 j + drow][token 16 s2 + 8 (e>>2) + 4 hh + (e&3)] (the accumulator-order k permutation)
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+          const h16* vr = &vT[(32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh];
+          const h16x8 vf = cat8h(*reinterpret_cast<const h16x4*>(vr), *reinterpret_cast<const h16x4*>(vr + 8));
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, acc[j], 0, 0, 0);
+        }
       }
     }
   }
   l += __shfl_xor(l, 32, 64);
   if (valid) {
     const float inv = 1.0f / l;
-    // O^T rows d = (i&3) + 8 (i>>2) + 4 hh, valid for i < 8: this lane holds d = 4 hh + {0..3} and 8 + 4 hh + {0..3}
+    // O^T rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh (i < 8 at HD = 16): group g of accumulator j holds d = 32 j + 8 g + 4 hh + {0..3}
     h16* dst = a + m * AE + h * AD;
-    *reinterpret_cast<h16x4*>(dst + 4 * hh) = (h16x4){(h16)(acc[0] * inv), (h16)(acc[1] * inv), (h16)(acc[2] * inv), (h16)(acc[3] * inv)};
-    *reinterpret_cast<h16x4*>(dst + 8 + 4 * hh) = (h16x4){(h16)(acc[4] * inv), (h16)(acc[5] * inv), (h16)(acc[6] * inv), (h16)(acc[7] * inv)};
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int g = 0; g < NG; ++g)
+        *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
+            (h16x4){(h16)(acc[j][4 * g] * inv), (h16)(acc[j][4 * g + 1] * inv), (h16)(acc[j][4 * g + 2] * inv), (h16)(acc[j][4 * g + 3] * inv)};
     if (lse && hh == 0) lse[m * AH + h] = mx * ASCALE + __logf(l);
   }
 }
 
 // backward: workgroup = 4 waves = ITILES x 128 rows of one (pass, head); everything on MFMA.
-// Phase 1 (wave = 32 rows, row = lane): S^T = K . Q^T and dP^T = V . dA^T (one 32x32x16 MFMA per 32-token block each),
-// p = exp(s/4 - lse) (lse saved by the forward, same fp16 K), delta = a . da (flash identity), ds = p (dp - delta) / 4,
+// Phase 1 (wave = 32 rows, row = lane): S^T = K . Q^T and dP^T = V . dA^T (a chain of HD / 16 32x32x16 MFMAs per 32-token block
+// each), p = exp(s/sqrt(HD) - lse) (lse saved by the forward, same fp16 K), delta = a . da (flash identity), ds = p (dp - delta) / sqrt(HD),
 // dQ^T += K^T . dS^T with dS^T taken from the accumulators; p / ds / q / da go to LDS TRANSPOSED ([token][row], [dim][row]).
 // Phase 2: dk[t,d] += sum_rows ds[row,t] q[row,d] and dv[t,d] += sum_rows p[row,t] da[row,d] are 32x32x16 products with
 // the row index as the reduction dimension -- both operands are plain 16-byte row reads of the transposed images
 // (wave w: product w & 1, token blocks w >> 1 and (w >> 1) + 2).  The accumulators live across the row tiles: one
-// atomic per (token, dim) per workgroup at the very end.
+// atomic per (token, dim) per workgroup at the very end.  At HD = 64 the two phase-2 accumulators per token block double (dims 0..31
+// and 32..63).  LDS at T = 128: 93 / 113 / 155 KiB at HD = 16 / 32 / 64; at T = 65: 56 / 75 / 112 KiB (two workgroups per CU at 16 and
+// 32, one at 64).
 constexpr int IBR = 128, ITILES = 4, RSTR = IBR + 8;   // RSTR: halves per transposed row (272 B: conflict-free b128)
+template <int HD, int HC>
 __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restrict__ q, const h16* __restrict__ a,
                                                               const float* __restrict__ lse, const h16* __restrict__ da,
                                                               int rows_per_pass, const float* __restrict__ k,
-                                                              const float* __restrict__ v, int T, h16* __restrict__ dq,
+                                                              const float* __restrict__ v, int T, int heads, h16* __restrict__ dq,
                                                               float* __restrict__ dk, float* __restrict__ dv) {
+  AD_DIMS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
   h16* ksh = reinterpret_cast<h16*>(smem);            // [TB][KP]   K rows
   h16* vsh = ksh + TB * KP;                           // [TB][KP]   V rows
-  h16* kT = vsh + TB * KP;                            // [16][TPV]  K^T
+  h16* kT = vsh + TB * KP;                            // [HD][TPV]  K^T
   h16* psT = kT + AD * TPV;                           // [T][RSTR]
   h16* dssT = psT + T * RSTR;                         // [T][RSTR]
-  h16* qT = dssT + T * RSTR;                          // [16][RSTR]
-  h16* daT = qT + AD * RSTR;                          // [16][RSTR]
+  h16* qT = dssT + T * RSTR;                          // [HD][RSTR]
+  h16* daT = qT + AD * RSTR;                          // [HD][RSTR]
   const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
   for (int i = tid; i < TB * AD; i += 256) {
@@ -137,11 +195,14 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
     kT[d * TPV + t] = kv_;
     vsh[t * KP + d] = (h16)(ok ? v[((long)b * T + t) * AE + h * AD + d] : 0.f);
   }
-  f32x16 acc[TMAX / 64];            // phase 2: token blocks (wave >> 1) and (wave >> 1) + 2 of product (wave & 1)
+  const int drow = HD == 16 ? (l31 & 15) : l31;
+  f32x16 acc[TMAX / 64][NA];        // phase 2: token blocks (wave >> 1) and (wave >> 1) + 2 of product (wave & 1), dims 32 j2 + lane
 #pragma unroll
   for (int j = 0; j < TMAX / 64; ++j)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+    for (int j2 = 0; j2 < NA; ++j2)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[j][j2][i] = 0.f;
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   const float c = ASCALE * 1.4426950408889634f;
   __syncthreads();
@@ -152,31 +213,43 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
     const int r = r0 + rl;
     const bool valid = r < rows_per_pass;
     const long m = (long)b * rows_per_pass + (valid ? r : 0);
-    const h16x8 qf = valid ? ldg8(q + m * AE + h * AD + 8 * hh) : zero8;
-    const h16x8 daf = valid ? ldg8(da + m * AE + h * AD + 8 * hh) : zero8;
-    const h16x8 af = ldg8(a + m * AE + h * AD + 8 * hh);
+    h16x8 qf[NC], daf[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      qf[c] = valid ? ldg8(q + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
+      daf[c] = valid ? ldg8(da + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
+    }
     const float nl2 = valid ? -lse[m * AH + h] * 1.4426950408889634f : -1.0e30f;
     float delta = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      delta = fmaf((float)af[e], (float)daf[e], delta);
-      qT[(8 * hh + e) * RSTR + rl] = qf[e];
-      daT[(8 * hh + e) * RSTR + rl] = daf[e];
+    for (int c = 0; c < NC; ++c) {
+      const h16x8 af = ldg8(a + m * AE + h * AD + 16 * c + 8 * hh);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        delta = fmaf((float)af[e], (float)daf[c][e], delta);
+        qT[(16 * c + 8 * hh + e) * RSTR + rl] = qf[c][e];
+        daT[(16 * c + 8 * hh + e) * RSTR + rl] = daf[c][e];
+      }
     }
     delta += __shfl_xor(delta, 32, 64);
-    f32x16 dqa;
+    f32x16 dqa[NA];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) dqa[i] = 0.f;
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) dqa[j][i] = 0.f;
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
         f32x16 sc, dpv;
 #pragma unroll
         for (int i = 0; i < 16; ++i) { sc[i] = 0.f; dpv[i] = 0.f; }
-        const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 8 * hh]);
-        const h16x8 vf = *reinterpret_cast<const h16x8*>(&vsh[(tb * 32 + l31) * KP + 8 * hh]);
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, sc, 0, 0, 0);
-        dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, daf, dpv, 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+          const h16x8 vf = *reinterpret_cast<const h16x8*>(&vsh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+          sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc, 0, 0, 0);
+          dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, daf[c], dpv, 0, 0, 0);
+        }
         h16x8 dsf[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -191,16 +264,23 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          const h16* kr = &kT[(l31 & 15) * TPV + tb * 32 + 16 * s2 + 4 * hh];
-          const h16x8 ktf = cat8h(*reinterpret_cast<const h16x4*>(kr), *reinterpret_cast<const h16x4*>(kr + 8));
-          dqa = __builtin_amdgcn_mfma_f32_32x32x16_f16(ktf, dsf[s2], dqa, 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < NA; ++j) {
+            const h16* kr = &kT[(32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh];
+            const h16x8 ktf = cat8h(*reinterpret_cast<const h16x4*>(kr), *reinterpret_cast<const h16x4*>(kr + 8));
+            dqa[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ktf, dsf[s2], dqa[j], 0, 0, 0);
+          }
         }
       }
     }
     if (valid) {
       h16* dst = dq + m * AE + h * AD;
-      *reinterpret_cast<h16x4*>(dst + 4 * hh) = (h16x4){(h16)dqa[0], (h16)dqa[1], (h16)dqa[2], (h16)dqa[3]};
-      *reinterpret_cast<h16x4*>(dst + 8 + 4 * hh) = (h16x4){(h16)dqa[4], (h16)dqa[5], (h16)dqa[6], (h16)dqa[7]};
+#pragma unroll
+      for (int j = 0; j < NA; ++j)
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
+              (h16x4){(h16)dqa[j][4 * g], (h16)dqa[j][4 * g + 1], (h16)dqa[j][4 * g + 2], (h16)dqa[j][4 * g + 3]};
     }
     __syncthreads();
     const h16* Asrc = (wave & 1) ? psT : dssT;
@@ -213,90 +293,122 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
 #pragma unroll
         for (int kk = 0; kk < IBR / 16; ++kk) {
           const h16x8 afr = *reinterpret_cast<const h16x8*>(&Asrc[trow * RSTR + kk * 16 + hh * 8]);
-          const h16x8 bfr = *reinterpret_cast<const h16x8*>(&Bsrc[(l31 & 15) * RSTR + kk * 16 + hh * 8]);
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr, bfr, acc[j], 0, 0, 0);
+#pragma unroll
+          for (int j2 = 0; j2 < NA; ++j2) {
+            const h16x8 bfr = *reinterpret_cast<const h16x8*>(&Bsrc[(32 * j2 + drow) * RSTR + kk * 16 + hh * 8]);
+            acc[j][j2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr, bfr, acc[j][j2], 0, 0, 0);
+          }
         }
       }
     }
     __syncthreads();
   }
-  // accumulator rows are tokens: row(i) = (i&3) + 8 (i>>2) + 4 hh; column = lane & 31 = dim (16 valid)
+  // accumulator rows are tokens: row(i) = (i&3) + 8 (i>>2) + 4 hh; column = lane & 31 = dim 32 j2 + lane (16 valid at HD = 16)
   float* dst = (wave & 1) ? dv : dk;
-  if (l31 < AD) {
+  if (HD != 16 || l31 < AD) {
 #pragma unroll
     for (int j = 0; j < TMAX / 64; ++j) {
       const int tb = (wave >> 1) + 2 * j;
       if (tb < ntb) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-          if (t < T) atomicAdd(&dst[((long)b * T + t) * AE + h * AD + l31], acc[j][i]);
-        }
+        for (int j2 = 0; j2 < NA; ++j2)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            if (t < T) atomicAdd(&dst[((long)b * T + t) * AE + h * AD + 32 * j2 + l31], acc[j][j2][i]);
+          }
       }
     }
   }
 }
 
 // ---------------------------------------------------------------- extractor ----------------------
-// forward on MFMA: grid (nsplit, 12, B); 4 waves, wave w sweeps the 32-key blocks w, w + 4, ... of the split.
+// forward on MFMA: grid (nsplit, heads, B); 4 waves, wave w sweeps the 32-key blocks w, w + 4, ... of the split.
 // S^T[key, token] = K . Q^T: K rows straight from global memory (A operand, key = lane & 31), Q^T (pre-scaled, fp16) in
-// registers, one 32x32x16 MFMA per 32-token block; online softmax lane-local (token = lane, keys in registers + one
+// registers, a chain of HD / 16 32x32x16 MFMAs per 32-token block; online softmax lane-local (token = lane, keys in registers + one
 // cross-half shuffle); O^T[d, token] += V^T . P^T with P^T from the accumulators and V^T read transposed
-// (ds_read_b64_tr_b16) from a wave-private LDS copy of the 32 x 16 V block.  The four waves' partials are merged
-// through LDS into one partial per (split, token) for the reduce kernel below.
-constexpr int EKT = 32, EFT = 256, VP = 24;       // VP: halves per LDS row of the V block (48 B, 8-byte aligned tr reads)
+// (ds_read_b64_tr_b16) from a wave-private LDS copy of the 32 x HD V block.  The four waves' partials are merged
+// through LDS into one partial per (split, token) for the reduce kernel below.  The merge image [4][T][HD + 2] fp32 is static at
+// HD = 16 (36 KiB) and dynamic, sized by T, beyond (T = 128: 68 KiB at 32, 132 KiB at 64 -- one workgroup per CU there; the grid is
+// nsplit x heads x B workgroups, about one per CU, so LDS does not set the occupancy of this kernel).
+constexpr int EKT = 32, EFT = 256;
 MT_DEVINL h16x4 ad_tr4(const h16* p) {
   s16x4 r = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s16x4*)(__attribute__((address_space(3))) void*)p);
   return __builtin_bit_cast(h16x4, r);
 }
-__global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv, int T, int L,
+template <int HD, int HC>
+__global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv, int T, int L, int heads,
                                                                int keys_per_split, float* __restrict__ part_acc, float* __restrict__ part_ml) {
-  __shared__ __attribute__((aligned(16))) h16 vsh[4][32 * VP];
-  __shared__ float mrg[4][TMAX][AD + 2];
+  AD_DIMS;
+  constexpr int VP = Dm::VP, MS = AD + 2, NV = 4 * NG;      // MS: floats per (wave, token) of the merge image; NV: valid accumulator rows
+  h16* vsh;                         // [4][32 * VP]
+  float* mrg;                       // [4][MT][MS]
+  if constexpr (HD == 16) {
+    __shared__ __attribute__((aligned(16))) h16 vsh_s[4 * 32 * VP];
+    __shared__ float mrg_s[4 * TMAX * MS];
+    vsh = vsh_s; mrg = mrg_s;
+  } else {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    vsh = reinterpret_cast<h16*>(smem);
+    mrg = smem + 4 * 32 * VP / 2;
+  }
+  const int MW = (HD == 16 ? TMAX : T) * MS;                // floats per wave of the merge image
   const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
   const int nsplit = gridDim.x;
   const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
   const int li = lane & 15, tq = li >> 2, tp = li & 3;
   const int ntb = (T + 31) / 32;
-  h16x8 qf[TMAX / 32];              // B operands: Q^T[d = 8 hh + j][token]
-  f32x16 acc[TMAX / 32];
+  h16x8 qf[TMAX / 32][NC];          // B operands: Q^T[d = 16 c + 8 hh + j][token]
+  f32x16 acc[TMAX / 32][NA];
   float mrun[TMAX / 32], lrun[TMAX / 32];
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
     const int t = tb * 32 + l31;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) qf[tb][e] = (h16)(t < T ? q[((long)b * T + t) * AE + h * AD + 8 * hh + e] * ASCALE : 0.f);
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
+      for (int e = 0; e < 8; ++e) qf[tb][c][e] = scaled_h16<HD>(t < T ? q[((long)b * T + t) * AE + h * AD + 16 * c + 8 * hh + e] : 0.f);
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[tb][j][i] = 0.f;
     mrun[tb] = -1.0e30f; lrun[tb] = 0.f;
   }
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   const int kbeg = sp * keys_per_split, kend = min(L, kbeg + keys_per_split);
-  h16* vw = vsh[wave];
+  h16* vw = vsh + wave * 32 * VP;
+  const int dcol = HD == 16 ? 0 : 16 * (l31 >> 4);          // lanes 16..31 of a half transpose the next sixteen dims
   for (int k0 = kbeg + wave * EKT; k0 < kend; k0 += 4 * EKT) {
     const int key = k0 + l31;
     const bool valid = key < kend;
     const h16* row = kv + ((long)b * L + (valid ? key : kbeg)) * (2 * AE) + h * AD + 8 * hh;
-    const h16x8 kf = valid ? ldg8(row) : zero8;
-    const h16x8 vf = valid ? ldg8(row + AE) : zero8;
-    *reinterpret_cast<h16x8*>(&vw[l31 * VP + 8 * hh]) = vf;      // wave-private: no workgroup barrier needed
-    // V^T fragments (A operand of O^T += V^T . P^T), shared by the token blocks; lanes >= 16 of a half produce the unused
-    // d rows 16..31 from the same columns
-    h16x8 vt[2];
+    h16x8 kf[NC];
 #pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const h16* vr = &vw[(s2 * 16 + 4 * hh + tq) * VP + 4 * tp];
-      const h16x4 lo = ad_tr4(vr), hi = ad_tr4(vr + 8 * VP);
-      vt[s2] = (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    for (int c = 0; c < NC; ++c) {
+      kf[c] = valid ? ldg8(row + 16 * c) : zero8;
+      const h16x8 vf = valid ? ldg8(row + AE + 16 * c) : zero8;
+      *reinterpret_cast<h16x8*>(&vw[l31 * VP + 16 * c + 8 * hh]) = vf;      // wave-private: no workgroup barrier needed
     }
+    // V^T fragments (A operand of O^T += V^T . P^T), shared by the token blocks; at HD = 16 lanes >= 16 of a half produce the
+    // unused d rows 16..31 from the same columns
+    h16x8 vt[NA][2];
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const h16* vr = &vw[(s2 * 16 + 4 * hh + tq) * VP + 32 * j + dcol + 4 * tp];
+        const h16x4 lo = ad_tr4(vr), hi = ad_tr4(vr + 8 * VP);
+        vt[j][s2] = (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      }
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
         f32x16 sc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[tb], sc, 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[c], qf[tb][c], sc, 0, 0, 0);
         float mx = -1.0e30f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {      // accumulator rows are keys (i&3) + 8 (i>>2) + 4 hh
@@ -318,34 +430,41 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
         lrun[tb] = lrun[tb] * al + ls;
         mrun[tb] = mn;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[tb][i] *= al;
-        acc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vt[0], pf[0], acc[tb], 0, 0, 0);
-        acc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vt[1], pf[1], acc[tb], 0, 0, 0);
+        for (int j = 0; j < NA; ++j) {
+#pragma unroll
+          for (int i = 0; i < NV; ++i) acc[tb][j][i] *= al;
+          acc[tb][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vt[j][0], pf[0], acc[tb][j], 0, 0, 0);
+          acc[tb][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vt[j][1], pf[1], acc[tb][j], 0, 0, 0);
+        }
       }
     }
   }
-  // per-wave partials -> LDS: O^T rows d = (i&3) + 8 (i>>2) + 4 hh (i < 8), column = token
+  // per-wave partials -> LDS: O^T rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh (i < 8 at HD = 16), column = token
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
     const int t = tb * 32 + l31;
     if (tb < ntb && t < T) {
+      float* mr = mrg + wave * MW + t * MS;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) mrg[wave][t][(i & 3) + 8 * (i >> 2) + 4 * hh] = acc[tb][i];
-      if (hh == 0) { mrg[wave][t][AD] = mrun[tb]; mrg[wave][t][AD + 1] = lrun[tb]; }
+      for (int j = 0; j < NA; ++j)
+#pragma unroll
+        for (int i = 0; i < NV; ++i) mr[32 * j + (i & 3) + 8 * (i >> 2) + 4 * hh] = acc[tb][j][i];
+      if (hh == 0) { mr[AD] = mrun[tb]; mr[AD + 1] = lrun[tb]; }
     }
   }
   __syncthreads();
   if (tid < T) {
+    const float* mt = mrg + tid * MS;
     float m2 = -1.0e30f;
-    for (int wv = 0; wv < 4; ++wv) m2 = fmaxf(m2, mrg[wv][tid][AD]);
+    for (int wv = 0; wv < 4; ++wv) m2 = fmaxf(m2, mt[wv * MW + AD]);
     float l2 = 0.f, a2[AD];
 #pragma unroll
     for (int d = 0; d < AD; ++d) a2[d] = 0.f;
     for (int wv = 0; wv < 4; ++wv) {
-      const float wgt = __expf(mrg[wv][tid][AD] - m2);
-      l2 = fmaf(wgt, mrg[wv][tid][AD + 1], l2);
+      const float wgt = __expf(mt[wv * MW + AD] - m2);
+      l2 = fmaf(wgt, mt[wv * MW + AD + 1], l2);
 #pragma unroll
-      for (int d = 0; d < AD; ++d) a2[d] = fmaf(wgt, mrg[wv][tid][d], a2[d]);
+      for (int d = 0; d < AD; ++d) a2[d] = fmaf(wgt, mt[wv * MW + d], a2[d]);
     }
     const long o = (((long)b * AH + h) * nsplit + sp) * T + tid;
 #pragma unroll
@@ -354,9 +473,11 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
   }
 }
 
-__global__ void extract_attn_reduce_kernel(const float* __restrict__ part_acc, const float* __restrict__ part_ml, int T, int nsplit,
+template <int HD, int HC>
+__global__ void extract_attn_reduce_kernel(const float* __restrict__ part_acc, const float* __restrict__ part_ml, int T, int nsplit, int heads,
                                            float* __restrict__ out, float* __restrict__ lse) {
-  // grid (B*12), block T threads (<=128): thread = token
+  // grid (B * heads), block T threads (<=128): thread = token
+  AD_DIMS;
   const int bh = blockIdx.x, b = bh / AH, h = bh % AH, t = threadIdx.x;
   if (t >= T) return;
   float mx = -1.0e30f;
@@ -378,33 +499,35 @@ __global__ void extract_attn_reduce_kernel(const float* __restrict__ part_acc, c
 }
 
 // backward on MFMA: workgroup = 4 waves = ETILES x 128 keys of one (pass, head); wave = 32 keys (key = lane & 31).
-// Phase 1: S[t,key] = Q . K^T and dP[t,key] = dO . V^T, one 32x32x16 MFMA per 32-token block each, with -lse[t] and
+// Phase 1: S[t,key] = Q . K^T and dP[t,key] = dO . V^T, a chain of HD / 16 32x32x16 MFMAs per 32-token block each, with -lse[t] and
 // -delta[t] as the initial accumulators (rows of the accumulators are tokens); p = exp(S'), ds = p dP';
 // dK^T[d,key] += Q^T . dS and dV^T[d,key] += dO^T . P with dS / P taken from the accumulators (Q^T, dO^T from
 // transposed fp16 LDS images); ds and k go to LDS transposed.  Phase 2: dq[t,d] += sum_keys ds[key,t] k[key,d] (wave w:
-// token block w); one atomic per (token, dim) per workgroup at the end.  q (pre-scaled by 1/4) and dout are rounded to
-// fp16 for the MFMA, as in the forward.
+// token block w); one atomic per (token, dim) per workgroup at the end.  q (pre-scaled by 1/sqrt(HD)) and dout are rounded to
+// fp16 for the MFMA, as in the forward.  LDS at T = 128: 60 KiB at HD = 16 (two workgroups per CU), 80 KiB at 32, 121 KiB at 64 (one).
 constexpr int EBK = 128, ETILES = 4;
+template <int HD, int HC>
 __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
                                                                const float* __restrict__ out, const float* __restrict__ lse,
-                                                               const float* __restrict__ dout, int T, int L, float* __restrict__ dq,
+                                                               const float* __restrict__ dout, int T, int L, int heads, float* __restrict__ dq,
                                                                h16* __restrict__ dkv) {
+  AD_DIMS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
   float* nls = smem;                                  // [TB]  -lse (natural log) ; big negative past T
   float* ndl = nls + TMAX;                            // [TB]  -delta
   h16* qsh = reinterpret_cast<h16*>(ndl + TMAX);      // [TB][KP]   Q rows (scaled)
   h16* dosh = qsh + TB * KP;                          // [TB][KP]   dO rows
-  h16* qT = dosh + TB * KP;                           // [16][TPV]  Q^T
-  h16* doT = qT + AD * TPV;                           // [16][TPV]  dO^T
+  h16* qT = dosh + TB * KP;                           // [HD][TPV]  Q^T
+  h16* doT = qT + AD * TPV;                           // [HD][TPV]  dO^T
   h16* dssT = doT + AD * TPV;                         // [T][RSTR]
-  h16* kT = dssT + T * RSTR;                          // [16][RSTR]
+  h16* kT = dssT + T * RSTR;                          // [HD][RSTR]
   const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
   for (int i = tid; i < TB * AD; i += 256) {
     const int t = i / AD, d = i % AD;
     const bool ok = t < T;
-    const h16 qv_ = (h16)(ok ? q[((long)b * T + t) * AE + h * AD + d] * ASCALE : 0.f);
+    const h16 qv_ = scaled_h16<HD>(ok ? q[((long)b * T + t) * AE + h * AD + d] : 0.f);
     const h16 dv_ = (h16)(ok ? dout[((long)b * T + t) * AE + h * AD + d] : 0.f);
     qsh[t * KP + d] = qv_; qT[d * TPV + t] = qv_;
     dosh[t * KP + d] = dv_; doT[d * TPV + t] = dv_;
@@ -417,9 +540,12 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
     }
     nls[t] = -l; ndl[t] = -d;
   }
-  f32x16 accq;                      // phase 2: token block `wave`
+  const int drow = HD == 16 ? (l31 & 15) : l31;
+  f32x16 accq[NA];                  // phase 2: token block `wave`, dims 32 j + lane
 #pragma unroll
-  for (int i = 0; i < 16; ++i) accq[i] = 0.f;
+  for (int j = 0; j < NA; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) accq[j][i] = 0.f;
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   __syncthreads();
   for (int tile = 0; tile < ETILES; ++tile) {
@@ -429,13 +555,19 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
     const int key = k0 + kl;
     const bool valid = key < L;
     const h16* kvrow = kv + ((long)b * L + (valid ? key : 0)) * (2 * AE) + h * AD + 8 * hh;
-    const h16x8 kf = valid ? ldg8(kvrow) : zero8;             // B operands: K^T[d = 8 hh + j][key], V^T likewise
-    const h16x8 vf = valid ? ldg8(kvrow + AE) : zero8;
+    h16x8 kf[NC], vf[NC];                                     // B operands: K^T[d = 16 c + 8 hh + j][key], V^T likewise
 #pragma unroll
-    for (int e = 0; e < 8; ++e) kT[(8 * hh + e) * RSTR + kl] = kf[e];
-    f32x16 dka, dva;
+    for (int c = 0; c < NC; ++c) {
+      kf[c] = valid ? ldg8(kvrow + 16 * c) : zero8;
+      vf[c] = valid ? ldg8(kvrow + AE + 16 * c) : zero8;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { dka[i] = 0.f; dva[i] = 0.f; }
+      for (int e = 0; e < 8; ++e) kT[(16 * c + 8 * hh + e) * RSTR + kl] = kf[c][e];
+    }
+    f32x16 dka[NA], dva[NA];
+#pragma unroll
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) { dka[j][i] = 0.f; dva[j][i] = 0.f; }
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
@@ -447,10 +579,13 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
 #pragma unroll
           for (int e = 0; e < 4; ++e) { sc[4 * g4 + e] = l4[e]; dpv[4 * g4 + e] = d4[e]; }
         }
-        const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(tb * 32 + l31) * KP + 8 * hh]);
-        const h16x8 da = *reinterpret_cast<const h16x8*>(&dosh[(tb * 32 + l31) * KP + 8 * hh]);
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf, sc, 0, 0, 0);
-        dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(da, vf, dpv, 0, 0, 0);
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+          const h16x8 da = *reinterpret_cast<const h16x8*>(&dosh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+          sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf[c], sc, 0, 0, 0);
+          dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(da, vf[c], dpv, 0, 0, 0);
+        }
         h16x8 pf[2], dsf[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -463,20 +598,30 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          const int toff = (l31 & 15) * TPV + tb * 32 + 16 * s2 + 4 * hh;
-          const h16x8 qtf = cat8h(*reinterpret_cast<const h16x4*>(&qT[toff]), *reinterpret_cast<const h16x4*>(&qT[toff + 8]));
-          const h16x8 dtf = cat8h(*reinterpret_cast<const h16x4*>(&doT[toff]), *reinterpret_cast<const h16x4*>(&doT[toff + 8]));
-          dka = __builtin_amdgcn_mfma_f32_32x32x16_f16(qtf, dsf[s2], dka, 0, 0, 0);
-          dva = __builtin_amdgcn_mfma_f32_32x32x16_f16(dtf, pf[s2], dva, 0, 0, 0);
+#pragma unroll
+          for (int j = 0; j < NA; ++j) {
+            const int toff = (32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh;
+            const h16x8 qtf = cat8h(*reinterpret_cast<const h16x4*>(&qT[toff]), *reinterpret_cast<const h16x4*>(&qT[toff + 8]));
+            const h16x8 dtf = cat8h(*reinterpret_cast<const h16x4*>(&doT[toff]), *reinterpret_cast<const h16x4*>(&doT[toff + 8]));
+            dka[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qtf, dsf[s2], dka[j], 0, 0, 0);
+            dva[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dtf, pf[s2], dva[j], 0, 0, 0);
+          }
         }
       }
     }
-    if (valid) {      // rows d = (i&3) + 8 (i>>2) + 4 hh of the d x key accumulators, i < 8 (qsh already carries the 1/4)
+    if (valid) {      // rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh of the d x key accumulators (i < 8 at HD = 16; qsh already carries the scale)
       h16* dst = dkv + ((long)b * L + key) * (2 * AE) + h * AD;
-      *reinterpret_cast<h16x4*>(dst + 4 * hh) = (h16x4){(h16)dka[0], (h16)dka[1], (h16)dka[2], (h16)dka[3]};
-      *reinterpret_cast<h16x4*>(dst + 8 + 4 * hh) = (h16x4){(h16)dka[4], (h16)dka[5], (h16)dka[6], (h16)dka[7]};
-      *reinterpret_cast<h16x4*>(dst + AE + 4 * hh) = (h16x4){(h16)dva[0], (h16)dva[1], (h16)dva[2], (h16)dva[3]};
-      *reinterpret_cast<h16x4*>(dst + AE + 8 + 4 * hh) = (h16x4){(h16)dva[4], (h16)dva[5], (h16)dva[6], (h16)dva[7]};
+#pragma unroll
+      for (int j = 0; j < NA; ++j) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
+              (h16x4){(h16)dka[j][4 * g], (h16)dka[j][4 * g + 1], (h16)dka[j][4 * g + 2], (h16)dka[j][4 * g + 3]};
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+          *reinterpret_cast<h16x4*>(dst + AE + 32 * j + 8 * g + 4 * hh) =
+              (h16x4){(h16)dva[j][4 * g], (h16)dva[j][4 * g + 1], (h16)dva[j][4 * g + 2], (h16)dva[j][4 * g + 3]};
+      }
     }
     __syncthreads();
     if (wave < ntb) {               // uniform per wave
@@ -484,18 +629,23 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
 #pragma unroll
       for (int kk = 0; kk < EBK / 16; ++kk) {
         const h16x8 af = *reinterpret_cast<const h16x8*>(&dssT[trow * RSTR + kk * 16 + hh * 8]);
-        const h16x8 bf = *reinterpret_cast<const h16x8*>(&kT[(l31 & 15) * RSTR + kk * 16 + hh * 8]);
-        accq = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, accq, 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+          const h16x8 bf = *reinterpret_cast<const h16x8*>(&kT[(32 * j + drow) * RSTR + kk * 16 + hh * 8]);
+          accq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, accq[j], 0, 0, 0);
+        }
       }
     }
     __syncthreads();
   }
-  if (l31 < AD && wave < ntb) {
+  if ((HD != 16 || l31 < AD) && wave < ntb) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int t = wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-      if (t < T) atomicAdd(&dq[((long)b * T + t) * AE + h * AD + l31], accq[i]);
-    }
+    for (int j = 0; j < NA; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int t = wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        if (t < T) atomicAdd(&dq[((long)b * T + t) * AE + h * AD + 32 * j + l31], accq[j][i]);
+      }
   }
 }
 
@@ -505,23 +655,27 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
 // for the backward) in one pass.  (The first form -- a thread per query looping over the keys with the score row in GLOBAL
 // memory, written and re-read three times -- ran 24 us for 36 workgroups of 65 tokens; the step launches it between dependent
 // token-side products, so its latency is exposed.  256 threads = 64 tokens per sweep: 13 us at T = 65, the 65th token costs a
-// whole second sweep.)
+// whole second sweep.)  Templated on the head dim HD: a thread of a token's four owns HD / 4 consecutive dims in the output sweeps.
+// K, V and the scores take 16 T HD + 4 T S1 bytes (T = 128: 83 KiB at 16, 99 KiB at 32, 131 KiB at 64): the forward fits at every T.
 MT_DEVINL f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // Score rows of the forward: T entries padded to a multiple of four, row stride S1 = 4 x odd >= that (sixteen tokens of a wave then start
 // on sixteen different 16-byte bank groups), so that the value sweep reads FOUR probabilities with one 16-byte read -- every LDS read of
 // that loop is in the 8 / 16-byte banking class (common.h: no counted lgkmcnt wait may span both classes).
 MT_DEVINL int mha_t4(int T) { return (T + 3) & ~3; }
 MT_DEVINL int mha_s1(int T) { const int t4 = mha_t4(T); return ((t4 >> 2) & 1) ? t4 : t4 + 4; }
+template <int HD>
 __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                             int T, int E, int heads, float* __restrict__ out, float* __restrict__ probs) {
+  constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;      // C4: 16-byte chunks per row; DS: dims a thread owns in the value sweep
+  constexpr float ASCALE = AdDim<HD>::SCALE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int T4 = mha_t4(T), S1 = mha_s1(T);
-  float* ks = smem;                 // [T][16]
-  float* vs = ks + T * AD;          // [T4][16], rows T .. T4 - 1 zero
+  float* ks = smem;                 // [T][HD]
+  float* vs = ks + T * AD;          // [T4][HD], rows T .. T4 - 1 zero
   float* ss = vs + T4 * AD;         // [T][S1], entries T .. T4 - 1 of a row zero
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3;
-  for (int i = tid; i < T4 * 4; i += 512) {
-    const int tt = i >> 2, c = (i & 3) * 4;
+  for (int i = tid; i < T4 * C4; i += 512) {
+    const int tt = i / C4, c = (i % C4) * 4;
     if (tt < T) {
       const long o = ((long)b * T + tt) * E + h * AD + c;
       *reinterpret_cast<f32x4*>(ks + tt * AD + c) = ld4(k + o);
@@ -536,7 +690,7 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
   if (act) {
     const float* qr = q + ((long)b * T + t) * E + h * AD;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < C4; ++c) {
       const f32x4 x = ld4(qr + 4 * c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) qv[4 * c + e] = x[e] * ASCALE;
@@ -567,37 +721,50 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
   __syncthreads();          // a row's four writers -> its four readers
   if (act) {
     // value sweep, four keys per step: one 16-byte read of the row's probabilities, four 16-byte value rows (all one banking class)
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[DS / 4];
+#pragma unroll
+    for (int x = 0; x < DS / 4; ++x) acc[x] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int j = 0; j < T4; j += 4) {
       const f32x4 p4 = ld4(ss + t * S1 + j);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) acc += p4[u] * ld4(vs + (j + u) * AD + 4 * sub);
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int x = 0; x < DS / 4; ++x) acc[x] += p4[u] * ld4(vs + (j + u) * AD + DS * sub + 4 * x);
     }
-    *reinterpret_cast<f32x4*>(out + ((long)b * T + t) * E + h * AD + 4 * sub) = acc;
+#pragma unroll
+    for (int x = 0; x < DS / 4; ++x) *reinterpret_cast<f32x4*>(out + ((long)b * T + t) * E + h * AD + DS * sub + 4 * x) = acc[x];
   }
 }
 
 // dq / dk / dv of the above from the saved probs: dP = dO V^T, dS = P (dP - rowsum(P dP)) scale, dQ = dS K, dK = dS^T Q, dV = P^T dO.
-// Q, K, V, dO and dS in LDS -- and P too while both T x T images fit (PL: T <= 127; beyond that P is read from global memory);
-// four threads per token, each owning four of the sixteen head dimensions in the output sweeps.
-template <bool PL>
+// Q, K, V, dO and dS in LDS -- and P too while both T x T images fit; four threads per token, each owning HD / 4 consecutive head
+// dimensions in the output sweeps.  FORM picks what lives in LDS (16 T HD bytes of operands + 4 T (T + 1) per T x T image, 160 KiB):
+//   0  Q, K, V, dO, dS, P      T <= 127 at HD = 16, <= 114 at 32, <= 92 at 64
+//   1  Q, K, V, dO, dS         P read from global memory: every T <= 128 at 16 and 32, T <= 111 at 64
+//   2  V, dO, dS               P, Q and K read from global memory (L2-resident: T x HD floats per head): the rest, HD = 64 and T > 111
+template <int HD, int FORM>
 __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                             const float* __restrict__ probs, const float* __restrict__ dout, int T, int E,
                                                             int heads, float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv) {
+  constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;
+  constexpr float ASCALE = AdDim<HD>::SCALE;
+  constexpr bool PL = FORM == 0, GQK = FORM == 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* qs = smem;                 // [T][16]
+  float* qs = smem;                 // [T][HD]     (Q and K: not in FORM 2)
   float* ks = qs + T * AD;
-  float* vs = ks + T * AD;
+  float* vs = GQK ? smem : ks + T * AD;
   float* dos = vs + T * AD;
   float* dss = dos + T * AD;        // [T][T + 1]  dS (already scaled)
-  float* pls = dss + T * (T + 1);   // [T][T + 1]  P (PL only)
+  float* pls = dss + T * (T + 1);   // [T][T + 1]  P (FORM 0 only)
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3, S1 = T + 1;
   const float* pbase = probs + ((long)b * heads + h) * T * T;
-  for (int i = tid; i < T * 4; i += 512) {
-    const int tt = i >> 2, c = (i & 3) * 4;
+  for (int i = tid; i < T * C4; i += 512) {
+    const int tt = i / C4, c = (i % C4) * 4;
     const long o = ((long)b * T + tt) * E + h * AD + c;
-    *reinterpret_cast<f32x4*>(qs + tt * AD + c) = ld4(q + o);
-    *reinterpret_cast<f32x4*>(ks + tt * AD + c) = ld4(k + o);
+    if (!GQK) {
+      *reinterpret_cast<f32x4*>(qs + tt * AD + c) = ld4(q + o);
+      *reinterpret_cast<f32x4*>(ks + tt * AD + c) = ld4(k + o);
+    }
     *reinterpret_cast<f32x4*>(vs + tt * AD + c) = ld4(v + o);
     *reinterpret_cast<f32x4*>(dos + tt * AD + c) = ld4(dout + o);
   }
@@ -629,17 +796,31 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
     for (int j = sub; j < T; j += 4) dss[t * S1 + j] = lds_f32(&pr[j]) * (lds_f32(&dss[t * S1 + j]) - delta) * ASCALE;
   }
   __syncthreads();
-  if (act) {          // dQ: thread (query t, dims 4 sub ..);  dK, dV: thread (key t, dims 4 sub ..)
-    f32x4 aq = {0.f, 0.f, 0.f, 0.f}, ak = {0.f, 0.f, 0.f, 0.f}, av = {0.f, 0.f, 0.f, 0.f};
+  if (act) {          // dQ: thread (query t, dims DS sub ..);  dK, dV: thread (key t, dims DS sub ..)
+    f32x4 aq[DS / 4], ak[DS / 4], av[DS / 4];
+#pragma unroll
+    for (int x = 0; x < DS / 4; ++x) aq[x] = ak[x] = av[x] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    const float* kr = GQK ? k + ((long)b * T) * E + h * AD + DS * sub : ks + DS * sub;      // row j of K / Q: + j * rst
+    const float* qr = GQK ? q + ((long)b * T) * E + h * AD + DS * sub : qs + DS * sub;
+    const long rst = GQK ? E : AD;
     for (int j = 0; j < T; ++j) {      // (4-byte LDS reads only, as in the forward's value sweep)
-      aq += lds_f32(&dss[t * S1 + j]) * lds_f32x4_by_dword(ks + j * AD + 4 * sub);
-      ak += lds_f32(&dss[j * S1 + t]) * lds_f32x4_by_dword(qs + j * AD + 4 * sub);
-      av += lds_f32(&pc[j * pst]) * lds_f32x4_by_dword(dos + j * AD + 4 * sub);
+      const float dsq = lds_f32(&dss[t * S1 + j]);
+#pragma unroll
+      for (int x = 0; x < DS / 4; ++x) aq[x] += dsq * lds_f32x4_by_dword(kr + j * rst + 4 * x);
+      const float dsk = lds_f32(&dss[j * S1 + t]);
+#pragma unroll
+      for (int x = 0; x < DS / 4; ++x) ak[x] += dsk * lds_f32x4_by_dword(qr + j * rst + 4 * x);
+      const float pv = lds_f32(&pc[j * pst]);
+#pragma unroll
+      for (int x = 0; x < DS / 4; ++x) av[x] += pv * lds_f32x4_by_dword(dos + j * AD + DS * sub + 4 * x);
     }
-    const long o = ((long)b * T + t) * E + h * AD + 4 * sub;
-    *reinterpret_cast<f32x4*>(dq + o) = aq;
-    *reinterpret_cast<f32x4*>(dk + o) = ak;
-    *reinterpret_cast<f32x4*>(dv + o) = av;
+    const long o = ((long)b * T + t) * E + h * AD + DS * sub;
+#pragma unroll
+    for (int x = 0; x < DS / 4; ++x) {
+      *reinterpret_cast<f32x4*>(dq + o + 4 * x) = aq[x];
+      *reinterpret_cast<f32x4*>(dk + o + 4 * x) = ak[x];
+      *reinterpret_cast<f32x4*>(dv + o + 4 * x) = av[x];
+    }
   }
 }
 
@@ -649,27 +830,26 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
 // forward rounds them, so every row of every head sums to one against the saved LSE.
 constexpr int PBR = 128;          // keys (extractor) / patch rows (injector) per workgroup: 4 waves x 32
 
-// Extractor: w[b, t, l] = 1/12 sum_h exp(s_bthl - lse_bth), s = fp16(q / 4) . fp16(k) (extract_attn_fwd's rounding).
-// grid (ceil(L / 128), B); wave = 32 keys (key = lane & 31).  Per head one 32x32x16 MFMA per 32-token block with -lse as the
-// initial accumulator (extract_attn_bwd phase 1); the exp is summed over the heads in registers and every element is stored
-// once (a store instruction writes two 128-byte rows).  LDS: -lse [12][TB] and fp16(q / 4) [12][TB][KP], all reads 16 bytes wide.
+// Extractor: w[b, t, l] = 1/heads sum_h exp(s_bthl - lse_bth), s = fp16(q / sqrt(HD)) . fp16(k) (extract_attn_fwd's rounding).
+// grid (ceil(L / 128), B); wave = 32 keys (key = lane & 31).  Per head a chain of HD / 16 32x32x16 MFMAs per 32-token block with
+// -lse as the initial accumulator (extract_attn_bwd phase 1); the exp is summed over the heads in registers and every element is
+// stored once (a store instruction writes two 128-byte rows).  LDS: -lse [G][TB] and fp16(q / sqrt(HD)) [G][TB][KP], all reads 16
+// bytes wide, for a GROUP of G heads at a time: the launcher picks the largest G whose image stays within PROBS_LDS = 80 KiB, so
+// that two workgroups (8 waves) share a CU in every form -- all 12 heads at once at 12 x 16 (78 KiB at T = 128, as before the
+// template), 3 passes of 4 heads at 9 x 64 rather than a 162 KiB image of all nine or fewer tokens per workgroup.
+constexpr int PROBS_LDS = 80 * 1024;
+template <int HD, int HC>
 __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
-                                                                 const float* __restrict__ lse, int T, int L, float* __restrict__ w) {
+                                                                 const float* __restrict__ lse, int T, int L, int heads, int hgroup,
+                                                                 float* __restrict__ w) {
+  AD_DIMS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
-  float* nls = smem;                                      // [12][TB]      -lse; -1e30 past T
-  h16* qsh = reinterpret_cast<h16*>(nls + AH * TB);       // [12][TB][KP]  q / 4 (fp16); zero past T
+  const int G = HC ? HC : hgroup;                         // heads per LDS image
+  float* nls = smem;                                      // [G][TB]      -lse; -1e30 past T
+  h16* qsh = reinterpret_cast<h16*>(nls + G * TB);        // [G][TB][KP]  q / sqrt(HD) (fp16); zero past T
   const int b = blockIdx.y, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
-  for (int i = tid; i < TB * AE; i += 256) {
-    const int t = i / AE, e = i % AE;
-    qsh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? q[((long)b * T + t) * AE + e] * ASCALE : 0.f);
-  }
-  for (int i = tid; i < TB * AH; i += 256) {
-    const int t = i / AH, h = i % AH;
-    nls[h * TB + t] = t < T ? -lse[((long)b * T + t) * AH + h] : -1.0e30f;
-  }
-  __syncthreads();
   const int key = blockIdx.x * PBR + wave * 32 + l31;
   const bool valid = key < L;
   const h16* row = kv + ((long)b * L + (valid ? key : 0)) * (2 * AE) + 8 * hh;
@@ -679,27 +859,45 @@ __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __
   for (int tb = 0; tb < TMAX / 32; ++tb)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
-  for (int h = 0; h < AH; ++h) {
-    const h16x8 kf = valid ? ldg8(row + h * AD) : zero8;     // B operand: K^T[d = 8 hh + j][key]
+  for (int h0 = 0; h0 < AH; h0 += G) {
+    const int gh = min(G, AH - h0), GE = gh * AD;
+    if (h0) __syncthreads();          // the previous group's image has been read by every wave
+    for (int i = tid; i < TB * GE; i += 256) {
+      const int t = i / GE, e = i % GE;
+      qsh[((e / AD) * TB + t) * KP + e % AD] = scaled_h16<HD>(t < T ? q[((long)b * T + t) * AE + h0 * AD + e] : 0.f);
+    }
+    for (int i = tid; i < TB * gh; i += 256) {
+      const int t = i / gh, h = i % gh;
+      nls[h * TB + t] = t < T ? -lse[((long)b * T + t) * AH + h0 + h] : -1.0e30f;
+    }
+    __syncthreads();
+    for (int h = 0; h < gh; ++h) {
+      h16x8 kf[NC];                   // B operands: K^T[d = 16 c + 8 hh + j][key]
 #pragma unroll
-    for (int tb = 0; tb < TMAX / 32; ++tb) {
-      if (tb < ntb) {
-        f32x16 sc;
+      for (int c = 0; c < NC; ++c) kf[c] = valid ? ldg8(row + (h0 + h) * AD + 16 * c) : zero8;
 #pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh
-          const f32x4 l4 = *reinterpret_cast<const f32x4*>(&nls[h * TB + tb * 32 + 8 * g4 + 4 * hh]);
+      for (int tb = 0; tb < TMAX / 32; ++tb) {
+        if (tb < ntb) {
+          f32x16 sc;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) sc[4 * g4 + e] = l4[e];
+          for (int g4 = 0; g4 < 4; ++g4) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh
+            const f32x4 l4 = *reinterpret_cast<const f32x4*>(&nls[h * TB + tb * 32 + 8 * g4 + 4 * hh]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sc[4 * g4 + e] = l4[e];
+          }
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(h * TB + tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf[c], sc, 0, 0, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(sc[i]);
         }
-        const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(h * TB + tb * 32 + l31) * KP + 8 * hh]);
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf, sc, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(sc[i]);
       }
     }
   }
   if (valid) {
-    const float inv = 1.0f / AH;
+    const float inv = 1.0f / (float)AH;
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
@@ -713,23 +911,23 @@ __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __
   }
 }
 
-// Injector: w[m, t] = 1/12 sum_h exp(s_mht / 4 - lse_mh), s = fp16(k) . q (inject_attn_fwd's rounding; its lse is natural-log).
-// grid (ceil(rows_per_pass / 128), B); wave = 32 patch rows (row = lane & 31).  Per head S^T = K . Q^T, one 32x32x16 MFMA per
-// 32-token block (K rows from an fp16 LDS image of all 12 heads, 16-byte reads).  The [128 rows][T] tile then goes through LDS
+// Injector: w[m, t] = 1/heads sum_h exp(s_mht / sqrt(HD) - lse_mh), s = fp16(k) . q (inject_attn_fwd's rounding; its lse is natural-log).
+// grid (ceil(rows_per_pass / 128), B); wave = 32 patch rows (row = lane & 31).  Per head S^T = K . Q^T, a chain of HD / 16 32x32x16 MFMAs
+// per 32-token block (K rows from an fp16 LDS image of a group of G heads, 16-byte reads; G as above: the image or the 65 KiB output
+// tile, whichever is larger, stays within 80 KiB -- two workgroups per CU in every form).  The [128 rows][T] tile then goes through LDS
 // (4-byte writes, a barrier, 4-byte reads; odd row stride) and leaves as one contiguous, coalesced run of the [M, T] output.
 MT_DEVINL int probs_stride(int T) { return T | 1; }
+template <int HD, int HC>
 __global__ __launch_bounds__(256) void inject_attn_probs_kernel(const h16* __restrict__ q, int rows_per_pass, const float* __restrict__ k,
-                                                                const float* __restrict__ lse, int T, float* __restrict__ w) {
+                                                                const float* __restrict__ lse, int T, int heads, int hgroup,
+                                                                float* __restrict__ w) {
+  AD_DIMS;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
-  h16* ksh = reinterpret_cast<h16*>(smem);                // [12][TB][KP]  fp16(k); zero past T
+  const int G = HC ? HC : hgroup;                         // heads per LDS image
+  h16* ksh = reinterpret_cast<h16*>(smem);                // [G][TB][KP]  fp16(k); zero past T
   const int b = blockIdx.y, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
-  for (int i = tid; i < TB * AE; i += 256) {
-    const int t = i / AE, e = i % AE;
-    ksh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? k[((long)b * T + t) * AE + e] : 0.f);
-  }
-  __syncthreads();
   const int r0 = blockIdx.x * PBR, rl = wave * 32 + l31;
   const bool valid = r0 + rl < rows_per_pass;
   const long m = (long)b * rows_per_pass + (valid ? r0 + rl : 0);
@@ -739,26 +937,40 @@ __global__ __launch_bounds__(256) void inject_attn_probs_kernel(const h16* __res
   for (int tb = 0; tb < TMAX / 32; ++tb)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
-  for (int h = 0; h < AH; ++h) {
-    const h16x8 qf = valid ? ldg8(q + m * AE + h * AD + 8 * hh) : zero8;     // B operand: Q^T[d = 8 hh + j][row]
-    const float nl = valid ? -lse[m * AH + h] : 0.f;
+  for (int h0 = 0; h0 < AH; h0 += G) {
+    const int gh = min(G, AH - h0), GE = gh * AD;
+    if (h0) __syncthreads();          // the previous group's image has been read by every wave
+    for (int i = tid; i < TB * GE; i += 256) {
+      const int t = i / GE, e = i % GE;
+      ksh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? k[((long)b * T + t) * AE + h0 * AD + e] : 0.f);
+    }
+    __syncthreads();
+    for (int h = 0; h < gh; ++h) {
+      h16x8 qf[NC];                   // B operands: Q^T[d = 16 c + 8 hh + j][row]
 #pragma unroll
-    for (int tb = 0; tb < TMAX / 32; ++tb) {
-      if (tb < ntb) {
-        f32x16 sc;
+      for (int c = 0; c < NC; ++c) qf[c] = valid ? ldg8(q + m * AE + (h0 + h) * AD + 16 * c + 8 * hh) : zero8;
+      const float nl = valid ? -lse[m * AH + h0 + h] : 0.f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-        const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(h * TB + tb * 32 + l31) * KP + 8 * hh]);
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf, sc, 0, 0, 0);
+      for (int tb = 0; tb < TMAX / 32; ++tb) {
+        if (tb < ntb) {
+          f32x16 sc;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(fmaf(sc[i], ASCALE, nl));
+          for (int i = 0; i < 16; ++i) sc[i] = 0.f;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(h * TB + tb * 32 + l31) * KP + 16 * c + 8 * hh]);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc, 0, 0, 0);
+          }
+#pragma unroll
+          for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(fmaf(sc[i], ASCALE, nl));
+        }
       }
     }
   }
   __syncthreads();                  // every wave is done with the K image: its storage takes the output tile
   const int S = probs_stride(T);
   float* osh = smem;                // [128][S]
-  const float inv = 1.0f / AH;
+  const float inv = 1.0f / (float)AH;
   if (valid) {
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
@@ -788,65 +1000,235 @@ __global__ void token_probs_mean_kernel(const float* __restrict__ probs, int B, 
   out[e] = s / (float)heads;
 }
 
+// ---------------------------------------------------------------- launchers ----------------------
+// One launcher per kernel, templated like it; AD_DISPATCH picks the instantiation: <16, 12> for the shipped 12 x 16 (the head count a
+// compile-time constant, as before the template), <HD, 0> otherwise.
+#define AD_DISPATCH(heads, hd, CALL)                        \
+  do {                                                      \
+    if ((hd) == 16 && (heads) == 12) return CALL(16, 12);   \
+    if ((hd) == 16) return CALL(16, 0);                     \
+    if ((hd) == 32) return CALL(32, 0);                     \
+    if ((hd) == 64) return CALL(64, 0);                     \
+    return MT_ERR_UNSUPPORTED;                              \
+  } while (0)
+
+constexpr int LDS_MAX = 160 * 1024;
+
+template <int HD, int HC>
+int launch_inject_fwd(const h16* q, int rows_per_pass, int B, const float* k, const float* v, int T, int heads, h16* a, float* lse,
+                      hipStream_t stream) {
+  hipLaunchKernelGGL((inject_attn_fwd_kernel<HD, HC>), dim3(cdiv(rows_per_pass, 128), heads, B), dim3(256), 0, stream, q, rows_per_pass, k,
+                     v, T, heads, a, lse);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD, int HC>
+int launch_inject_bwd(const h16* q, const h16* a, const float* lse, const h16* da, int rows_per_pass, int B, const float* k, const float* v,
+                      int T, int heads, h16* dq, float* dk, float* dv, hipStream_t stream) {
+  using Dm = AdDim<HD>;
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t shm = sizeof(h16) * ((size_t)2 * TBk * Dm::KP + HD * Dm::TPV + (size_t)(2 * T + 2 * HD) * RSTR);
+  if (shm > (size_t)LDS_MAX) return MT_ERR_UNSUPPORTED;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)inject_attn_bwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((inject_attn_bwd_kernel<HD, HC>), dim3(cdiv(rows_per_pass, IBR * ITILES), heads, B), dim3(256), shm, stream, q, a, lse,
+                     da, rows_per_pass, k, v, T, heads, dq, dk, dv);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD, int HC>
+int launch_extract_fwd(const float* q, const h16* kv, int B, int T, int L, int heads, int kps, float* out, float* lse, float* part_acc,
+                       float* part_ml, int nsplit, hipStream_t stream) {
+  // (HD = 16: static LDS; beyond, the V blocks and the merge image [4][T][HD + 2] are dynamic)
+  const size_t shm = HD == 16 ? 0 : sizeof(h16) * 4 * 32 * AdDim<HD>::VP + sizeof(float) * 4 * (size_t)T * (HD + 2);
+  if (HD != 16) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      (void)hipFuncSetAttribute((const void*)extract_attn_fwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+      attr_set = true;
+    }
+  }
+  hipLaunchKernelGGL((extract_attn_fwd_kernel<HD, HC>), dim3(nsplit, heads, B), dim3(EFT), shm, stream, q, kv, T, L, heads, kps, part_acc,
+                     part_ml);
+  hipLaunchKernelGGL((extract_attn_reduce_kernel<HD, HC>), dim3(B * heads), dim3(TMAX), 0, stream, part_acc, part_ml, T, nsplit, heads, out,
+                     lse);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD, int HC>
+int launch_extract_bwd(const float* q, const h16* kv, const float* out, const float* lse, const float* dout, int B, int T, int L, int heads,
+                       float* dq, h16* dkv, hipStream_t stream) {
+  using Dm = AdDim<HD>;
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t shm = sizeof(float) * (2 * TMAX) + sizeof(h16) * ((size_t)2 * TBk * Dm::KP + 2 * HD * Dm::TPV + (size_t)(T + HD) * RSTR);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)extract_attn_bwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((extract_attn_bwd_kernel<HD, HC>), dim3(cdiv(L, EBK * ETILES), heads, B), dim3(256), shm, stream, q, kv, out, lse, dout,
+                     T, L, heads, dq, dkv);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+// heads per LDS image of the attention-map kernels: all of them when that fits PROBS_LDS, else the largest group that does
+inline int probs_group(int heads, size_t per_head) {
+  const int g = (int)((size_t)PROBS_LDS / per_head);
+  return g < 1 ? 1 : g > heads ? heads : g;
+}
+
+template <int HD, int HC>
+int launch_extract_probs(const float* q, const h16* kv, const float* lse, int B, int T, int L, int heads, float* w, hipStream_t stream) {
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t per_head = sizeof(float) * TBk + sizeof(h16) * (size_t)TBk * AdDim<HD>::KP;
+  const int G = HC ? HC : probs_group(heads, per_head);
+  const size_t shm = per_head * G;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)extract_attn_probs_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((extract_attn_probs_kernel<HD, HC>), dim3(cdiv(L, PBR), B), dim3(256), shm, stream, q, kv, lse, T, L, heads, G, w);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD, int HC>
+int launch_inject_probs(const h16* q, int rows_per_pass, int B, const float* k, const float* lse, int T, int heads, float* w,
+                        hipStream_t stream) {
+  const int TBk = cdiv(T, 32) * 32;
+  const size_t per_head = sizeof(h16) * (size_t)TBk * AdDim<HD>::KP;
+  const int G = HC ? HC : probs_group(heads, per_head);
+  const size_t kimg = per_head * G, otile = sizeof(float) * (size_t)PBR * (T | 1);
+  const size_t shm = kimg > otile ? kimg : otile;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)inject_attn_probs_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((inject_attn_probs_kernel<HD, HC>), dim3(cdiv(rows_per_pass, PBR), B), dim3(256), shm, stream, q, rows_per_pass, k, lse,
+                     T, heads, G, w);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD>
+int launch_token_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out, float* probs,
+                     hipStream_t stream) {
+  const int T4 = (T + 3) & ~3, S1 = ((T4 >> 2) & 1) ? T4 : T4 + 4;      // (mha_t4 / mha_s1 of the kernel)
+  const size_t shm = sizeof(float) * ((size_t)T * HD + (size_t)T4 * HD + (size_t)T * S1);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)token_mha_fwd_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(token_mha_fwd_kernel<HD>, dim3(heads, B), dim3(512), shm, stream, q, k, v, T, E, heads, out, probs);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+template <int HD, int FORM>
+void launch_token_bwd_form(size_t shm, const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
+                           int E, int heads, float* dq, float* dk, float* dv, hipStream_t stream) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<HD, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((token_mha_bwd_kernel<HD, FORM>), dim3(heads, B), dim3(512), shm, stream, q, k, v, probs, dout, T, E, heads, dq, dk, dv);
+}
+
+template <int HD>
+int launch_token_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E, int heads,
+                     float* dq, float* dk, float* dv, hipStream_t stream) {
+  // FORM 0 while the four operand images and both T x T images (dS, P) fit (T <= 127 / 114 / 92 at HD = 16 / 32 / 64), FORM 1 while the
+  // operands and dS do (every T at 16 and 32, T <= 111 at 64), FORM 2 (V, dO, dS) beyond
+  const size_t op = sizeof(float) * (size_t)T * HD, tt = sizeof(float) * (size_t)T * (T + 1);
+  if (4 * op + 2 * tt <= (size_t)LDS_MAX)
+    launch_token_bwd_form<HD, 0>(4 * op + 2 * tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
+  else if (4 * op + tt <= (size_t)LDS_MAX)
+    launch_token_bwd_form<HD, 1>(4 * op + tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
+  else
+    launch_token_bwd_form<HD, 2>(2 * op + tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+inline bool ad_heads_ok(int heads, int head_dim) { return heads >= 1 && head_dim >= 1 && heads <= 1024; }
+
 }  // namespace
+
+extern "C" int mt_inject_attn_fwd_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T, int heads,
+                                     int head_dim, mt_half* a, float* lse, mt_stream_t stream) {
+  if (!q || !k || !v || !a || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+#define AD_CALL(HD, HC) \
+  launch_inject_fwd<HD, HC>((const h16*)q, rows_per_pass, M / rows_per_pass, k, v, T, heads, (h16*)a, lse, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
+}
 
 extern "C" int mt_inject_attn_fwd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T,
                                   mt_half* a, float* lse, mt_stream_t stream) {
-  if (!q || !k || !v || !a || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX) return MT_ERR_BAD_ARG;
-  const int B = M / rows_per_pass;
-  hipLaunchKernelGGL(inject_attn_fwd_kernel, dim3(cdiv(rows_per_pass, 128), AH, B), dim3(256), 0, (hipStream_t)stream,
-                     (const h16*)q, rows_per_pass, k, v, T, (h16*)a, lse);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return mt_inject_attn_fwd_hd(q, M, rows_per_pass, k, v, T, 12, 16, a, lse, stream);
+}
+
+extern "C" int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M, int rows_per_pass,
+                                     const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq, float* dk, float* dv,
+                                     mt_stream_t stream) {
+  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 ||
+      T > TMAX || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+#define AD_CALL(HD, HC)                                                                                                              \
+  launch_inject_bwd<HD, HC>((const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, M / rows_per_pass, k, v, T, heads, (h16*)dq, \
+                            dk, dv, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
 }
 
 extern "C" int mt_inject_attn_bwd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
                                   int rows_per_pass, const float* k, const float* v, int T, mt_half* dq, float* dk,
                                   float* dv, mt_stream_t stream) {
-  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 ||
-      T > TMAX)
+  return mt_inject_attn_bwd_hd(q, a, lse, da, M, rows_per_pass, k, v, T, 12, 16, dq, dk, dv, stream);
+}
+
+extern "C" int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
+                                      float* lse, float* part_acc, float* part_ml, int nsplit, mt_stream_t stream) {
+  if (!q || !kv || !out || !lse || !part_acc || !part_ml || B < 1 || T < 1 || T > TMAX || L < 1 || nsplit < 1 ||
+      !ad_heads_ok(heads, head_dim))
     return MT_ERR_BAD_ARG;
-  const int B = M / rows_per_pass;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t shm = sizeof(h16) * ((size_t)2 * TBk * KP + AD * TPV + (size_t)(2 * T + 2 * AD) * RSTR);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)inject_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(inject_attn_bwd_kernel, dim3(cdiv(rows_per_pass, IBR * ITILES), AH, B), dim3(256), shm, (hipStream_t)stream,
-                     (const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, k, v, T, (h16*)dq, dk, dv);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  const int kps = cdiv(cdiv(L, nsplit), EKT) * EKT;
+  if ((long)kps * (nsplit - 1) >= L && nsplit > 1) return MT_ERR_BAD_ARG;   // every split must own >= 1 key
+#define AD_CALL(HD, HC) \
+  launch_extract_fwd<HD, HC>(q, (const h16*)kv, B, T, L, heads, kps, out, lse, part_acc, part_ml, nsplit, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
 }
 
 extern "C" int mt_extract_attn_fwd(const float* q, const mt_half* kv, int B, int T, int L, float* out, float* lse,
                                    float* part_acc, float* part_ml, int nsplit, mt_stream_t stream) {
-  if (!q || !kv || !out || !lse || !part_acc || !part_ml || B < 1 || T < 1 || T > TMAX || L < 1 || nsplit < 1) return MT_ERR_BAD_ARG;
-  const int kps = cdiv(cdiv(L, nsplit), EKT) * EKT;
-  if ((long)kps * (nsplit - 1) >= L && nsplit > 1) return MT_ERR_BAD_ARG;   // every split must own >= 1 key
-  hipLaunchKernelGGL(extract_attn_fwd_kernel, dim3(nsplit, AH, B), dim3(EFT), 0, (hipStream_t)stream, q, (const h16*)kv, T, L,
-                     kps, part_acc, part_ml);
-  hipLaunchKernelGGL(extract_attn_reduce_kernel, dim3(B * AH), dim3(TMAX), 0, (hipStream_t)stream, part_acc, part_ml, T,
-                     nsplit, out, lse);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return mt_extract_attn_fwd_hd(q, kv, B, T, L, 12, 16, out, lse, part_acc, part_ml, nsplit, stream);
+}
+
+extern "C" int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout, int B,
+                                      int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, mt_stream_t stream) {
+  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+#define AD_CALL(HD, HC) launch_extract_bwd<HD, HC>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, dq, (h16*)dkv, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
 }
 
 extern "C" int mt_extract_attn_bwd(const float* q, const mt_half* kv, const float* out, const float* lse,
                                    const float* dout, int B, int T, int L, float* dq, mt_half* dkv, mt_stream_t stream) {
-  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || B < 1 || T < 1 || T > TMAX || L < 1) return MT_ERR_BAD_ARG;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t shm = sizeof(float) * (2 * TMAX) + sizeof(h16) * ((size_t)2 * TBk * KP + 2 * AD * TPV + (size_t)(T + AD) * RSTR);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)extract_attn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(extract_attn_bwd_kernel, dim3(cdiv(L, EBK * ETILES), AH, B), dim3(256), shm, (hipStream_t)stream, q,
-                     (const h16*)kv, out, lse, dout, T, L, dq, (h16*)dkv);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return mt_extract_attn_bwd_hd(q, kv, out, lse, dout, B, T, L, 12, 16, dq, dkv, stream);
 }
 
 static bool mha_ptrs_ok(const float* const* ps, int n, int E) {
@@ -854,76 +1236,61 @@ static bool mha_ptrs_ok(const float* const* ps, int n, int E) {
     if (!ps[i] || ((uintptr_t)ps[i] & 15)) return false;
   return (E & 3) == 0;
 }
+// head dim of the prompt self-attention: E / heads, one of 16 / 32 / 64 (0: none of them)
+static int mha_head_dim(int E, int heads) {
+  const int hd = E / heads;
+  return (hd == 16 || hd == 32 || hd == 64) ? hd : 0;
+}
 extern "C" int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads,
                                 float* out, float* probs, mt_stream_t stream) {
   const float* ps[] = {q, k, v, out};
-  if (!mha_ptrs_ok(ps, 4, E) || !probs || B < 1 || T < 1 || T > TMAX || E != heads * AD) return MT_ERR_BAD_ARG;
-  const int T4 = (T + 3) & ~3, S1 = ((T4 >> 2) & 1) ? T4 : T4 + 4;      // (mha_t4 / mha_s1 of the kernel)
-  const size_t shm = sizeof(float) * ((size_t)T * AD + (size_t)T4 * AD + (size_t)T * S1);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
+  if (!mha_ptrs_ok(ps, 4, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads) return MT_ERR_BAD_ARG;
+  switch (mha_head_dim(E, heads)) {
+    case 16: return launch_token_fwd<16>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
+    case 32: return launch_token_fwd<32>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
+    case 64: return launch_token_fwd<64>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
+    default: return MT_ERR_UNSUPPORTED;
   }
-  hipLaunchKernelGGL(token_mha_fwd_kernel, dim3(heads, B), dim3(512), shm, (hipStream_t)stream, q, k, v, T, E, heads, out, probs);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
 }
 
 extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout,
                                 int B, int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream) {
   const float* ps[] = {q, k, v, dout, dq, dk, dv};
-  if (!mha_ptrs_ok(ps, 7, E) || !probs || B < 1 || T < 1 || T > TMAX || E != heads * AD) return MT_ERR_BAD_ARG;
-  const bool pl = sizeof(float) * (4 * T * AD + 2 * T * (T + 1)) <= 160 * 1024;      // both T x T images (dS, P) fit up to T = 127
-  const size_t shm = sizeof(float) * (4 * T * AD + (pl ? 2 : 1) * T * (T + 1));
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
+  if (!mha_ptrs_ok(ps, 7, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads) return MT_ERR_BAD_ARG;
+  switch (mha_head_dim(E, heads)) {
+    case 16: return launch_token_bwd<16>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
+    case 32: return launch_token_bwd<32>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
+    case 64: return launch_token_bwd<64>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
+    default: return MT_ERR_UNSUPPORTED;
   }
-  if (pl)
-    hipLaunchKernelGGL(token_mha_bwd_kernel<true>, dim3(heads, B), dim3(512), shm, (hipStream_t)stream, q, k, v, probs, dout, T, E,
-                       heads, dq, dk, dv);
-  else
-    hipLaunchKernelGGL(token_mha_bwd_kernel<false>, dim3(heads, B), dim3(512), shm, (hipStream_t)stream, q, k, v, probs, dout, T, E,
-                       heads, dq, dk, dv);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+}
+
+extern "C" int mt_extract_attn_probs_hd(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, int heads, int head_dim,
+                                        float* w, mt_stream_t stream) {
+  if (!q || !kv || !lse || !w || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim)) return MT_ERR_BAD_ARG;
+#define AD_CALL(HD, HC) launch_extract_probs<HD, HC>(q, (const h16*)kv, lse, B, T, L, heads, w, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
 }
 
 extern "C" int mt_extract_attn_probs(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, float* w,
                                      mt_stream_t stream) {
-  if (!q || !kv || !lse || !w || B < 1 || T < 1 || T > TMAX || L < 1) return MT_ERR_BAD_ARG;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t shm = sizeof(float) * AH * TBk + sizeof(h16) * (size_t)AH * TBk * KP;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)extract_attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(extract_attn_probs_kernel, dim3(cdiv(L, PBR), B), dim3(256), shm, (hipStream_t)stream, q, (const h16*)kv, lse,
-                     T, L, w);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return mt_extract_attn_probs_hd(q, kv, lse, B, T, L, 12, 16, w, stream);
+}
+
+extern "C" int mt_inject_attn_probs_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, int heads,
+                                       int head_dim, float* w, mt_stream_t stream) {
+  if (!q || !k || !lse || !w || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+#define AD_CALL(HD, HC) \
+  launch_inject_probs<HD, HC>((const h16*)q, rows_per_pass, M / rows_per_pass, k, lse, T, heads, (float*)w, (hipStream_t)stream)
+  AD_DISPATCH(heads, head_dim, AD_CALL);
+#undef AD_CALL
 }
 
 extern "C" int mt_inject_attn_probs(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, float* w,
                                     mt_stream_t stream) {
-  if (!q || !k || !lse || !w || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX) return MT_ERR_BAD_ARG;
-  const int B = M / rows_per_pass;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t kimg = sizeof(h16) * (size_t)AH * TBk * KP, otile = sizeof(float) * (size_t)PBR * (T | 1);
-  const size_t shm = kimg > otile ? kimg : otile;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)inject_attn_probs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(inject_attn_probs_kernel, dim3(cdiv(rows_per_pass, PBR), B), dim3(256), shm, (hipStream_t)stream, (const h16*)q,
-                     rows_per_pass, k, lse, T, w);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return mt_inject_attn_probs_hd(q, M, rows_per_pass, k, lse, T, 12, 16, w, stream);
 }
 
 extern "C" int mt_token_probs_mean(const float* probs, int B, int heads, int T, float* out, mt_stream_t stream) {

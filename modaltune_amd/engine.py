@@ -847,11 +847,12 @@ class Engine:
         bqi = t[ap + "multihead_attn.in_proj_bias"][:E]
         ops.gemm_nt(q1, w16[ap + "q_in"].w, q2, Mp, E, E, bias=bqi)
         a = torch.empty(Mp, E, dtype=H16, device=dev)
-        alse = torch.empty(Mp, 12, dtype=F32, device=dev)
-        ops.inject_attn_fwd(q2, k.data, v.data, a, Mp, L, T, lse=alse)
+        AHn, AHd = cfg.num_heads, cfg.adapter_head_dim
+        alse = torch.empty(Mp, AHn, dtype=F32, device=dev)
+        ops.inject_attn_fwd(q2, k.data, v.data, a, Mp, L, T, lse=alse, heads=AHn, head_dim=AHd)
         wmap = self._maps.get(ap + "multihead_attn")
         if wmap is not None:
-            ops.inject_attn_probs(q2, k.data, alse, wmap, Mp, L, T)
+            ops.inject_attn_probs(q2, k.data, alse, wmap, Mp, L, T, heads=AHn, head_dim=AHd)
         o1 = torch.empty(Mp, E, dtype=H16, device=dev)
         ops.gemm_nt(a, w16[ap + "out_in"].w, o1, Mp, E, E, bias=t[ap + "multihead_attn.out_proj.bias"])
         ops.gemm_nt(o1, w16[ap + "output_proj"].w, hin, Mp, D, E, cmap=pm, epilogue=ops.EPI_INJECT, bias=t[ap + "output_proj.bias"],
@@ -875,7 +876,7 @@ class Engine:
             da = torch.empty(Mp, E, dtype=H16, device=dev)
             ops.gemm_nt(do1, w16[ap + "out_in"].wt, da, Mp, E, E)
             dq2 = torch.empty(Mp, E, dtype=H16, device=dev)
-            ops.inject_attn_bwd(q2, a, alse, da, k.data, v.data, dq2, k.g(), v.g(), Mp, L, T)
+            ops.inject_attn_bwd(q2, a, alse, da, k.data, v.data, dq2, k.g(), v.g(), Mp, L, T, heads=AHn, head_dim=AHd)
             self._leaf(lambda: ops.gemm_tn(dq2, q1, g[ap + "multihead_attn.q_proj_weight"], Mp, E, E, colsum=g[ap + "multihead_attn.in_proj_bias"][:E]),
                        dq2, q1)
             dq1 = torch.empty(Mp, E, dtype=H16, device=dev)
@@ -995,21 +996,22 @@ class Engine:
         Wq, _, _, bq, _, _ = self._mha_in(ap + "multihead_attn.")
         q2 = tape.linear(q1, Wq, bq)
         out = Var(tape.new(B, T, E))
-        lse = tape.new(B, T, 12)
+        AHn, AHd = cfg.num_heads, cfg.adapter_head_dim
+        lse = tape.new(B, T, AHn)
         kps = -(-(-(-L // max(1, min(64, L // 256))) ) // 64) * 64      # keys per split: multiple of the 64-key tile
         nsplit = -(-L // kps)                                           # every split owns >= 1 key
-        pa = tape.new(B * 12 * nsplit * T * 16)
-        pml = tape.new(B * 12 * nsplit * T * 2)
-        ops.extract_attn_fwd(q2.data, kv, out.data, lse, pa, pml, B, T, L, nsplit)
+        pa = tape.new(B * AHn * nsplit * T * AHd)
+        pml = tape.new(B * AHn * nsplit * T * 2)
+        ops.extract_attn_fwd(q2.data, kv, out.data, lse, pa, pml, B, T, L, nsplit, heads=AHn, head_dim=AHd)
         wmap = self._maps.get(ap + "multihead_attn")
         if wmap is not None:
-            ops.extract_attn_probs(q2.data, kv, lse, wmap, B, T, L)
+            ops.extract_attn_probs(q2.data, kv, lse, wmap, B, T, L, heads=AHn, head_dim=AHd)
 
         def bwd_core():
             if out.grad is None:
                 return
             dkv = torch.empty(Mp, 2 * E, dtype=H16, device=dev)
-            ops.extract_attn_bwd(q2.data, kv, out.data, lse, out.grad, q2.g(), dkv, B, T, L)
+            ops.extract_attn_bwd(q2.data, kv, out.data, lse, out.grad, q2.g(), dkv, B, T, L, heads=AHn, head_dim=AHd)
             self._leaf(lambda: ops.gemm_tn(dkv, xk, g[ap + "multihead_attn.k_proj_weight"], Mp, 2 * E, D,       # k | v weights are adjacent
                                            colsum=g[ap + "multihead_attn.in_proj_bias"][E:]), dkv, xk)
             dxk = torch.empty(Mp, D, dtype=H16, device=dev)

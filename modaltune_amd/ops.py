@@ -329,23 +329,26 @@ def gene_snn_bwd(params, grads, offs, sizes, goff, genes, G, latent, a1, a2, dz,
                                       _p(a2), _p(dz), _dr(alpha_drop), _s()), "gene_snn_bwd")
 
 
-def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None):
-    check(_lib.load().mt_inject_attn_fwd(_p(q), M, rows_per_pass, _p(k), _p(v), T, _p(a), _p(lse), _s()), "inject_attn_fwd")
+# Adapter attention cores: `heads` heads of dim `head_dim` (16 / 32 / 64), E = heads * head_dim; the defaults are the shipped 12 x 16.
+def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None, heads=12, head_dim=16):
+    check(_lib.load().mt_inject_attn_fwd_hd(_p(q), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(a), _p(lse), _s()),
+          "inject_attn_fwd")
 
 
-def inject_attn_bwd(q, a, lse, da, k, v, dq, dk, dv, M, rows_per_pass, T):
-    check(_lib.load().mt_inject_attn_bwd(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, _p(dq), _p(dk),
-                                         _p(dv), _s()), "inject_attn_bwd")
+def inject_attn_bwd(q, a, lse, da, k, v, dq, dk, dv, M, rows_per_pass, T, heads=12, head_dim=16):
+    check(_lib.load().mt_inject_attn_bwd_hd(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(dq),
+                                            _p(dk), _p(dv), _s()), "inject_attn_bwd")
 
 
-def extract_attn_fwd(q, kv, out, lse, part_acc, part_ml, B, T, L, nsplit):
-    check(_lib.load().mt_extract_attn_fwd(_p(q), _p(kv), B, T, L, _p(out), _p(lse), _p(part_acc), _p(part_ml), nsplit,
-                                          _s()), "extract_attn_fwd")
+def extract_attn_fwd(q, kv, out, lse, part_acc, part_ml, B, T, L, nsplit, heads=12, head_dim=16):
+    """part_acc / part_ml: B * heads * nsplit * T * head_dim / * 2 floats."""
+    check(_lib.load().mt_extract_attn_fwd_hd(_p(q), _p(kv), B, T, L, heads, head_dim, _p(out), _p(lse), _p(part_acc), _p(part_ml),
+                                             nsplit, _s()), "extract_attn_fwd")
 
 
-def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L):
-    check(_lib.load().mt_extract_attn_bwd(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, _p(dq), _p(dkv), _s()),
-          "extract_attn_bwd")
+def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L, heads=12, head_dim=16):
+    check(_lib.load().mt_extract_attn_bwd_hd(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, heads, head_dim, _p(dq), _p(dkv),
+                                             _s()), "extract_attn_bwd")
 
 
 def token_mha_fwd(q, k, v, out, probs, B, T, E, heads):
@@ -357,16 +360,17 @@ def token_mha_bwd(q, k, v, probs, dout, dq, dk, dv, B, T, E, heads):
                                        _s()), "token_mha_bwd")
 
 
-def extract_attn_probs(q, kv, lse, w, B, T, L):
+def extract_attn_probs(q, kv, lse, w, B, T, L, heads=12, head_dim=16):
     """w [B, T, L] fp32: head-averaged attention of the extractor's token queries over the patch rows (lse of extract_attn_fwd)."""
     _need(w, torch.float32, "w")
-    check(_lib.load().mt_extract_attn_probs(_p(q), _p(kv), _p(lse), B, T, L, _p(w), _s()), "extract_attn_probs")
+    check(_lib.load().mt_extract_attn_probs_hd(_p(q), _p(kv), _p(lse), B, T, L, heads, head_dim, _p(w), _s()), "extract_attn_probs")
 
 
-def inject_attn_probs(q, k, lse, w, M, rows_per_pass, T):
+def inject_attn_probs(q, k, lse, w, M, rows_per_pass, T, heads=12, head_dim=16):
     """w [M, T] fp32: head-averaged attention of the injector's patch rows over the tokens (lse of inject_attn_fwd)."""
     _need(w, torch.float32, "w")
-    check(_lib.load().mt_inject_attn_probs(_p(q), M, rows_per_pass, _p(k), _p(lse), T, _p(w), _s()), "inject_attn_probs")
+    check(_lib.load().mt_inject_attn_probs_hd(_p(q), M, rows_per_pass, _p(k), _p(lse), T, heads, head_dim, _p(w), _s()),
+          "inject_attn_probs")
 
 
 def token_probs_mean(probs, out, B, heads, T):

@@ -185,32 +185,43 @@ _op("dense_attention_bwd(Tensor d_o, Tensor qkv, Tensor o, Tensor lse, int N, in
 
 
 # ---- Injector / Extractor attention cores (AM:225-229)
-def _inject_attention_fwd(q: Tensor, k: Tensor, v: Tensor, rows_per_pass: int) -> Tuple[Tensor, Tensor]:
+def _adapter_head_dim(E: int, heads: int, what: str) -> int:
+    """E = heads * head_dim with head_dim one of the widths the adapter kernels are built for."""
+    if heads < 1 or E % heads or E // heads not in (16, 32, 64):
+        raise RuntimeError(f"modaltune_hip::{what}: width {E} is not {heads} heads of dim 16, 32 or 64")
+    return E // heads
+
+
+def _inject_attention_fwd(q: Tensor, k: Tensor, v: Tensor, rows_per_pass: int, heads: int = 12) -> Tuple[Tensor, Tensor]:
+    """q fp16 [M, E], k / v fp32 [B, T, E], E = heads * {16, 32, 64} -> (a fp16 [M, E], lse fp32 [M, heads])."""
     _need(q, H16, "q", 2); _need(k, F32, "k", 3); _need(v, F32, "v", 3)
-    M, T = q.shape[0], k.shape[1]
-    a, lse = torch.empty(M, 192, dtype=H16, device=q.device), torch.empty(M, 12, dtype=F32, device=q.device)
-    ops.inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=lse)
+    M, E, T = q.shape[0], q.shape[1], k.shape[1]
+    hd = _adapter_head_dim(E, heads, "inject_attention_fwd")
+    a, lse = torch.empty(M, E, dtype=H16, device=q.device), torch.empty(M, heads, dtype=F32, device=q.device)
+    ops.inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=lse, heads=heads, head_dim=hd)
     return a, lse
 
 
-_op("inject_attention_fwd(Tensor q, Tensor k, Tensor v, int rows_per_pass) -> (Tensor, Tensor)")(
-    (_inject_attention_fwd, lambda q, k, v, r: (q.new_empty(q.shape), q.new_empty((q.shape[0], 12), dtype=F32))))
+_op("inject_attention_fwd(Tensor q, Tensor k, Tensor v, int rows_per_pass, int heads=12) -> (Tensor, Tensor)")(
+    (_inject_attention_fwd, lambda q, k, v, r, heads=12: (q.new_empty(q.shape), q.new_empty((q.shape[0], heads), dtype=F32))))
 
 
-def _extract_attention_fwd(q: Tensor, kv: Tensor, L: int) -> Tuple[Tensor, Tensor]:
+def _extract_attention_fwd(q: Tensor, kv: Tensor, L: int, heads: int = 12) -> Tuple[Tensor, Tensor]:
+    """q fp32 [B, T, E], kv fp16 [B * L, 2 E], E = heads * {16, 32, 64} -> (out fp32 [B, T, E], lse fp32 [B, T, heads])."""
     _need(q, F32, "q", 3); _need(kv, H16, "kv", 2)
-    B, T = q.shape[0], q.shape[1]
+    B, T, E = q.shape
+    hd = _adapter_head_dim(E, heads, "extract_attention_fwd")
     dev = q.device
     kps = -(-(-(-L // max(1, min(64, L // 256)))) // 64) * 64
     nsplit = -(-L // kps)
-    out, lse = torch.empty(B, T, 192, dtype=F32, device=dev), torch.empty(B, T, 12, dtype=F32, device=dev)
-    pa, pml = torch.empty(B * 12 * nsplit * T * 16, dtype=F32, device=dev), torch.empty(B * 12 * nsplit * T * 2, dtype=F32, device=dev)
-    ops.extract_attn_fwd(q, kv, out, lse, pa, pml, B, T, L, nsplit)
+    out, lse = torch.empty(B, T, E, dtype=F32, device=dev), torch.empty(B, T, heads, dtype=F32, device=dev)
+    pa, pml = torch.empty(B * heads * nsplit * T * hd, dtype=F32, device=dev), torch.empty(B * heads * nsplit * T * 2, dtype=F32, device=dev)
+    ops.extract_attn_fwd(q, kv, out, lse, pa, pml, B, T, L, nsplit, heads=heads, head_dim=hd)
     return out, lse
 
 
-_op("extract_attention_fwd(Tensor q, Tensor kv, int L) -> (Tensor, Tensor)")(
-    (_extract_attention_fwd, lambda q, kv, L: (q.new_empty(q.shape), q.new_empty((q.shape[0], q.shape[1], 12)))))
+_op("extract_attention_fwd(Tensor q, Tensor kv, int L, int heads=12) -> (Tensor, Tensor)")(
+    (_extract_attention_fwd, lambda q, kv, L, heads=12: (q.new_empty(q.shape), q.new_empty((q.shape[0], q.shape[1], heads)))))
 
 
 # ---- fused multi-tensor AdamW over a flat buffer (functional: returns the updated p, m, v)

@@ -1,0 +1,94 @@
+"""Train-step time and the adapter attention kernels' share of it across adapter widths (`cffn_ratio`, `num_heads`).
+
+    python tools/adapter_width_bench.py [steps=10] [L ...=10000 4096]
+
+For each (E, heads) of the six pairs of tests/test_adapter_width_gpu.py -- head dims 16 / 32 / 64 at E = 192 and 384 -- and each bag
+length: the median ms of a hipGraph-replayed train step (TrainStep.step_graphed, 3 task passes, dropout off), and from ONE eager step
+with HIP events around every launch (ops.TIMER) the time of the four templated patch-side kernels (inject_attn_fwd / bwd,
+extract_attn_fwd / bwd: 3 / 3 / 5 / 5 launches per step), their share of the eager step's kernel time, and the HBM rate each achieves
+counted from the tensor sizes (patch-side operands read once, outputs written once; the token side is noise at these lengths).
+Prints one JSON line per (pair, L) and a table."""
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from modaltune_amd import ops, synth  # noqa: E402
+from modaltune_amd.config import ModelConfig  # noqa: E402
+from modaltune_amd.engine import Engine  # noqa: E402
+from modaltune_amd.trainer import TrainStep  # noqa: E402
+
+PAIRS = [(192, 12), (192, 6), (192, 3), (384, 24), (384, 12), (384, 6)]
+KERNELS = ["inject_attn_fwd", "inject_attn_bwd", "extract_attn_fwd", "extract_attn_bwd"]
+steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+lengths = [int(a) for a in sys.argv[2:]] or [10000, 4096]
+dev = torch.device("cuda", 0)
+B = 3
+
+
+def bytes_per_launch(name, L, E, heads):
+    M = B * L
+    if name == "inject_attn_fwd":       # q in, a + lse out
+        return M * (2 * E + 2 * E + 4 * heads)
+    if name == "inject_attn_bwd":       # q, a, da, lse in, dq out
+        return M * (4 * 2 * E + 4 * heads)
+    if name == "extract_attn_fwd":      # k | v in
+        return M * 2 * 2 * E
+    return M * 2 * 2 * 2 * E            # extract_attn_bwd: k | v in, dk | dv out
+
+
+rows = []
+for L in lengths:
+    for E, heads in PAIRS:
+        cfg = ModelConfig(cffn_ratio=E / 768, num_heads=heads, dropout=0.0, drop_path_rate=0.0)
+        assert cfg.adapter_dim == E
+        sizes = synth.toy_group_sizes(6)
+        eng = Engine(cfg, sizes, dev)
+        eng.load_state_dict(synth.synth_state_dict(cfg, sizes, seed=0))
+        ts = TrainStep(eng)
+        ts.set_projector(synth.projector_state(0))
+        inp = synth.synth_inputs(L, sizes, seed=1000, grid=128 if L <= 128 * 128 else 512)
+        x = torch.from_numpy(inp["x"]).to(dev)
+        genes = [torch.from_numpy(a).to(dev) for a in inp["genes"]]
+        text = torch.from_numpy(inp["text"]).to(dev)
+        for _ in range(4):                      # eager visits, capture, first replay
+            ts.step_graphed(x, inp["coords"], genes, text)
+        torch.cuda.synchronize()
+        r0, ms = ts.graph_replays, []
+        for _ in range(steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            ts.step_graphed(x, inp["coords"], genes, text)
+            b.record()
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+        assert ts.graph_replays == r0 + steps, "a timed step did not replay its captured graph"
+        ops.TIMER = {}
+        ts.split_min_patches = 1 << 30          # one batched pass: every launch on one stream
+        ts.step(x, inp["coords"], genes, text, update=False)
+        torch.cuda.synchronize()
+        kt = {k: [e0.elapsed_time(e1) for e0, e1 in v] for k, v in ops.TIMER.items()}
+        ops.TIMER = None
+        total = sum(sum(v) for v in kt.values())
+        rec = {"patches": L, "E": E, "heads": heads, "head_dim": E // heads, "ms_per_step": round(statistics.median(ms), 3),
+               "ms_min_max": [round(min(ms), 3), round(max(ms), 3)], "eager_kernel_ms": round(total, 3)}
+        ad = 0.0
+        for k in KERNELS:
+            t = kt.get(k, [])
+            ad += sum(t)
+            rec[k] = {"launches": len(t), "ms_per_step": round(sum(t), 4),
+                      "gb_per_s": round(bytes_per_launch(k, L, E, heads) * len(t) / (sum(t) * 1e-3) / 1e9, 1) if t else None}
+        rec["adapter_attn_ms"] = round(ad, 4)
+        rec["adapter_attn_share"] = round(ad / total, 4)
+        rows.append(rec)
+        print(json.dumps(rec), flush=True)
+        del ts, eng
+        torch.cuda.empty_cache()
+
+print(f"{'L':>6} {'E':>4} {'heads x d':>9} {'ms/step':>8} {'attn ms':>8} {'share':>6}  " + "  ".join(f"{k + ' ms GB/s':>26}" for k in KERNELS))
+for r in rows:
+    print(f"{r['patches']:>6} {r['E']:>4} {str(r['heads']) + ' x ' + str(r['head_dim']):>9} {r['ms_per_step']:>8.2f} {r['adapter_attn_ms']:>8.3f} "
+          f"{100 * r['adapter_attn_share']:>5.1f}%  " + "  ".join(f"{r[k]['ms_per_step']:>17.4f} {r[k]['gb_per_s']:>8}" for k in KERNELS))

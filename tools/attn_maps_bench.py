@@ -52,7 +52,7 @@ for s in sites:
     if s.startswith("prompt_"):
         moved += 4 * B * T * T * (cfg.num_heads + 1)
     elif ".injector." in s:
-        moved += B * L * (2 * E + 4 * 12) + 4 * B * L * T       # q fp16 + lse in, [B, L, T] out
+        moved += B * L * (2 * E + 4 * cfg.num_heads) + 4 * B * L * T       # q fp16 + lse in, [B, L, T] out
     else:
         moved += B * L * 2 * E + 4 * B * T * L                   # k fp16 in, [B, T, L] out
 p, m = statistics.median(times["plain"]), statistics.median(times["maps"])
