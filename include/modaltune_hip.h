@@ -278,8 +278,11 @@ int mt_pool_attn_bwd(const float* q, const mt_half* kv, const float* scores, con
 
 /* ------------------------------------------------- composite launchers: one backbone layer per call ---- */
 /* The launch list of ONE frozen backbone layer behind one entry point per direction (mt_lnqkv_fwd, mt_dilated_attn_*,
- * mt_mix_ln_outproj_*, mt_ffn_* as one sequence).  Exactly the launches listed above, in order, with the same arguments -- results
- * are bit-identical to issuing them one by one; the host makes 2 calls per layer and step instead of ~20.
+ * mt_mix_ln_outproj_*, mt_ffn_* as one sequence): the host makes 2 calls per layer and step instead of ~20.
+ * `steps`: bit i selects the i-th launch of the entry's list (the enums below, in launch order); MT_LAYER_ALL enqueues the whole
+ * list.  A tool that wants HIP events around every kernel issues the bits one call at a time: the buffers then hold the same bits
+ * as after one MT_LAYER_ALL call.  A step whose condition does not hold (the cast when dh16_valid is set) is skipped whether
+ * selected or not; which variant a step takes (pend_x, defer, dh16_valid, feeds_lower) never depends on `steps`.
  * LongNet EncoderLayer (ENC:121-175; DA:146-262; FFN:132-143), D = 768, F = ffn width.  Weights: fp32 LayerNorm affines and
  * biases, fp16 [N, K] weight caches (q rows of w_qkv / b_qkv pre-scaled by MT_QK_SCALE_LOG2) and their transposes for the dX GEMMs.
  * Buffers: saved per layer (hin, hmid fp32 [M, D]; qkv fp16 head-major; o_br fp16 [nbranch, M, D]; lse_br fp32 [nbranch, M, 16];
@@ -299,12 +302,25 @@ typedef struct {
   mt_half *u16, *br16, *t16;
   float* dh; mt_half *dy16, *dh16, *dt16, *da1, *dmixed, *dqkv16; float* delta; void* attn_ws;
 } MtLongNetLayerBuffers;
+enum { MT_LAYER_ALL = 0x7fffffff };
+/* forward, in launch order: self_attn_layer_norm (mt_layernorm_fwd; with pend_x: mt_add_layernorm_fwd, which also writes hin) ->
+ * QKV GEMM (head-major) -> mt_dilated_attn_fwd -> mt_dilated_mix_ln_fwd -> out_proj GEMM -> final_layer_norm
+ * (mt_add_layernorm_fwd: hmid = hin + drop(branch)) -> fc1 GEMM -> ffn_layernorm of gelu(a1) -> fc2 GEMM (+ hmid into `out`;
+ * with defer: the plain branch into br16). */
+enum { MT_LNF_LN1 = 1 << 0, MT_LNF_QKV = 1 << 1, MT_LNF_ATTN = 1 << 2, MT_LNF_MIX = 1 << 3, MT_LNF_OUT = 1 << 4, MT_LNF_LN2 = 1 << 5,
+       MT_LNF_FC1 = 1 << 6, MT_LNF_FFN_LN = 1 << 7, MT_LNF_FC2 = 1 << 8 };
 int mt_longnet_layer_fwd(const MtLongNetLayerWeights* w, const MtLongNetLayerBuffers* b, const MtDilatedPlan* plan, int M, int D, int F,
                          const float* pend_x, const mt_half* pend_branch, const MtDropout* pend_drop, int defer, float* out,
-                         const MtDropout* drop_attn, const MtDropout* drop_ffn, mt_stream_t stream);
+                         const MtDropout* drop_attn, const MtDropout* drop_ffn, int steps, mt_stream_t stream);
+/* backward, in launch order: fp16(drop(dh)) (only without dh16_valid) -> fc2 dX GEMM -> ffn_layernorm backward -> fc1 dX GEMM ->
+ * final_layer_norm backward (dh +=, fp16 copy in dh16) -> out_proj dX GEMM -> mt_dilated_mix_ln_bwd -> mt_dilated_attn_bwd (its
+ * three `phases` are the bits MT_ATTN_BWD_* << MT_LNB_ATTN_SHIFT: one call with the selected ones) -> QKV dX GEMM ->
+ * self_attn_layer_norm backward (dh +=; with feeds_lower also dh16). */
+enum { MT_LNB_CAST = 1 << 0, MT_LNB_FC2 = 1 << 1, MT_LNB_FFN_LN = 1 << 2, MT_LNB_FC1 = 1 << 3, MT_LNB_LN2 = 1 << 4, MT_LNB_OUT = 1 << 5,
+       MT_LNB_MIX = 1 << 6, MT_LNB_ATTN_SHIFT = 7, MT_LNB_QKV = 1 << 10, MT_LNB_LN1 = 1 << 11 };
 int mt_longnet_layer_bwd(const MtLongNetLayerWeights* w, const MtLongNetLayerBuffers* b, const MtDilatedPlan* plan, int M, int D, int F,
                          int dh16_valid, int feeds_lower, const MtDropout* drop_attn, const MtDropout* drop_ffn,
-                         const MtDropout* drop_lower_ffn, mt_stream_t stream);
+                         const MtDropout* drop_lower_ffn, int steps, mt_stream_t stream);
 /* Dense pre-norm ViT block of the TITAN configuration (TA:359-361: x + proj(attn(LN(x))), then + fc2(gelu(fc1(LN(.)))); layer scale
  * folded into w_proj / w_fc2 by the caller): qkv fp16 TOKEN-major [M, 3D], o16 fp16 [M, D], lse fp32 [M, H], a1 fp16 [M, F]. */
 typedef struct {
@@ -318,10 +334,20 @@ typedef struct {
   mt_half *u16, *br16, *t16;
   float* dh; mt_half *dy16, *dh16, *dt16, *da1, *dqkv16; float* delta;
 } MtVitBlockBuffers;
+/* forward, in launch order: norm1 (mt_layernorm_fwd_eps; with pend_x: mt_add_layernorm_fwd_eps, which also writes hin) -> QKV GEMM ->
+ * mt_dense_attn_fwd -> proj GEMM -> norm2 (mt_add_layernorm_fwd_eps: hmid = hin + branch) -> fc1 GEMM -> mt_gelu_f16_fwd ->
+ * fc2 GEMM (+ hmid into `out`; with defer: the plain branch into br16). */
+enum { MT_VBF_LN1 = 1 << 0, MT_VBF_QKV = 1 << 1, MT_VBF_ATTN = 1 << 2, MT_VBF_PROJ = 1 << 3, MT_VBF_LN2 = 1 << 4, MT_VBF_FC1 = 1 << 5,
+       MT_VBF_GELU = 1 << 6, MT_VBF_FC2 = 1 << 7 };
 int mt_vit_block_fwd(const MtVitBlockWeights* w, const MtVitBlockBuffers* b, const MtDensePlan* plan, int M, int D, int F,
-                     const float* pend_x, const mt_half* pend_branch, int defer, float* out, mt_stream_t stream);
+                     const float* pend_x, const mt_half* pend_branch, int defer, float* out, int steps, mt_stream_t stream);
+/* backward, in launch order: fp16(dh) (only without dh16_valid) -> fc2 dX GEMM -> mt_gelu_f16_bwd -> fc1 dX GEMM -> norm2 backward
+ * (dh +=, fp16 copy in dh16) -> proj dX GEMM -> mt_dense_attn_bwd (its three `phases` are the bits MT_DENSE_BWD_* <<
+ * MT_VBB_ATTN_SHIFT: one call with the selected ones) -> QKV dX GEMM -> norm1 backward (dh +=; with feeds_lower also dh16). */
+enum { MT_VBB_CAST = 1 << 0, MT_VBB_FC2 = 1 << 1, MT_VBB_GELU = 1 << 2, MT_VBB_FC1 = 1 << 3, MT_VBB_LN2 = 1 << 4, MT_VBB_PROJ = 1 << 5,
+       MT_VBB_ATTN_SHIFT = 6, MT_VBB_QKV = 1 << 9, MT_VBB_LN1 = 1 << 10 };
 int mt_vit_block_bwd(const MtVitBlockWeights* w, const MtVitBlockBuffers* b, const MtDensePlan* plan, int M, int D, int F,
-                     int dh16_valid, int feeds_lower, mt_stream_t stream);
+                     int dh16_valid, int feeds_lower, int steps, mt_stream_t stream);
 
 /* ------------------------------------------------------------ adapter ops -------------------------- */
 /* Injector attention core (AM:225-229 inside AM:359-369): for each of M patch rows and 12 heads (dim 16):

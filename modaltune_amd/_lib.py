@@ -138,10 +138,10 @@ SIGNATURES = {
     "mt_axpy_dev": [P, P, P, P, L, P],
     "mt_coords_to_grid": [P, I, F, I, P, P, P, P],
     "mt_mfma_probe": [P, I, I, P],
-    "mt_longnet_layer_fwd": [P, P, PL, I, I, I, P, P, DR, I, P, DR, DR, P],
-    "mt_longnet_layer_bwd": [P, P, PL, I, I, I, I, I, DR, DR, DR, P],
-    "mt_vit_block_fwd": [P, P, DP, I, I, I, P, P, I, P, P],
-    "mt_vit_block_bwd": [P, P, DP, I, I, I, I, I, P],
+    "mt_longnet_layer_fwd": [P, P, PL, I, I, I, P, P, DR, I, P, DR, DR, I, P],
+    "mt_longnet_layer_bwd": [P, P, PL, I, I, I, I, I, DR, DR, DR, I, P],
+    "mt_vit_block_fwd": [P, P, DP, I, I, I, P, P, I, P, I, P],
+    "mt_vit_block_bwd": [P, P, DP, I, I, I, I, I, I, P],
     "mt_alibi_dist": [P, I, P, P],
     "mt_alibi_dist_halves": [I],
     "mt_dense_attn_fwd": [P, DP, P, P, P],

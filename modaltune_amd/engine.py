@@ -898,84 +898,31 @@ class Engine:
         (mt_add_layernorm_fwd): the out_proj / fc2 GEMMs write their fp16 branch with a plain epilogue.  `pend` is the
         (stream, branch, dropout) of the layer below whose fc2 add is still outstanding; with `defer` this layer leaves
         its own fc2 add to the layer above and returns such a triple instead of writing `out`."""
-        cfg, ctx, t = self.cfg, self._ctx, self.store.tensors
+        cfg, ctx = self.cfg, self._ctx
         M, D, Fd, ws, plan = ctx["M"], cfg.embed_dim, cfg.ffn_dim, ctx["ws"], ctx["plan"]
-        p = f"encoder.layers.{l}."
-        f16 = self._frozen16
-        hin, hmid, qkv, obr, lsebr, lsetot, a1 = (ws[f"hin{l}"], ws[f"hmid{l}"], ws[f"qkv{l}"], ws[f"obr{l}"], ws[f"lsebr{l}"],
-                                                  ws[f"lsetot{l}"], ws[f"a1_{l}"])
-        st1, stin, st2, stf = ws[f"st1_{l}"], ws[f"stin_{l}"], ws[f"st2_{l}"], ws[f"stf_{l}"]
-        u16, t16 = ws["u16"], ws["t16"]
         N_tok = ctx["N"]
         d_attn, d_ffn = self._layer_drops(l, N_tok)
-        br16 = ws["br16"]
+        # (feeds_lower: nothing else touches dh between two layers of one interaction block: the lower layer can take fp16(dh)
+        # from the layer above -- LN backward's second output)
         feeds_lower = all(l != a for a, _ in cfg.interaction_indexes)
         d_lower_ffn = self._layer_drops(l - 1, N_tok)[1] if feeds_lower else None
-        if ops.TIMER is None:
-            # one C call per direction (csrc/layer.hip enqueues exactly the launches spelled out below); the instrumented
-            # pass of bench.py (ops.TIMER) keeps the launch-by-launch form so that every kernel gets its own HIP events
-            cb = ws.get(("_cb", l))
-            if cb is None:
-                cb = ws[("_cb", l)] = ops.struct_of(
-                    ops.MtLongNetLayerBuffers, hin=hin, hmid=hmid, qkv=qkv, o_br=obr, lse_br=lsebr, lse_tot=lsetot, a1=a1, st1=st1, stin=stin,
-                    st2=st2, stf=stf, u16=u16, br16=br16, t16=t16, dh=ws["dh"], dy16=ws["dy16"], dh16=ws["dh16"], dt16=ws["dt16"],
-                    da1=ws["da1"], dmixed=ws["dmixed"], dqkv16=ws["dqkv16"], delta=ws["delta"], attn_ws=ws["attn_ws"])
-            lw = self._layer_w[l]
-            ops.longnet_layer_fwd(lw, cb, plan, M, D, Fd, out, pend=pend, defer=defer, drop_attn=d_attn, drop_ffn=d_ffn)
+        cb = ws.get(("_cb", l))
+        if cb is None:
+            cb = ws[("_cb", l)] = ops.struct_of(
+                ops.MtLongNetLayerBuffers, hin=ws[f"hin{l}"], hmid=ws[f"hmid{l}"], qkv=ws[f"qkv{l}"], o_br=ws[f"obr{l}"], lse_br=ws[f"lsebr{l}"],
+                lse_tot=ws[f"lsetot{l}"], a1=ws[f"a1_{l}"], st1=ws[f"st1_{l}"], stin=ws[f"stin_{l}"], st2=ws[f"st2_{l}"], stf=ws[f"stf_{l}"],
+                u16=ws["u16"], br16=ws["br16"], t16=ws["t16"], dh=ws["dh"], dy16=ws["dy16"], dh16=ws["dh16"], dt16=ws["dt16"],
+                da1=ws["da1"], dmixed=ws["dmixed"], dqkv16=ws["dqkv16"], delta=ws["delta"], attn_ws=ws["attn_ws"])
+        lw = self._layer_w[l]
+        # one C call per direction: csrc/layer.hip holds the launch list
+        ops.longnet_layer_fwd(lw, cb, plan, M, D, Fd, out, pend=pend, defer=defer, drop_attn=d_attn, drop_ffn=d_ffn)
 
-            def bwd_c():
-                ops.longnet_layer_bwd(lw, cb, plan, M, D, Fd, bool(ctx.get("dh16_valid")), feeds_lower, drop_attn=d_attn, drop_ffn=d_ffn,
-                                      drop_lower_ffn=d_lower_ffn)
-                ctx["dh16_valid"] = feeds_lower
-            self.tape.record(bwd_c)
-            return (hmid, br16, d_ffn) if defer else None
-        if pend is None:
-            ops.layernorm_fwd(hin, t[p + "self_attn_layer_norm.weight"], t[p + "self_attn_layer_norm.bias"], u16, st1, M, D)
-        else:       # hin = hmid(l-1) + drop(fc2 branch of l-1)
-            ops.add_layernorm_fwd(pend[0], pend[1], t[p + "self_attn_layer_norm.weight"], t[p + "self_attn_layer_norm.bias"],
-                                  hin, u16, st1, M, D, drop=pend[2])
-        ops.gemm_nt(u16, f16[p + "qkv"].w, qkv, M, 3 * D, D, bias=f16[p + "bqkv"], epilogue=ops.EPI_QKV_HM)   # head-major q|k|v
-        ops.dilated_attn_fwd(qkv, plan, obr, lsebr)
-        ops.dilated_mix_ln_fwd(obr, lsebr, plan, t[p + "self_attn.inner_attn_ln.weight"], t[p + "self_attn.inner_attn_ln.bias"],
-                               u16, stin, lsetot)
-        ops.gemm_nt(u16, f16[p + "out"].w, br16, M, D, D, bias=t[p + "self_attn.out_proj.bias"])
-        ops.add_layernorm_fwd(hin, br16, t[p + "final_layer_norm.weight"], t[p + "final_layer_norm.bias"], hmid, u16, st2, M, D,
-                              drop=d_attn)       # hmid = hin + drop(out_proj branch)
-        ops.gemm_nt(u16, f16[p + "fc1"].w, a1, M, Fd, D, bias=t[p + "ffn.fc1.bias"])
-        ops.layernorm_fwd(a1, t[p + "ffn.ffn_layernorm.weight"], t[p + "ffn.ffn_layernorm.bias"], t16, stf, M, Fd, gelu_in=True)
-        if defer:
-            ops.gemm_nt(t16, f16[p + "fc2"].w, br16, M, D, Fd, bias=t[p + "ffn.fc2.bias"])
-            nxt = (hmid, br16, d_ffn)
-        else:
-            ops.gemm_nt(t16, f16[p + "fc2"].w, out, M, D, Fd, epilogue=ops.EPI_BIAS_RESID, bias=t[p + "ffn.fc2.bias"], resid=hmid, ldr=D,
-                        drop=d_ffn)
-            nxt = None
-
-        # (feeds_lower: nothing else touches dh between two layers of one interaction block: the lower layer can take fp16(dh)
-        # from here)
         def bwd():
-            dh, dy16, dt16, da1 = ws["dh"], ws["dy16"], ws["dt16"], ws["da1"]
-            # FFN: out = hmid + fc2(LN(gelu(fc1(LN(hmid)))))
-            if ctx.get("dh16_valid"):             # the layer above left fp16(dh) behind (LN backward's second output)
-                src16 = ws["dh16"]
-            else:
-                ops.cast_f32_to_f16(dh, dy16, drop=d_ffn, D=D)        # gradient of the (dropped) FFN branch output
-                src16 = dy16
-            ops.gemm_nt(src16, f16[p + "fc2"].wt, dt16, M, Fd, D)
-            ops.layernorm_bwd(dt16, a1, t[p + "ffn.ffn_layernorm.weight"], stf, da1, M, Fd, gelu_in=True)
-            ops.gemm_nt(da1, f16[p + "fc1"].wt, dy16, M, D, Fd)
-            ops.layernorm_bwd(dy16, hmid, t[p + "final_layer_norm.weight"], st2, dh, M, D, accumulate=True, dx16=ws["dh16"],
-                              dx16_drop=d_attn)
-            # attention: hmid = hin + out_proj(LN(mix(dilated(qkv(LN(hin))))))
-            ops.gemm_nt(ws["dh16"], f16[p + "out"].wt, u16, M, D, D)
-            ops.dilated_mix_ln_bwd(u16, obr, lsebr, lsetot, plan, t[p + "self_attn.inner_attn_ln.weight"], stin, ws["dmixed"], ws["delta"])
-            ops.dilated_attn_bwd(qkv, ws["dmixed"], lsetot, ws["delta"], plan, ws["attn_ws"], ws["dqkv16"])
-            ops.gemm_nt(ws["dqkv16"], f16[p + "qkv"].wt, dy16, M, D, 3 * D)
-            ops.layernorm_bwd(dy16, hin, t[p + "self_attn_layer_norm.weight"], st1, dh, M, D, accumulate=True,
-                              dx16=ws["dh16"] if feeds_lower else None, dx16_drop=d_lower_ffn if feeds_lower else None)
+            ops.longnet_layer_bwd(lw, cb, plan, M, D, Fd, bool(ctx.get("dh16_valid")), feeds_lower, drop_attn=d_attn, drop_ffn=d_ffn,
+                                  drop_lower_ffn=d_lower_ffn)
             ctx["dh16_valid"] = feeds_lower
         self.tape.record(bwd)
-        return nxt
+        return (ws[f"hmid{l}"], ws["br16"], d_ffn) if defer else None
 
     # ------------------------------------------------------------------ extractor (A.2)
     def _extractor(self, pref: str, c: Var, pe: Param, hout: torch.Tensor) -> Var:

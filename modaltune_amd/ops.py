@@ -197,14 +197,8 @@ def dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqk
 def dilated_attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16):
     if TIMER is None:
         return _dilated_attn_bwd_phase(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, ATTN_BWD_ALL)
-    for name, ph in (("dilated_attn_bwd_kv", ATTN_BWD_KV), ("dilated_attn_bwd_q", ATTN_BWD_Q), ("dilated_attn_bwd_combine", ATTN_BWD_COMBINE)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _dilated_attn_bwd_phase(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, ph)
-        e1.record()
-        TIMER.setdefault(name, []).append((e0, e1))
-        if TIMELINE is not None:
-            TIMELINE.append((name, e0, e1, torch.cuda.current_stream().cuda_stream))
+    for key, ph in (("dilated_attn_bwd_kv", ATTN_BWD_KV), ("dilated_attn_bwd_q", ATTN_BWD_Q), ("dilated_attn_bwd_combine", ATTN_BWD_COMBINE)):
+        _bracket(key, _dilated_attn_bwd_phase, qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, ph)
 
 
 # ---- dense attention with the 2-D ALiBi bias (one fp16 distance table per slide) + the other TITAN-side launchers (include/modaltune_hip.h)
@@ -244,12 +238,8 @@ def _dense_attn_bwd_phase(qkv, o, d_o, lse, plan, delta, dqkv, phases):
 def dense_attn_bwd(qkv, o, d_o, lse, plan, delta, dqkv):
     if TIMER is None:
         return _dense_attn_bwd_phase(qkv, o, d_o, lse, plan, delta, dqkv, DENSE_BWD_ALL)
-    for name, ph in (("dense_attn_delta", DENSE_BWD_DELTA), ("dense_attn_bwd_kv", DENSE_BWD_KV), ("dense_attn_bwd_q", DENSE_BWD_Q)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        _dense_attn_bwd_phase(qkv, o, d_o, lse, plan, delta, dqkv, ph)
-        e1.record()
-        TIMER.setdefault(name, []).append((e0, e1))
+    for key, ph in (("dense_attn_delta", DENSE_BWD_DELTA), ("dense_attn_bwd_kv", DENSE_BWD_KV), ("dense_attn_bwd_q", DENSE_BWD_Q)):
+        _bracket(key, _dense_attn_bwd_phase, qkv, o, d_o, lse, plan, delta, dqkv, ph)
 
 
 def gelu_f16_fwd(x, y, n=None):
@@ -299,24 +289,73 @@ def struct_of(cls, **tensors):
     return st
 
 
-def longnet_layer_fwd(w, b, plan, M, D, Fd, out, pend=None, defer=False, drop_attn=None, drop_ffn=None):
+# `steps`: bit i = the i-th launch of the entry's list (the enums of include/modaltune_hip.h).  All Python knows about a list is the
+# TIMER key of each step, in order: the string the per-op wrapper's key function gives for the same launch.  {M} {D} {F} {Q = 3D}
+# are filled in; a pair is (key without, key with) the entry's variant -- forward: `pend` given, backward: `dh16_valid` -- and None
+# a step that does not run then; LayerNorms over <= 1024 rows file under "token_side" like their per-op wrappers do.
+LAYER_ALL = 0x7FFFFFFF
+LAYER_STEPS = {
+    "longnet_layer_fwd": (("layernorm_fwd[{D}]", "add_layernorm_fwd[{D}]"), "gemm_nt[{M}x{Q}x{D}]", "dilated_attn_fwd", "dilated_mix_ln_fwd",
+                          "gemm_nt[{M}x{D}x{D}]", "add_layernorm_fwd[{D}]", "gemm_nt[{M}x{F}x{D}]", "layernorm_fwd[{F}]", "gemm_nt[{M}x{D}x{F}]"),
+    "longnet_layer_bwd": (("cast", None), "gemm_nt[{M}x{F}x{D}]", "layernorm_bwd[{F}]", "gemm_nt[{M}x{D}x{F}]", "layernorm_bwd[{D}]",
+                          "gemm_nt[{M}x{D}x{D}]", "dilated_mix_ln_bwd", "dilated_attn_bwd_kv", "dilated_attn_bwd_q", "dilated_attn_bwd_combine",
+                          "gemm_nt[{M}x{D}x{Q}]", "layernorm_bwd[{D}]"),
+    "vit_block_fwd": (("layernorm_fwd[{D}]", "add_layernorm_fwd[{D}]"), "gemm_nt[{M}x{Q}x{D}]", "dense_attn_fwd", "gemm_nt[{M}x{D}x{D}]",
+                      "add_layernorm_fwd[{D}]", "gemm_nt[{M}x{F}x{D}]", "gelu_f16_fwd", "gemm_nt[{M}x{D}x{F}]"),
+    "vit_block_bwd": (("cast", None), "gemm_nt[{M}x{F}x{D}]", "gelu_f16_bwd", "gemm_nt[{M}x{D}x{F}]", "layernorm_bwd[{D}]", "gemm_nt[{M}x{D}x{D}]",
+                      "dense_attn_delta", "dense_attn_bwd_kv", "dense_attn_bwd_q", "gemm_nt[{M}x{D}x{Q}]", "layernorm_bwd[{D}]"),
+}
+
+
+def layer_steps(entry, M, D, Fd, variant):
+    """[(bit, TIMER key)] of the launches one all-steps call of composite launcher `entry` makes, in order."""
+    out = []
+    for i, key in enumerate(LAYER_STEPS[entry]):
+        if isinstance(key, tuple):
+            key = key[bool(variant)]
+        if key is not None:
+            key = key.format(M=M, D=D, F=Fd, Q=3 * D)
+            out.append((1 << i, "token_side" if key.startswith("layernorm_") and M <= 1024 else key))
+    return out
+
+
+def _step_by_step(entry, variant, w, b, plan, M, D, Fd, *a, **k):
+    """The timed form of an all-steps call: one single-step call per launch, each under its own events, issued through the module's
+    public name (a tool that has replaced ops.<entry> sees one call per kernel)."""
+    for bit, key in layer_steps(entry, M, D, Fd, variant):
+        _bracket(key, globals()[entry], w, b, plan, M, D, Fd, *a, steps=bit, **k)
+
+
+def longnet_layer_fwd(w, b, plan, M, D, Fd, out, pend=None, defer=False, drop_attn=None, drop_ffn=None, steps=LAYER_ALL):
+    if TIMER is not None and steps == LAYER_ALL:
+        return _step_by_step("longnet_layer_fwd", pend is not None, w, b, plan, M, D, Fd, out, pend=pend, defer=defer, drop_attn=drop_attn,
+                             drop_ffn=drop_ffn)
     px, pb, pd = (pend[0], pend[1], pend[2]) if pend is not None else (None, None, None)
     check(_lib.load().mt_longnet_layer_fwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, _p(px), _p(pb), _dr(pd), int(defer), _p(out),
-                                           _dr(drop_attn), _dr(drop_ffn), _s()), "longnet_layer_fwd")
+                                           _dr(drop_attn), _dr(drop_ffn), steps, _s()), "longnet_layer_fwd")
 
 
-def longnet_layer_bwd(w, b, plan, M, D, Fd, dh16_valid, feeds_lower, drop_attn=None, drop_ffn=None, drop_lower_ffn=None):
+def longnet_layer_bwd(w, b, plan, M, D, Fd, dh16_valid, feeds_lower, drop_attn=None, drop_ffn=None, drop_lower_ffn=None, steps=LAYER_ALL):
+    if TIMER is not None and steps == LAYER_ALL:
+        return _step_by_step("longnet_layer_bwd", dh16_valid, w, b, plan, M, D, Fd, dh16_valid, feeds_lower, drop_attn=drop_attn,
+                             drop_ffn=drop_ffn, drop_lower_ffn=drop_lower_ffn)
     check(_lib.load().mt_longnet_layer_bwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, int(dh16_valid), int(feeds_lower), _dr(drop_attn),
-                                           _dr(drop_ffn), _dr(drop_lower_ffn), _s()), "longnet_layer_bwd")
+                                           _dr(drop_ffn), _dr(drop_lower_ffn), steps, _s()), "longnet_layer_bwd")
 
 
-def vit_block_fwd(w, b, plan, M, D, Fd, out, pend=None, defer=False):
+def vit_block_fwd(w, b, plan, M, D, Fd, out, pend=None, defer=False, steps=LAYER_ALL):
+    if TIMER is not None and steps == LAYER_ALL:
+        return _step_by_step("vit_block_fwd", pend is not None, w, b, plan, M, D, Fd, out, pend=pend, defer=defer)
     px, pb = (pend[0], pend[1]) if pend is not None else (None, None)
-    check(_lib.load().mt_vit_block_fwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, _p(px), _p(pb), int(defer), _p(out), _s()), "vit_block_fwd")
+    check(_lib.load().mt_vit_block_fwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, _p(px), _p(pb), int(defer), _p(out), steps, _s()),
+          "vit_block_fwd")
 
 
-def vit_block_bwd(w, b, plan, M, D, Fd, dh16_valid, feeds_lower):
-    check(_lib.load().mt_vit_block_bwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, int(dh16_valid), int(feeds_lower), _s()), "vit_block_bwd")
+def vit_block_bwd(w, b, plan, M, D, Fd, dh16_valid, feeds_lower, steps=LAYER_ALL):
+    if TIMER is not None and steps == LAYER_ALL:
+        return _step_by_step("vit_block_bwd", dh16_valid, w, b, plan, M, D, Fd, dh16_valid, feeds_lower)
+    check(_lib.load().mt_vit_block_bwd(C.byref(w), C.byref(b), C.byref(plan), M, D, Fd, int(dh16_valid), int(feeds_lower), steps, _s()),
+          "vit_block_bwd")
 
 
 def gene_snn_fwd(params, offs, sizes, goff, genes, G, latent, a1, a2, z, alpha_drop=None, passes=1):
@@ -520,6 +559,18 @@ RECORD_KEEP = []       # tensors the recorded launches point to (Tape.new append
 TIMELINE = None        # bench.py: with TIMER set, also (key, start event, end event, stream handle) of every launch, in launch order
 
 
+def _bracket(key, fn, *a, **k):
+    """fn(*a, **k) between two HIP events on the launch stream, filed under `key` in TIMER (and TIMELINE)."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    r = fn(*a, **k)
+    e1.record()
+    TIMER.setdefault(key, []).append((e0, e1))
+    if TIMELINE is not None:
+        TIMELINE.append((key, e0, e1, torch.cuda.current_stream().cuda_stream))
+    return r
+
+
 def _timed(name_fn):
     def deco(fn):
         def wrapper(*a, **k):
@@ -528,16 +579,7 @@ def _timed(name_fn):
             key = name_fn(*a, **k)
             if RECORD is not None and key == "token_side":
                 RECORD.append((fn, a, k))
-            if TIMER is None:
-                return fn(*a, **k)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            r = fn(*a, **k)
-            e1.record()
-            TIMER.setdefault(key, []).append((e0, e1))
-            if TIMELINE is not None:
-                TIMELINE.append((key, e0, e1, torch.cuda.current_stream().cuda_stream))
-            return r
+            return fn(*a, **k) if TIMER is None else _bracket(key, fn, *a, **k)
         wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
         return wrapper
     return deco

@@ -498,27 +498,8 @@ class NativeBackbone:
         """hin -> out (fp32 [M, D]).  The residual adds ride on the LayerNorm that consumes the sum (mt_add_layernorm_fwd), as in
         Engine._layer: `pend` = (stream, branch) of the block below whose fc2 add is outstanding (hin is then WRITTEN here); with
         `defer` this block leaves its own fc2 add to the block above and returns such a pair."""
-        w, D, Fd = self.blocks[l], self.D, self.F
-        u16, br16, t16 = ws["u16"], ws["br16"], ws["t16"]
-        hmid, qkv, o16, lse, a1 = ws[f"hmid{l}"], ws[f"qkv{l}"], ws[f"o{l}"], ws[f"lse{l}"], ws[f"a1_{l}"]
-        if ops.TIMER is None:      # one C call (csrc/layer.hip enqueues exactly the launches spelled out below)
-            ops.vit_block_fwd(w["cw"], self._cbuf(l, ws, hin), plan, M, D, Fd, out, pend=pend, defer=defer)
-            return (hmid, br16) if defer else None
-        if pend is None:
-            ops.layernorm_fwd(hin, w["n1w"], w["n1b"], u16, ws[f"st1_{l}"], M, D, eps=w["n1e"])
-        else:
-            ops.add_layernorm_fwd(pend[0], pend[1], w["n1w"], w["n1b"], hin, u16, ws[f"st1_{l}"], M, D, eps=w["n1e"])
-        ops.gemm_nt(u16, w["qkv"].w, qkv, M, 3 * D, D, bias=w["qkv"].b)
-        ops.dense_attn_fwd(qkv, plan, o16, lse)
-        ops.gemm_nt(o16, w["proj"].w, br16, M, D, D, bias=w["proj"].b)
-        ops.add_layernorm_fwd(hin, br16, w["n2w"], w["n2b"], hmid, u16, ws[f"st2_{l}"], M, D, eps=w["n2e"])      # hmid = hin + attention branch
-        ops.gemm_nt(u16, w["fc1"].w, a1, M, Fd, D, bias=w["fc1"].b)
-        ops.gelu_f16_fwd(a1, t16, M * Fd)
-        if defer:
-            ops.gemm_nt(t16, w["fc2"].w, br16, M, D, Fd, bias=w["fc2"].b)
-            return (hmid, br16)
-        ops.gemm_nt(t16, w["fc2"].w, out, M, D, Fd, epilogue=ops.EPI_BIAS_RESID, bias=w["fc2"].b, resid=hmid, ldr=D)
-        return None
+        ops.vit_block_fwd(self.blocks[l]["cw"], self._cbuf(l, ws, hin), plan, M, self.D, self.F, out, pend=pend, defer=defer)
+        return (ws[f"hmid{l}"], ws["br16"]) if defer else None
 
     def _cbuf(self, l: int, ws, hin: torch.Tensor, dh: Optional[torch.Tensor] = None):
         """Pointer table of block l's buffers in workspace `ws` (cached in it; `dh` is known from the first backward on)."""
@@ -534,23 +515,7 @@ class NativeBackbone:
 
     def block_bwd(self, l: int, ws: Dict[str, torch.Tensor], M: int, plan, hin: torch.Tensor, dh: torch.Tensor, dh16_valid: bool, feeds_lower: bool):
         """dh (fp32 [M, D], gradient of the block's output) -> gradient of its input, in place; activation gradients only."""
-        w, D, Fd = self.blocks[l], self.D, self.F
-        dy16, dt16, da1, u16 = ws["dy16"], ws["dt16"], ws["da1"], ws["u16"]
-        if ops.TIMER is None:
-            return ops.vit_block_bwd(w["cw"], self._cbuf(l, ws, hin, dh), plan, M, D, Fd, dh16_valid, feeds_lower)
-        if dh16_valid:
-            src16 = ws["dh16"]
-        else:
-            ops.cast_f32_to_f16(dh, dy16, M * D)
-            src16 = dy16
-        ops.gemm_nt(src16, w["fc2"].wt, dt16, M, Fd, D)
-        ops.gelu_f16_bwd(ws[f"a1_{l}"], dt16, da1, M * Fd)
-        ops.gemm_nt(da1, w["fc1"].wt, dy16, M, D, Fd)
-        ops.layernorm_bwd(dy16, ws[f"hmid{l}"], w["n2w"], ws[f"st2_{l}"], dh, M, D, accumulate=True, dx16=ws["dh16"])
-        ops.gemm_nt(ws["dh16"], w["proj"].wt, u16, M, D, D)                                   # dO
-        ops.dense_attn_bwd(ws[f"qkv{l}"], ws[f"o{l}"], u16, ws[f"lse{l}"], plan, ws["delta"], ws["dqkv16"])
-        ops.gemm_nt(ws["dqkv16"], w["qkv"].wt, dy16, M, D, 3 * D)
-        ops.layernorm_bwd(dy16, hin, w["n1w"], ws[f"st1_{l}"], dh, M, D, accumulate=True, dx16=ws["dh16"] if feeds_lower else None)
+        ops.vit_block_bwd(self.blocks[l]["cw"], self._cbuf(l, ws, hin, dh), plan, M, self.D, self.F, dh16_valid, feeds_lower)
 
     # -- final norm + attentional pooling (TA:400-402)
     def pool_fwd(self, tape, ws: Dict[str, torch.Tensor], B: int, N: int, hout: torch.Tensor) -> Tuple[Var, Var]:

@@ -53,7 +53,7 @@ else:
 ts.set_projector(synth.projector_state(3))
 genes = [torch.from_numpy(a).cuda() for a in inp["genes"]]
 text = torch.from_numpy(inp["text"]).cuda()
-ops.TIMER = {}                     # launch-by-launch form of the backbone layers (every kernel its own ops.* call)
+ops.TIMER = {}                     # timed form: the composite layer launchers issue one single-step call per kernel (ops.LAYER_STEPS)
 ts.step(x, coords, genes, text, update=False)
 torch.cuda.synchronize()
 
@@ -79,6 +79,8 @@ depth = [0]
 for n in names:
     def mk(n):
         def w(*a, **k):
+            if n in ops.LAYER_STEPS and k.get("steps", ops.LAYER_ALL) == ops.LAYER_ALL:
+                return orig[n](*a, **k)      # a layer's all-steps call: its single-step calls come back through here and are kept
             if depth[0] == 0:
                 REC.append((n, a, k))
                 keep(a); keep(k)
@@ -105,8 +107,8 @@ for n, a, k in REC:
     key = n
     if n == "gemm_nt":
         key = f"gemm_nt[{a[3]}x{a[4]}x{a[5]}]"
-    elif n in ("dilated_attn_bwd_phases", "dense_attn_bwd") or n.startswith("_"):
-        key = n
+    elif n in ops.LAYER_STEPS:           # one kernel of a backbone layer: entry and step
+        key = f"{n}[step {k['steps'].bit_length() - 1}]"
     by_name.setdefault(key, []).append((n, a, k))
 print("recorded", len(REC), "launches of", len(by_name), "kinds", flush=True)
 

@@ -27,7 +27,6 @@ ws = eng._workspace(B, L)
 plan = ops.make_plan(branch_table(N, eng.seg_lengths, DILATED_RATIOS), N, B)
 eng._ctx = dict(B=B, L=L, N=N, M=M, Mp=B * L, ws=ws, plan=plan, patch_map=rowmap(L, N, 1))
 eng._drop_now = False
-ops.TIMER = {}                     # launch-by-launch form of the layer
 tape = eng.tape
 tape.grad_enabled = True
 tape.reset()
@@ -39,31 +38,14 @@ eng._ctx["dh16_valid"] = False
 bwd = tape.back[-1]
 bwd()
 torch.cuda.synchronize()
-ops.TIMER = None
-t, f16 = eng.store.tensors, eng._frozen16
-p = "encoder.layers.0."
-u16, t16, br16, qkv, obr, lsebr, lsetot, a1 = ws["u16"], ws["t16"], ws["br16"], ws["qkv0"], ws["obr0"], ws["lsebr0"], ws["lsetot0"], ws["a1_0"]
-hin, hmid, st1, stin, st2, stf = ws["hin0"], ws["hmid0"], ws["st1_0"], ws["stin_0"], ws["st2_0"], ws["stf_0"]
-dh, dy16, dt16, da1 = ws["dh"], ws["dy16"], ws["dt16"], ws["da1"]
-AGG = {
-    "ln_fwd": lambda: ops.layernorm_fwd(hin, t[p + "self_attn_layer_norm.weight"], t[p + "self_attn_layer_norm.bias"], u16, st1, M, D),
-    "gemm_qkv(ps)": lambda: ops.gemm_nt(u16, f16[p + "qkv"].w, qkv, M, 3 * D, D, bias=f16[p + "bqkv"], epilogue=ops.EPI_QKV_HM),
-    "attn_fwd": lambda: ops.dilated_attn_fwd(qkv, plan, obr, lsebr),
-    "mix_ln_fwd": lambda: ops.dilated_mix_ln_fwd(obr, lsebr, plan, t[p + "self_attn.inner_attn_ln.weight"], t[p + "self_attn.inner_attn_ln.bias"], u16, stin, lsetot),
-    "gemm_out(768^2)": lambda: ops.gemm_nt(u16, f16[p + "out"].w, br16, M, D, D, bias=t[p + "self_attn.out_proj.bias"]),
-    "add_ln_fwd": lambda: ops.add_layernorm_fwd(hin, br16, t[p + "final_layer_norm.weight"], t[p + "final_layer_norm.bias"], hmid, u16, st2, M, D),
-    "gemm_fc1(ps)": lambda: ops.gemm_nt(u16, f16[p + "fc1"].w, a1, M, Fd, D, bias=t[p + "ffn.fc1.bias"]),
-    "ln_gelu_fwd": lambda: ops.layernorm_fwd(a1, t[p + "ffn.ffn_layernorm.weight"], t[p + "ffn.ffn_layernorm.bias"], t16, stf, M, Fd, gelu_in=True),
-    "gemm_fc2(pp)": lambda: ops.gemm_nt(t16, f16[p + "fc2"].w, br16, M, D, Fd, bias=t[p + "ffn.fc2.bias"]),
-    "gemm_dfc2": lambda: ops.gemm_nt(dy16, f16[p + "fc2"].wt, dt16, M, Fd, D),
-    "ln_gelu_bwd": lambda: ops.layernorm_bwd(dt16, a1, t[p + "ffn.ffn_layernorm.weight"], stf, da1, M, Fd, gelu_in=True),
-    "gemm_dfc1(pp)": lambda: ops.gemm_nt(da1, f16[p + "fc1"].wt, dy16, M, D, Fd),
-    "ln_bwd": lambda: ops.layernorm_bwd(dy16, hmid, t[p + "final_layer_norm.weight"], st2, ws["scratch32"].view(-1)[:M * D].view(M, D) if ws["scratch32"].numel() >= M * D else dh, M, D),
-    "mix_ln_bwd": lambda: ops.dilated_mix_ln_bwd(u16, obr, lsebr, lsetot, plan, t[p + "self_attn.inner_attn_ln.weight"], stin, ws["dmixed"], ws["delta"]),
-    "attn_bwd(kv+q+combine)": lambda: ops.dilated_attn_bwd(qkv, ws["dmixed"], lsetot, ws["delta"], plan, ws["attn_ws"], ws["dqkv16"]),
-    "gemm_dqkv": lambda: ops.gemm_nt(ws["dqkv16"], f16[p + "qkv"].wt, dy16, M, D, 3 * D),
-    "copy(hbm)": lambda: ws["dt16"].copy_(ws["t16"]),
-}
+lw, cb = eng._layer_w[0], ws[("_cb", 0)]
+# one aggressor per launch of the layer: the single-step calls of the composite launchers, named by ops.LAYER_STEPS' keys
+AGG = {}
+for entry, call in (("longnet_layer_fwd", lambda steps: ops.longnet_layer_fwd(lw, cb, plan, M, D, Fd, ws["hout0"], steps=steps)),
+                    ("longnet_layer_bwd", lambda steps: ops.longnet_layer_bwd(lw, cb, plan, M, D, Fd, False, False, steps=steps))):
+    for bit, key in ops.layer_steps(entry, M, D, Fd, False):
+        AGG[f"{entry[-3:]}.{bit.bit_length() - 1} {key}"] = lambda call=call, bit=bit: call(bit)
+AGG["copy(hbm)"] = lambda: ws["dt16"].copy_(ws["t16"])
 
 # victim: the prompt self-attention at the step's geometry (one pass, 65 tokens, 12 heads x 16)
 T, E, H = 65, 192, 12
