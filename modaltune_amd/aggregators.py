@@ -12,14 +12,13 @@ The module-level forward is the compatibility path (one pass per call, any numbe
 """
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 from typing import Any, Dict, Iterator, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import init, ops
+from . import init, ops, pass_groups
 from .config import ModelConfig
 from .engine import Engine, F32
 
@@ -102,20 +101,7 @@ def _bridge_backward(ctx, dlogits):
             elif split is None:
                 eng.backward(scaled, call=ctx.call)
             else:        # every group replays its tape on its own stream into its own gradient set; the sets are summed behind the join
-                main = torch.cuda.current_stream()
-                fork = torch.cuda.Event()
-                fork.record(main)
-                for (a, b), call, st, (gflat, _) in zip(split["groups"], ctx.call, split["streams"], split["sets"]):
-                    st.wait_event(fork)
-                    with torch.cuda.stream(st):
-                        if gflat is not store.flat_grad:
-                            gflat.zero_()
-                        eng.backward(scaled[a:b], call=call)
-                for st in split["streams"]:
-                    main.wait_stream(st)
-                for gflat, _ in split["sets"]:
-                    if gflat is not store.flat_grad:
-                        ops.axpy(store.flat_grad, gflat, 1.0, store.flat_grad)
+                module._split.backward(split, lambda gi, a, b: eng.backward(scaled[a:b], call=ctx.call[gi]))
         finally:
             eng.grad_ready_hook = hook
         ctx.call = None                                            # the tape and its private workspace are dead from here
@@ -154,30 +140,22 @@ class _ModelFn(torch.autograd.Function):
             ctx.module, ctx.call, ctx.group, ctx.has_pred = module, "replay", grp, False
             ctx.batched = module.is_multi and logits.shape[0] > 1
             return logits, torch.zeros((), dtype=F32, device=logits.device)
-        if need and grp is not None and B >= 3 and L >= module.split_min_patches and module.split_passes and not eng.collect_taps:
-            # A batched pass over a long bag runs as TWO concurrent pass groups (B - B // 3 and B // 3 task passes on two HIP streams:
-            # trainer.TrainStep._fwd_bwd_split has the measurements) -- own workspace, tape, dropout masks and gradient set per group,
-            # the task-independent patch embedding once in front of the fork.
-            sp = module._split_state()
-            groups = [(0, B - B // 3), (B - B // 3, B)]
+        if need and grp is not None and pass_groups.eligible(eng, B, L, module.split_min_patches, module.split_passes):
+            # A batched pass over a long bag runs as TWO concurrent pass groups on two HIP streams (pass_groups.py has the mechanics
+            # and the measurements) -- own workspace, tape, dropout masks and gradient set per group, the task-independent patch
+            # embedding once in front of the fork.
+            groups = pass_groups.group_bounds(B)
+            pg = module._split_state(len(groups))
             eng.prepare_shared(x, coords, grp.share)
-            main = torch.cuda.current_stream()
-            fork = torch.cuda.Event()
-            fork.record(main)
+            pg.fork(len(groups))
             calls, parts = [], []
-            for (a, b), st, gset in zip(groups, sp["streams"], sp["sets"]):
-                st.wait_event(fork)
-                with torch.cuda.stream(st):
-                    old = eng.store.use_grad_set(*gset)
-                    try:
-                        parts.append(eng.forward(x, coords, genes, onehots[a:b], need_grad=True, fresh=True, clinical=clinical, share=grp.share))
-                        calls.append(eng.last_call)
-                    finally:
-                        eng.store.use_grad_set(*old)
-            for st in sp["streams"]:
-                main.wait_stream(st)
+            for gi, (a, b) in enumerate(groups):
+                with pg.group(gi):
+                    parts.append(eng.forward(x, coords, genes, onehots[a:b], need_grad=True, fresh=True, clinical=clinical, share=grp.share))
+                    calls.append(eng.last_call)
+            pg.join()
             logits = torch.cat(parts, dim=0)
-            ctx.split = {"groups": groups, "streams": sp["streams"], "sets": sp["sets"]}
+            ctx.split = groups
             ctx.module, ctx.call, ctx.group, ctx.has_pred = module, calls, grp, token is not None
             ctx.batched = True
             return logits, torch.zeros((), dtype=F32, device=logits.device)
@@ -232,19 +210,14 @@ class LongNetGeneAdapter(Aggregator):
         self.train(True)
 
     def _split_state(self, n: int = 2):
-        """Streams and gradient sets of the pass groups a long batched pass runs as (created on first use; n > 2: experiments)."""
+        """The PassGroups of a long batched pass, shared by the eager bridge and ModuleReplay (created on first use; n > 2: experiments)."""
         if getattr(self, "_split", None) is None:
-            eng = self.engine
-            self._split = {"streams": [torch.cuda.Stream(device=eng.device) for _ in range(2)],
-                           "sets": [(eng.store.flat_grad, eng.store.grads), eng.store.new_grad_set()]}
-        while len(self._split["streams"]) < n:
-            self._split["streams"].append(torch.cuda.Stream(device=self.engine.device))
-            self._split["sets"].append(self.engine.store.new_grad_set())
-        return self._split
+            self._split = pass_groups.PassGroups(self.engine)
+        return self._split.ensure(n)
 
     def _init_nosync(self):
-        self.split_passes = os.environ.get("MT_SPLIT_PASSES", "1") not in ("0", "off")      # (see _ModelFn.forward)
-        self.split_min_patches = 7500
+        self.split_passes = pass_groups.split_mode() != "off"      # (see _ModelFn.forward)
+        self.split_min_patches = pass_groups.SPLIT_MIN_PATCHES
         self._split = None
         self.nosync_after = 2              # slides served in full by the same prediction before task tokens stop being read back (0: never)
         self._nosync_rows = self._ns_eye = self._ns_stream = self._ns_seen = None

@@ -8,13 +8,13 @@ The probes themselves (sklearn LogisticRegression / lifelines Cox, TM:329-458) a
 """
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import pass_groups
 from .config import attention_sites, coords_to_rowcol
 from .engine import Engine, F32
 
@@ -62,37 +62,33 @@ class EmbeddingExtractor:
         self._pool = None
         self.graph_replays = 0
         self.patch_size_lv0 = 1024          # TITAN configuration only (titan_adapter.py:335)
-        self.split_passes = os.environ.get("MT_SPLIT_PASSES", "1") not in ("0", "off")
-        self.split_min_patches = 7500
-        self._streams = self._tapes = None
+        self.split_passes = pass_groups.split_mode() != "off"
+        self.split_min_patches = pass_groups.SPLIT_MIN_PATCHES
+        self._pg = pass_groups.PassGroups(engine, grad_sets=False, tapes=True)
+
+    @property
+    def _streams(self):
+        return self._pg.streams or None       # (None until the first bag that ran as groups)
 
     def _forward_groups(self, B: int, L: int) -> torch.Tensor:
-        """The forward of a long bag as two concurrent pass groups (trainer.TrainStep._fwd_bwd_split, forward half): the patch
-        embedding once in front of the fork, own workspace and tape per group, logits joined behind it."""
-        eng = self.engine
-        if self._streams is None:
-            from .tape import Tape
-            self._streams = [torch.cuda.Stream(device=self.dev) for _ in range(2)]
-            self._tapes = [Tape(self.dev) for _ in range(2)]
-        a = B - B // 3
-        ws0 = eng._workspace(a, L)
+        """The forward of a long bag as two concurrent pass groups (pass_groups.py): the patch embedding once in front of the fork,
+        own workspace and tape per group, logits joined behind it."""
+        eng, pg = self.engine, self._pg
+        groups = pass_groups.group_bounds(B)
+        pg.ensure(len(groups))
+        ws0 = eng._workspace(groups[0][1], L)
         eng._embed_patches(None, None, ws0, True, L)
         share = {"x0": ws0["x0"]}
         out = torch.empty(B, eng.cfg.output_dim, dtype=F32, device=self.dev)
         maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None      # (each group writes its rows)
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        for gi, (lo, hi) in enumerate(((0, a), (a, B))):
-            st = self._streams[gi]
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
+        pg.fork(len(groups))
+        for gi, (lo, hi) in enumerate(groups):
+            with pg.group(gi):
                 lg = eng.forward(None, None, self._sgenes, self.onehots[lo:hi], need_grad=False, staged=True, geometry=(hi - lo, L),
-                                 clinical=self._sclin, share=share, tape=self._tapes[gi], site_group=gi + 1,
+                                 clinical=self._sclin, share=share, tape=pg.tapes[gi], site_group=gi + 1,
                                  attn_maps={s: w[lo:hi] for s, w in maps.items()} if maps else None)
                 out[lo:hi].copy_(lg)
-        for st in self._streams:
-            main.wait_stream(st)
+        pg.join()
         return (out, maps) if maps else out
 
     def _forward_batched(self, B: int, L: int):
@@ -136,9 +132,9 @@ class EmbeddingExtractor:
             eng._workspace(B, Lv)                                     # (may grow the workspace: bumps eng.generation)
         else:
             Lv = L
-            # long bags: the task passes as two concurrent groups (B - B // 3 and B // 3 passes on two HIP streams), as in the train step
-            split = self.split_passes and B >= 3 and L >= self.split_min_patches and eng.cfg.is_multi and not eng.collect_taps
-            gB = [B - B // 3, B // 3] if split else [B]
+            # long bags: the task passes as two concurrent groups on two HIP streams, as in the train step
+            split = pass_groups.eligible(eng, B, L, self.split_min_patches, self.split_passes)
+            gB = [hi - lo for lo, hi in pass_groups.group_bounds(B)] if split else [B]
             for nb in gB[1:]:
                 eng._workspace(nb, L)
             eng.stage_inputs(x, coords, B=gB[0])                      # (may grow the workspace: bumps eng.generation)

@@ -16,6 +16,7 @@ regenerates them from the same state).
 """
 from __future__ import annotations
 
+import gc
 import os
 import weakref
 from collections import OrderedDict
@@ -23,8 +24,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
-from .tape import Tape
+from . import ops, pass_groups
 
 F32 = torch.float32
 
@@ -59,7 +59,7 @@ class ModuleReplay:
         self.static_key = None
         self.sgenes = self.sonehots = self.sclin = None
         self.lease = None                 # weakref to the _Lease of the replayed forward whose backward is still to come
-        self.res = None                   # streams / gradient sets / tapes of the two pass groups
+        self.tapes = None                 # [0]: the batched pass, [1] ..: the pass groups (their streams and gradient sets: module._split_state)
         self.replays = self.captures = self.eager_fallbacks = self.primed = 0
         self.ncap = {}                    # captures per geometry: one that had to be captured AGAIN was evicted in between -> the cache grows
 
@@ -68,36 +68,20 @@ class ModuleReplay:
         l = self.lease() if self.lease is not None else None
         return l is not None and not l.done
 
-    def _resources(self, split: bool = False):
+    def _resources(self, groups):
+        """This class's tapes, and the module's PassGroups (shared with its eager split path) when `groups` are pass groups."""
         eng = self.module.engine
-        if self.res is None:
-            tapes = []
-            for _ in range(5):                         # [0]: the batched pass, [1] ..: the pass groups
-                t = Tape(eng.device)
-                t.on_realloc = eng._bump_generation    # captured graphs point into the tapes' gradient arenas
-                tapes.append(t)
-            self.res = {"tapes": tapes}
-        if split and "streams" not in self.res:
-            sp = self.module._split_state(3 if os.environ.get("MT_MODULE_GROUPS") == "singles" else 2)            # the module's own two streams and gradient sets (shared with its eager split path)
-            self.res.update(streams=sp["streams"], sets=sp["sets"])
-        return self.res
-
-    @staticmethod
-    def _groups(B: int):
-        if os.environ.get("MT_MODULE_GROUPS") == "singles":       # experiments: every task pass a group of its own (balanced: they meet at the loss)
-            return [(i, i + 1) for i in range(B)]
-        return [(0, B - B // 3), (B - B // 3, B)]
+        if self.tapes is None:
+            self.tapes = pass_groups.new_tapes(eng.device, 5, eng._bump_generation)      # captured graphs point into the tapes' gradient arenas
+        return self.module._split_state(len(groups)) if len(groups) > 1 else None
 
     SLOT0 = 8         # workspace slots of this class: its own, so that a TrainStep / EmbeddingExtractor / no-grad forward on the same engine
                       # (slots 0 ..) between a replayed forward and its backward cannot overwrite the saved activations
 
-    def _slots(self, groups):
-        return [self.SLOT0 + sum(1 for (a2, b2) in groups[:gi] if b2 - a2 == b - a) for gi, (a, b) in enumerate(groups)]
-
     # ---------------------------------------------------------------- forward
     def forward(self, x, coords, genes, onehots, clinical, token) -> Optional[tuple]:
-        """Returns (logits [B, O] -- a fresh tensor --, entry, lease) when this call was served by a replay (or by the capture that
-        makes the next ones replays), None when the eager path has to run it."""
+        """Returns (logits [B, O] -- a fresh tensor --, lease) when this call was served by a replay, by a priming visit or by the
+        capture that makes the next ones replays; None when the eager path has to run it."""
         m = self.module
         eng = m.engine
         if not self.enabled or token is not None or eng.collect_taps or hasattr(eng, "forward_slide"):
@@ -110,7 +94,7 @@ class ModuleReplay:
             return None
         gl = [genes] if torch.is_tensor(genes) else list(genes)
         ngenes = int(sum(g.numel() for g in gl))
-        split = bool(B >= 3 and L >= m.split_min_patches and m.split_passes)
+        split = pass_groups.eligible(eng, B, L, m.split_min_patches, m.split_passes)
         key = (L, B, ngenes, split, bool(eng.stochastic), None if clinical is None else tuple(clinical.shape))
         ent = self.cache.get(key)
         seen = self.visits.get(key, 0)
@@ -132,8 +116,8 @@ class ModuleReplay:
             self.sonehots = torch.empty(B, int(onehots.shape[1]), dtype=F32, device=dev)
             self.sclin = torch.empty(1, int(clinical.numel()), dtype=F32, device=dev) if clinical is not None else None
             self.cache.clear()
-        groups = self._groups(B) if split else [(0, B)]
-        slots = self._slots(groups)
+        groups = pass_groups.group_bounds(B, singles=os.environ.get("MT_MODULE_GROUPS") == "singles") if split else [(0, B)]      # (experiments)
+        slots = pass_groups.group_slots(groups, base=self.SLOT0)
         for (a, b), sl in list(zip(groups, slots))[1:]:
             eng._workspace(b - a, L, slot=sl)                       # (all workspaces exist -- and have grown -- before anything is captured)
         eng.stage_inputs(x2, coords, eng._workspace(groups[0][1] - groups[0][0], L, slot=slots[0]))      # (may grow the workspace: bumps eng.generation)
@@ -184,57 +168,34 @@ class ModuleReplay:
     def _forward_body(self, ent, L, B, groups, slots, split):
         m = self.module
         eng = m.engine
-        res = self._resources(split)
+        pg = self._resources(groups)
         if eng.stochastic:
             ops.rng_advance(eng.rng)
         if not split:
             logits = eng.forward(None, None, self.sgenes, self.sonehots, need_grad=True, staged=True, geometry=(B, L), clinical=self.sclin,
-                                 tape=res["tapes"][0], site_group=1, ws_slot=slots[0])
+                                 tape=self.tapes[0], site_group=1, ws_slot=slots[0])
             ent.logits.copy_(logits)
             return [eng.last_call]
         ws0 = eng._workspace(groups[0][1] - groups[0][0], L, slot=slots[0])
         eng._embed_patches(None, None, ws0, True, L)            # task-independent: once, in front of the fork
         share = {"x0": ws0["x0"]}
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
+        pg.fork(len(groups))
         calls = []
-        for gi, ((a, b), st, gset) in enumerate(zip(groups, res["streams"], res["sets"])):
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
-                old = eng.store.use_grad_set(*gset)
-                try:
-                    logits = eng.forward(None, None, self.sgenes, self.sonehots[a:b], need_grad=True, staged=True, geometry=(b - a, L),
-                                         clinical=self.sclin, share=share, tape=res["tapes"][1 + gi], site_group=gi + 1, ws_slot=slots[gi])
-                    calls.append(eng.last_call)
-                    ent.logits[a:b].copy_(logits)
-                finally:
-                    eng.store.use_grad_set(*old)
-        for st in res["streams"]:
-            main.wait_stream(st)
+        for gi, (a, b) in enumerate(groups):
+            with pg.group(gi):
+                logits = eng.forward(None, None, self.sgenes, self.sonehots[a:b], need_grad=True, staged=True, geometry=(b - a, L),
+                                     clinical=self.sclin, share=share, tape=self.tapes[1 + gi], site_group=gi + 1, ws_slot=slots[gi])
+                calls.append(eng.last_call)
+                ent.logits[a:b].copy_(logits)
+        pg.join()
         return calls
 
     def _backward_body(self, ent, calls, groups, split):
         eng = self.module.engine
-        store = eng.store
         if not split:
             eng.backward(ent.dl, call=calls[0])
             return
-        res = self._resources(True)
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
-        for (a, b), call, st, (gflat, _) in zip(groups, calls, res["streams"], res["sets"]):
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
-                if gflat is not store.flat_grad:
-                    gflat.zero_()
-                eng.backward(ent.dl[a:b], call=call)
-        for st in res["streams"]:
-            main.wait_stream(st)
-        for gflat, _ in res["sets"]:
-            if gflat is not store.flat_grad:
-                ops.axpy(store.flat_grad, gflat, 1.0, store.flat_grad)
+        self._resources(groups).backward(groups, lambda gi, a, b: eng.backward(ent.dl[a:b], call=calls[gi]))
 
     def _buffers(self, ent, B):
         eng = self.module.engine
@@ -248,8 +209,9 @@ class ModuleReplay:
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=eng.device)
         ent.split = split
-        self._resources(split)
+        self._resources(groups)
         main, side = torch.cuda.current_stream(), self.stream
+        gc.collect()          # (dead models' hipGraphs are finalised here, not inside the capture: see TrainStep._capture)
         side.wait_stream(main)
         if self.pool is None or not any(e.gf is not None for e in self.cache.values()):
             self.pool = torch.cuda.graph_pool_handle()      # (a pool dies with the last graph captured into it)

@@ -10,6 +10,7 @@ for just before AdamW -- the collectives of the upper blocks run under the backw
 """
 from __future__ import annotations
 
+import gc
 import os
 from collections import OrderedDict
 from typing import Dict, Optional, Sequence
@@ -17,7 +18,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import dp, ops
+from . import dp, ops, pass_groups
 from ._lib import rowmap
 from .engine import Engine, F32
 from .tape import Param, Var
@@ -90,33 +91,24 @@ class TrainStep:
         # compute stream -- ("grad", e0, e1): last backward kernel -> the optimiser may start (bucket all-reduces / the last bucket's
         # reduce-scatter not hidden under the backward); ("param", e0, e1): the next step's wait for the sharded parameter all-gather
         self.comm_events: Optional[list] = None
-        # The task passes of a step as TWO concurrent groups (B = 2 and B = 1 on two HIP streams) instead of one batched B = 3 pass: one
-        # group's HBM-bound kernels (LayerNorm family, branch mix, combine) run under the other's MFMA-bound ones (GEMMs, attention) and
-        # the tails of one group's launches fill with the other's workgroups -- same-box, eager: 42.0 -> 40.4-40.8 ms at L = 10 000
-        # (tools/experiments/pass_overlap.py; the same two groups one after the other on ONE stream: 45.0).  The groups share the staged
-        # input and the patch embedding (computed once before the fork), own their workspace / tape / dropout masks, and accumulate
-        # into their own flat gradient buffers (summed before the optimiser: the token-side dW products are read-modify-write).
-        # The loss is a sum over the task rows (TM:225-233), so each group runs loss + backward behind its own forward; the streams
-        # meet once, in front of the optimiser.  MT_SPLIT_PASSES=0 / split_passes=False: the batched pass.
+        # The task passes of a step as TWO concurrent groups (B = 2 and B = 1 on two HIP streams) instead of one batched B = 3 pass
+        # (pass_groups.py has the mechanics and the measurements).  The groups share the staged input and the patch embedding (computed
+        # once before the fork).  The loss is a sum over the task rows (TM:225-233), so each group runs loss + backward behind its own
+        # forward; the streams meet once, in front of the optimiser.  split_passes=False (or split_mode() "off"): the batched pass.
         B = int(self.onehots.shape[0])
-        self.split_passes = bool(split_passes) and B >= 2 and os.environ.get("MT_SPLIT_PASSES", "1") not in ("0", "off")
-        self._groups = [(0, B - B // 3 if B >= 3 else 1), (B - B // 3 if B >= 3 else 1, B)] if B >= 2 else [(0, B)]
-        if os.environ.get("MT_PASS_GROUPS") == "singles" and B >= 3:      # experiments: every task pass a group of its own (B streams)
-            self._groups = [(i, i + 1) for i in range(B)]
-        # workspace slot per group: the engine keys its workspace storage on the pass count, so groups of EQUAL size (B = 2: one pass
-        # each) must not share it -- they run concurrently on two streams
-        self._group_slots = [sum(1 for (a2, b2) in self._groups[:gi] if b2 - a2 == b - a) for gi, (a, b) in enumerate(self._groups)]
-        self._pass_streams = self._grad_sets = self._group_tapes = self._loss_parts = None
+        self.split_passes = bool(split_passes) and B >= 2 and pass_groups.split_mode() != "off"
+        self._groups = pass_groups.group_bounds(B, singles=os.environ.get("MT_PASS_GROUPS") == "singles")      # (experiments: B streams)
+        self._group_slots = pass_groups.group_slots(self._groups)
+        self._pg = pass_groups.PassGroups(engine, tapes=True, tape_on_realloc=engine._bump_generation)      # (captured graphs point into the tapes' gradient arenas)
+        self._loss_parts = None
         self._group_hook = None             # tests: called on the host after each group has been enqueued (throttles the interleaving)
-        # same-box, hipGraph replay, ms per step batched -> split: L = 16 000: 69.5 -> 67.6; 12 000: 51.4 -> 50.6; 10 000: 41.8 -> 40.5;
-        # 9 000: 37.7 -> 36.5; 8 000: 33.7 -> 32.9; 6 500: 26.6 -> 27.4 (!); 4 096: 18.2 -> 18.1; 2 500: 12.1 -> 12.2; 1 024: 8.2 -> 8.1
-        self.split_min_patches = 7500
+        self.split_min_patches = pass_groups.SPLIT_MIN_PATCHES
         # ... but between ~4 000 and ~7 500 patches the winner changes with the tile rounding of every GEMM and attention launch (round 6,
         # same box, ms batched -> groups: 4 096: 18.37 -> 17.68; 5 500: 23.47 -> 23.11; 6 500: 26.44 -> 27.09; 7 000: 28.65 -> 28.61), so a
         # geometry that is about to be CAPTURED (it keeps coming back) is decided by measurement: both schedules run eagerly a few times
         # with update=False semantics (nothing but the dropout counter moves, and that is restored) and the faster one is captured.
         # Geometries that never repeat keep the threshold.  split_passes="auto" (the default) / True (threshold only) / False.
-        self.auto_split = split_passes == "auto" and os.environ.get("MT_SPLIT_PASSES", "auto") == "auto"
+        self.auto_split = split_passes == "auto" and pass_groups.split_mode() == "auto"
         self.split_decisions: Dict[int, bool] = {}
         self.split_trials: Dict[int, dict] = {}
         # Data-parallel schedule of a long bag (world > 1).  "groups_joined": the two pass groups with PER-BUCKET joins -- their backwards
@@ -185,57 +177,43 @@ class TrainStep:
         else:
             self.reducer.start(b)
 
+    @property
+    def _pass_streams(self):
+        return self._pg.streams or None       # (None until the first step that ran as groups)
+
+    def _group_workspaces(self, L: int, split: bool, first: int = 0):
+        """The workspaces of a step over L patches (one per pass group, or the batched pass's) from group `first` on, grown to size."""
+        shapes = list(zip([b - a for a, b in self._groups], self._group_slots)) if split else [(int(self.onehots.shape[0]), 0)]
+        return [self.engine._workspace(nb, L, slot=sl) for nb, sl in shapes[first:]]
+
     def _can_split(self) -> bool:
-        """The pass groups are possible at all for this engine (multi-task model, no per-block taps; TITAN: the native backbone with its
-        native embedding)."""
+        """The pass groups are possible at all for this engine: a multi-task model, no per-block taps.  TITAN configuration: possible
+        (native backbone with its native embedding), parity-green -- and never a win: round 6, every geometry of the bench rotation
+        tried both ways, ms per replayed step batched / groups: 2 516 tokens 8.03 / 9.05, 3 027: 9.40 / 10.20, 4 001: 12.42 / 13.27,
+        4 589: 14.50 / 14.78, 5 491: 18.10 / 18.56, 6 061: 19.96 / 20.83 (twice the token-side launches for half-sized big kernels)
+        -- so no trial is spent on it; only pass_groups.split_mode() "force" runs it."""
         eng = self.engine
-        if not (self.split_passes and eng.cfg.is_multi and not eng.collect_taps):
+        if not pass_groups.eligible(eng, len(self.onehots), None, 0, self.split_passes, min_passes=2):
             return False
-        if hasattr(eng, "forward_slide"):
-            # TITAN configuration: possible (native backbone with its native embedding) but never a win -- round 6, every geometry of the
-            # bench rotation tried both ways, ms per replayed step batched / groups: 2 516 tokens 8.03 / 9.05, 3 027: 9.40 / 10.20,
-            # 4 001: 12.42 / 13.27, 4 589: 14.50 / 14.78, 5 491: 18.10 / 18.56, 6 061: 19.96 / 20.83 (twice the token-side launches for
-            # half-sized big kernels) -- so no trial is spent on it; MT_SPLIT_PASSES=force still runs it
-            bb = getattr(eng, "backbone", None)
-            return bool(os.environ.get("MT_SPLIT_PASSES") == "force" and getattr(eng, "native", False) and bb is not None
-                        and getattr(bb, "embed_w", None) is not None)
-        return True
+        if not hasattr(eng, "forward_slide"):
+            return True
+        return bool(pass_groups.split_mode() == "force" and getattr(eng, "native", False)
+                    and getattr(getattr(eng, "backbone", None), "embed_w", None) is not None)
 
     def _split_now(self, L: Optional[int] = None) -> bool:
-        eng = self.engine
-        if not (self.split_passes and eng.cfg.is_multi and not eng.collect_taps):
+        """This step runs as pass groups: "force" wherever possible, else a trial's decision for L patches, else the threshold."""
+        if not self._can_split() or (self._dp() and self.dp_schedule == "batched"):
             return False
-        if self._dp() and self.dp_schedule == "batched":
-            return False
-        if L is not None and L in self.split_decisions and os.environ.get("MT_SPLIT_PASSES") != "force":
-            return self.split_decisions[L] and self._can_split()
-        if L is not None and L < self.split_min_patches and os.environ.get("MT_SPLIT_PASSES") != "force":
-            return False
-        if hasattr(eng, "forward_slide"):
-            # TITAN configuration: built (native backbone with its native embedding), parity-green -- and 0.2-0.3 ms SLOWER at ~4k
-            # tokens (12.88 -> 13.06-13.19 ms same-box: twice the token-side launches for half-sized big kernels): only on request
-            bb = getattr(eng, "backbone", None)
-            return bool(os.environ.get("MT_SPLIT_PASSES") == "force" and getattr(eng, "native", False) and bb is not None
-                        and getattr(bb, "embed_w", None) is not None)
-        return True
-
-    def _split_setup(self):
-        eng = self.engine
-        self._pass_streams = [torch.cuda.Stream(device=self.dev) for _ in self._groups]
-        self._grad_sets = [(eng.store.flat_grad, eng.store.grads)] + [eng.store.new_grad_set() for _ in self._groups[1:]]
-        from .tape import Tape
-        self._group_tapes = []
-        for _ in self._groups:
-            t = Tape(self.dev)
-            t.on_realloc = eng._bump_generation          # captured graphs point into the tapes' gradient arenas
-            self._group_tapes.append(t)
-        self._loss_parts = [torch.zeros(1, dtype=F32, device=self.dev) for _ in self._groups]
+        if L is None or pass_groups.split_mode() == "force":
+            return True
+        return self.split_decisions[L] if L in self.split_decisions else L >= self.split_min_patches
 
     def _fwd_bwd_split(self, x, coords, genes, text, clinical, staged_geometry=None, reduce: bool = True):
         """_fwd_bwd with the task passes in two concurrent groups (see __init__)."""
-        eng = self.engine
-        if self._pass_streams is None:
-            self._split_setup()
+        eng, pg, ngroups = self.engine, self._pg, len(self._groups)
+        if self._loss_parts is None:
+            pg.ensure(ngroups)
+            self._loss_parts = [torch.zeros(1, dtype=F32, device=self.dev) for _ in self._groups]
         self._wait_params()
         eng.grad_ready_hook = None            # (world > 1: the buckets start behind the join, optimizer_step -> start_rest)
         if eng.stochastic:
@@ -254,8 +232,7 @@ class TrainStep:
                               staged=staged_geometry is not None, share=share, prologue_only=True)
             share["x0"] = share["tok"][1:]
             L = int(share["tok"].shape[0]) - 1
-            for nb, sl in zip(gB, self._group_slots):
-                eng._workspace(nb, L, slot=sl)
+            self._group_workspaces(L, True)
         else:
             if staged_geometry is None:
                 x = x.reshape(-1, x.shape[-1])
@@ -265,105 +242,72 @@ class TrainStep:
             else:
                 L = staged_geometry[1]
                 ws0 = eng._workspace(gB[0], L)         # (step_graphed staged the slide into the first group's workspace)
-            for nb, sl in list(zip(gB, self._group_slots))[1:]:
-                eng._workspace(nb, L, slot=sl)          # (grown before the fork: a growth bumps the generation)
+            self._group_workspaces(L, True, first=1)
             eng._embed_patches(None, None, ws0, True, L)        # task-independent: once, in front of the fork
             share = {"x0": ws0["x0"]}
         R, O = target.shape
         logits_all = torch.empty(R, O, dtype=F32, device=self.dev)
         self.grad_scale.copy_(self.scale)
-        main = torch.cuda.current_stream()
-        fork = torch.cuda.Event()
-        fork.record(main)
+        pg.fork(ngroups)
         # per-bucket joins: the groups' backwards advance stage by stage so that a bucket's all-reduce starts as soon as BOTH groups
         # have left its interaction block (see __init__: dp_schedule)
         joined = (self._dp() and self.dp_schedule == "groups_joined" and reduce) or self.force_bucket_joins
         eng.record_markers = bool(joined)
-        calls = []
+        calls, summed = [], set()
         self.buckets_started_early = 0
         try:
             for gi, (a, b) in enumerate(self._groups):
-                st = self._pass_streams[gi]
-                st.wait_event(fork)
-                with torch.cuda.stream(st):
-                    old = eng.store.use_grad_set(*self._grad_sets[gi])
-                    try:
-                        self._grad_sets[gi][0].zero_()
-                        if titan:
-                            logits = eng.forward_slide(None, None, genes, self.onehots[a:b], patch_size_lv0=self.patch_size_lv0, need_grad=True,
-                                                       clinical=clinical, share=share, staged=True, tape=self._group_tapes[gi], site_group=gi + 1,
-                                                       ws_slot=self._group_slots[gi])
-                        else:
-                            logits = eng.forward(None, None, genes, self.onehots[a:b], need_grad=True, staged=True, geometry=(b - a, L),
-                                                 clinical=clinical, share=share, tape=self._group_tapes[gi], site_group=gi + 1,
-                                                 ws_slot=self._group_slots[gi])
-                        call = eng.last_call
-                        dlogits = torch.empty_like(logits)
-                        ops.distill_loss(logits, target[a:b], self._loss_parts[gi], dlogits, b - a, O, 1.0, self.scale)
-                        if joined:
-                            eng.backward_begin(dlogits, call)
-                            calls.append(call)
-                        else:
-                            eng.backward(dlogits, call=call)
-                        logits_all[a:b].copy_(logits)
-                    finally:
-                        eng.store.use_grad_set(*old)
+                with pg.group(gi, zero="all"):
+                    own = dict(need_grad=True, staged=True, clinical=clinical, share=share, tape=pg.tapes[gi], site_group=gi + 1,
+                               ws_slot=self._group_slots[gi])
+                    if titan:
+                        logits = eng.forward_slide(None, None, genes, self.onehots[a:b], patch_size_lv0=self.patch_size_lv0, **own)
+                    else:
+                        logits = eng.forward(None, None, genes, self.onehots[a:b], geometry=(b - a, L), **own)
+                    call = eng.last_call
+                    dlogits = torch.empty_like(logits)
+                    ops.distill_loss(logits, target[a:b], self._loss_parts[gi], dlogits, b - a, O, 1.0, self.scale)
+                    if joined:
+                        eng.backward_begin(dlogits, call)
+                        calls.append(call)
+                    else:
+                        eng.backward(dlogits, call=call)
+                    logits_all[a:b].copy_(logits)
                 if self._group_hook is not None:
                     self._group_hook(gi)
-            fg = eng.store.flat_grad
-            summed = set()
-            if joined:
-                nint = self._nint
-                for stage in range(nint + 1):
-                    evs = []
-                    for gi, call in enumerate(calls):
-                        st = self._pass_streams[gi]
-                        with torch.cuda.stream(st):
-                            blk = eng.backward_stage(call)
-                            if stage < nint:
-                                if blk != nint - 1 - stage:
-                                    raise RuntimeError(f"pass group {gi}: backward stage {stage} ended at block marker {blk}")
-                                ev = torch.cuda.Event()
-                                ev.record(st)
-                                evs.append(ev)
-                            elif blk is not None:
-                                raise RuntimeError(f"pass group {gi}: a block marker ({blk}) below the last stage")
-                    if stage == nint:
-                        break
-                    # bucket `stage` (= the parameters of block nint - 1 - stage, and the head for stage 0) is final in every group's
-                    # set: sum its ranges on the main stream and start its all-reduce; the groups keep running their lower blocks
-                    for ev in evs:
-                        main.wait_event(ev)
-                    for o, n in self.reducer.buckets[stage]:
-                        for flat, _ in self._grad_sets[1:]:
-                            ops.axpy(fg[o:o + n], flat[o:o + n], 1.0, fg[o:o + n])
-                    summed.add(stage)
-                    self.buckets_started_early += 1
-                    if self._cap is not None:
-                        # under capture the graph is cut here (the collective is launched eagerly between two replays): a cut needs
-                        # every forked stream back on the capture stream, so the groups re-fork behind it
-                        self._segment_break(stage)
-                        fork = torch.cuda.Event()
-                        fork.record(main)
-                        for st in self._pass_streams:
-                            st.wait_event(fork)
-                    else:
-                        self.reducer.start(stage)
+            nint = self._nint
+            for stage in range(nint + 1 if joined else 0):
+                for gi, call in enumerate(calls):
+                    with pg.group(gi, wait=False, bind=False):
+                        blk = eng.backward_stage(call)
+                        if blk != (nint - 1 - stage if stage < nint else None):
+                            raise RuntimeError(f"pass group {gi}: backward stage {stage} ended at block marker {blk}")
+                if stage == nint:
+                    break
+                # bucket `stage` (= the parameters of block nint - 1 - stage, and the head for stage 0) is final in every group's
+                # set: sum its ranges on the main stream and start its all-reduce; the groups keep running their lower blocks
+                pg.join()
+                pg.sum_sets(self.reducer.buckets[stage])
+                summed.add(stage)
+                self.buckets_started_early += 1
+                if self._cap is not None:
+                    # under capture the graph is cut here (the collective is launched eagerly between two replays): a cut needs
+                    # every forked stream back on the capture stream, so the groups re-fork behind it
+                    self._segment_break(stage)
+                    pg.fork(ngroups, wait_all=True)
+                else:
+                    self.reducer.start(stage)
         finally:
             eng.record_markers = False
-            for st in self._pass_streams:
-                main.wait_stream(st)
+            pg.join()
         # the streams have met: one gradient buffer, one loss (buckets summed at their own joins are left alone: their all-reduce
         # may be in flight)
         if summed:
             for b, bk in enumerate(self.reducer.buckets):
                 if b not in summed:
-                    for o, n in bk:
-                        for flat, _ in self._grad_sets[1:]:
-                            ops.axpy(fg[o:o + n], flat[o:o + n], 1.0, fg[o:o + n])
+                    pg.sum_sets(bk)
         else:
-            for flat, _ in self._grad_sets[1:]:
-                ops.axpy(fg, flat, 1.0, fg)
+            pg.sum_sets()
         ops.axpy(self._loss_parts[0], self._loss_parts[1], 1.0, self.loss)
         for part in self._loss_parts[2:]:
             ops.axpy(self.loss, part, 1.0, self.loss)
@@ -492,19 +436,17 @@ class TrainStep:
             # TITAN configuration: the gridding kernels and the one host read-back (the token count: every shape downstream depends
             # on it) run eagerly; the captured part starts at the token gather and is keyed on (patches, TOKENS).
             Lv = eng.stage_slide(x, coords, self.patch_size_lv0)
-            for nb, sl in (list(zip([b - a for a, b in self._groups], self._group_slots)) if self._split_now(Lv) else [(B, 0)]):
-                eng._workspace(nb, Lv, slot=sl)   # (may grow the workspace: bumps eng.generation)
+            self._group_workspaces(Lv, self._split_now(Lv))      # (may grow the workspace: bumps eng.generation)
         else:
             Lv = L
-            gB = [b - a for a, b in self._groups] if self._split_now(L) else [B]
-            for nb, sl in list(zip(gB, self._group_slots))[1:]:
-                eng._workspace(nb, L, slot=sl)    # (all groups' workspaces exist -- and have grown -- before anything is captured)
-            eng.stage_inputs(x, coords, B=gB[0])  # (may grow the workspace: bumps eng.generation)
+            split = self._split_now(L)
+            self._group_workspaces(L, split, first=1)     # (all groups' workspaces exist -- and have grown -- before anything is captured)
+            eng.stage_inputs(x, coords, B=self._groups[0][1] - self._groups[0][0] if split else B)      # (may grow the workspace: bumps eng.generation)
         if self.auto_split and Lv not in self.split_decisions and B >= 3 and Lv >= 2048 and not self._dp() and self._can_split():
             # this geometry's schedule is still to be decided by a trial (below, on the visit that captures it): the workspaces of BOTH
             # schedules exist and have grown NOW, on an eager visit -- a growth bumps eng.generation and retires every capture
-            for nb, sl in [(B, 0)] + list(zip([b - a for a, b in self._groups], self._group_slots)):
-                eng._workspace(nb, Lv, slot=sl)
+            self._group_workspaces(Lv, False)
+            self._group_workspaces(Lv, True)
         self._wait_params()                       # last step's sharded parameter all-gather ran under the staging above
         self._sgenes.copy_(gflat, non_blocking=True)
         self._stext.copy_(text, non_blocking=True)
@@ -612,6 +554,10 @@ class TrainStep:
         return segs or None
 
     def _capture(self, ent: _Captured, fwd_bwd, world: int):
+        # Dead models that sit in reference cycles (a module and its ModuleReplay point at each other) keep their hipGraphs until the
+        # cyclic collector runs -- on whatever allocation, and a graph finalised INSIDE a capture aborts the process.  Collect them
+        # here, as torch.cuda.graph does on entry.
+        gc.collect()
         torch.cuda.synchronize()
         main = torch.cuda.current_stream()
         if self._cap_stream is None:          # ONE capture stream: the allocator hands a freed block only to the stream it was
