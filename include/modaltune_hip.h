@@ -528,6 +528,49 @@ int mt_scatter_rows_f32(const float* src, const int* src_idx, const int* idx, fl
                         mt_stream_t stream);
 int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_stream_t stream);
 
+/* ------------------------------------------------------- deterministic twins ------------------------ */
+/* The six launchers above that accumulate a trainable-parameter gradient with fp32 atomics (in whatever order their workgroups
+ * retire), in a bit-reproducible form: no atomic, global or LDS, executes.  Every workgroup stores its partial result with plain
+ * stores to its own slot of `partials` (a pure function of its block index), then ONE reduce kernel (csrc/det_reduce.hip) adds the
+ * slots in ascending order and adds the sum to the destination -- the `+=` of the default forms is kept, and every output that is not
+ * reduced across workgroups (dx, dx_f16, dproj, the patch-side dq, dkv) has the default form's bits.  Arguments as in the default
+ * form, plus the caller's fp32 workspace: `partials` (16-byte aligned) of `partials_elems` floats, at least what the `_det_elems`
+ * query of the same shape returns (host arithmetic only; a negative MtStatus for a shape the twin rejects).  A NULL or short
+ * workspace returns MT_ERR_BAD_ARG before any launch.  The workspace needs no initialisation: no slot is read that was not written
+ * by the same call.  Like everything here: no allocation, no synchronisation; two calls in flight need two workspaces.
+ *   mt_gemm_tn_f16_det        slots = the row ranges of the M-split that hold rows; [slots][N1][N2], then [slots][N1] with colsum
+ *   mt_colsum_f16_det         [cdiv(M, 256)][N]
+ *   mt_layernorm_bwd_det      dw and db required; [min(cdiv(M, 4), 512)][2][D]
+ *   mt_inject_resid_bwd_det   [min(cdiv(M, 4), 512)][D]
+ *   mt_inject_attn_bwd_hd_det [cdiv(rows_per_pass, 512)][B][T][E] for dk, then the same for dv
+ *   mt_extract_attn_bwd_hd_det [cdiv(L, 512)][B][T][E] */
+long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum);
+int mt_gemm_tn_f16_det(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb, const MtRowMap* bmap,
+                       int M, int N1, int N2, float* C, long ldc, float* colsum, float* partials, long partials_elems,
+                       mt_stream_t stream);
+long mt_colsum_f16_det_elems(int M, int N);
+int mt_colsum_f16_det(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, float* partials,
+                      long partials_elems, mt_stream_t stream);
+long mt_layernorm_bwd_det_elems(int M, int D);
+int mt_layernorm_bwd_det(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
+                         const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
+                         long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
+                         mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, float* partials, long partials_elems,
+                         mt_stream_t stream);
+long mt_inject_resid_bwd_det_elems(int M, int D);
+int mt_inject_resid_bwd_det(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
+                            const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
+                            const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,
+                            float* partials, long partials_elems, mt_stream_t stream);
+long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T, int heads, int head_dim);
+int mt_inject_attn_bwd_hd_det(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
+                              int rows_per_pass, const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq,
+                              float* dk, float* dv, float* partials, long partials_elems, mt_stream_t stream);
+long mt_extract_attn_bwd_hd_det_elems(int B, int T, int L, int heads, int head_dim);
+int mt_extract_attn_bwd_hd_det(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
+                               int B, int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, float* partials,
+                               long partials_elems, mt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,9 +157,24 @@ SIGNATURES = {
     "mt_titan_gather_tokens": [P, P, I, I, P, P],
     "mt_scatter_rows_f32": [P, P, P, P, I, I, I, P],
     "mt_row_absmax_f32": [P, P, I, I, P],
+    # deterministic twins: the default form's arguments + (partials, partials_elems); `_det_elems`: host-only size queries
+    "mt_gemm_tn_f16_det_elems": [I, I, I, I],
+    "mt_gemm_tn_f16_det": [P, L, RM, P, L, RM, I, I, I, P, L, P, P, L, P],
+    "mt_colsum_f16_det_elems": [I, I],
+    "mt_colsum_f16_det": [P, L, RM, I, I, P, P, L, P],
+    "mt_layernorm_bwd_det_elems": [I, I],
+    "mt_layernorm_bwd_det": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P, L, P],
+    "mt_inject_resid_bwd_det_elems": [I, I],
+    "mt_inject_resid_bwd_det": [P, L, RM, P, L, RM, P, P, P, L, RM, I, P, P, I, I, P, L, P],
+    "mt_inject_attn_bwd_hd_det_elems": [I, I, I, I, I],
+    "mt_inject_attn_bwd_hd_det": [P, P, P, P, I, I, P, P, I, I, I, P, P, P, P, L, P],
+    "mt_extract_attn_bwd_hd_det_elems": [I, I, I, I, I],
+    "mt_extract_attn_bwd_hd_det": [P, P, P, P, P, I, I, I, I, I, P, P, P, L, P],
 }
 _RESTYPE = {"mt_status_string": C.c_char_p, "mt_build_id": C.c_char_p, "mt_dilated_attn_bwd_workspace_bytes": C.c_long, "mt_pool_attn_workspace_floats": C.c_long,
-             "mt_alibi_dist_halves": C.c_long}
+             "mt_alibi_dist_halves": C.c_long,
+             **{n + "_det_elems": C.c_long for n in ("mt_gemm_tn_f16", "mt_colsum_f16", "mt_layernorm_bwd", "mt_inject_resid_bwd",
+                                                     "mt_inject_attn_bwd_hd", "mt_extract_attn_bwd_hd")}}
 
 _lib = None
 

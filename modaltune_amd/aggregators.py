@@ -13,7 +13,7 @@ The module-level forward is the compatibility path (one pass per call, any numbe
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Any, Dict, Iterator, Sequence, Tuple
+from typing import Any, Dict, Iterator, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
@@ -177,14 +177,16 @@ class LongNetGeneAdapter(Aggregator):
     CLINICAL = False
 
     def __init__(self, gene_group_defination: Dict[Any, Sequence[str]] = None, multi_task: int = 1, device="cuda",
-                 weights_location: str = None, init_seed: int = None, **kwargs):
+                 weights_location: str = None, init_seed: int = None, deterministic: Optional[bool] = None, **kwargs):
+        """deterministic (a create-time keyword of this port, not a reference constructor key; None: MT_DETERMINISTIC=1 or
+        torch.use_deterministic_algorithms(True)): the engine's bit-reproducible mode (Engine.__init__)."""
         super().__init__()
         gene_group_defination = gene_group_defination or {}
         cfg = ModelConfig.from_longnet_ctor(kwargs, multi_task=multi_task, clinical=self.CLINICAL)
         self.cfg = cfg
         self.is_multi = multi_task > 1                       # longvit_adapter.py:88 (read at TM:174)
         sizes = [len(v) for v in gene_group_defination.values()]
-        self.engine = Engine(cfg, sizes, device)
+        self.engine = Engine(cfg, sizes, device, deterministic=deterministic)
         # The reference's constructor leaves a TRAINABLE model behind (longvit_adapter.py:162,176-203: every adapter / gene / head
         # module initialised, gamma = init_values) on a backbone loaded from {GIGAPATH_WEIGHT_LOC}/slide_encoder.pth when
         # `pretrained` (longvit_adapter.py:75-77; a missing file warns and keeps the random init, slide_encoder.py:317-322).

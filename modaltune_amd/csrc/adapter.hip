@@ -169,7 +169,9 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
 // and 32..63).  LDS at T = 128: 93 / 113 / 155 KiB at HD = 16 / 32 / 64; at T = 65: 56 / 75 / 112 KiB (two workgroups per CU at 16 and
 // 32, one at 64).
 constexpr int IBR = 128, ITILES = 4, RSTR = IBR + 8;   // RSTR: halves per transposed row (272 B: conflict-free b128)
-template <int HD, int HC>
+// DET (deterministic mode, det_reduce.hip): dk / dv are partial workspaces [gridDim.x][B][T][E]; the workgroup stores its sums to slot
+// blockIdx.x (its row block) with plain stores -- every (t < T, column) of a slot is owned by one lane of one (head, pass) workgroup.
+template <int HD, int HC, bool DET = false>
 __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restrict__ q, const h16* __restrict__ a,
                                                               const float* __restrict__ lse, const h16* __restrict__ da,
                                                               int rows_per_pass, const float* __restrict__ k,
@@ -315,7 +317,11 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            if (t < T) atomicAdd(&dst[((long)b * T + t) * AE + h * AD + 32 * j2 + l31], acc[j][j2][i]);
+            if constexpr (DET) {
+              if (t < T) dst[(((long)blockIdx.x * gridDim.z + b) * T + t) * AE + h * AD + 32 * j2 + l31] = acc[j][j2][i];
+            } else {
+              if (t < T) atomicAdd(&dst[((long)b * T + t) * AE + h * AD + 32 * j2 + l31], acc[j][j2][i]);
+            }
           }
       }
     }
@@ -506,7 +512,8 @@ __global__ void extract_attn_reduce_kernel(const float* __restrict__ part_acc, c
 // token block w); one atomic per (token, dim) per workgroup at the end.  q (pre-scaled by 1/sqrt(HD)) and dout are rounded to
 // fp16 for the MFMA, as in the forward.  LDS at T = 128: 60 KiB at HD = 16 (two workgroups per CU), 80 KiB at 32, 121 KiB at 64 (one).
 constexpr int EBK = 128, ETILES = 4;
-template <int HD, int HC>
+// DET (deterministic mode): dq is the partial workspace [gridDim.x][B][T][E], slot = blockIdx.x (the key block), plain stores.
+template <int HD, int HC, bool DET = false>
 __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
                                                                const float* __restrict__ out, const float* __restrict__ lse,
                                                                const float* __restrict__ dout, int T, int L, int heads, float* __restrict__ dq,
@@ -644,7 +651,11 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int t = wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-        if (t < T) atomicAdd(&dq[((long)b * T + t) * AE + h * AD + 32 * j + l31], accq[j][i]);
+        if constexpr (DET) {
+          if (t < T) dq[(((long)blockIdx.x * gridDim.z + b) * T + t) * AE + h * AD + 32 * j + l31] = accq[j][i];
+        } else {
+          if (t < T) atomicAdd(&dq[((long)b * T + t) * AE + h * AD + 32 * j + l31], accq[j][i]);
+        }
       }
   }
 }
@@ -1023,7 +1034,7 @@ int launch_inject_fwd(const h16* q, int rows_per_pass, int B, const float* k, co
   return MT_OK;
 }
 
-template <int HD, int HC>
+template <int HD, int HC, bool DET = false>
 int launch_inject_bwd(const h16* q, const h16* a, const float* lse, const h16* da, int rows_per_pass, int B, const float* k, const float* v,
                       int T, int heads, h16* dq, float* dk, float* dv, hipStream_t stream) {
   using Dm = AdDim<HD>;
@@ -1032,10 +1043,10 @@ int launch_inject_bwd(const h16* q, const h16* a, const float* lse, const h16* d
   if (shm > (size_t)LDS_MAX) return MT_ERR_UNSUPPORTED;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)inject_attn_bwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)inject_attn_bwd_kernel<HD, HC, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     attr_set = true;
   }
-  hipLaunchKernelGGL((inject_attn_bwd_kernel<HD, HC>), dim3(cdiv(rows_per_pass, IBR * ITILES), heads, B), dim3(256), shm, stream, q, a, lse,
+  hipLaunchKernelGGL((inject_attn_bwd_kernel<HD, HC, DET>), dim3(cdiv(rows_per_pass, IBR * ITILES), heads, B), dim3(256), shm, stream, q, a, lse,
                      da, rows_per_pass, k, v, T, heads, dq, dk, dv);
   MT_CHECK_LAUNCH();
   return MT_OK;
@@ -1061,7 +1072,7 @@ int launch_extract_fwd(const float* q, const h16* kv, int B, int T, int L, int h
   return MT_OK;
 }
 
-template <int HD, int HC>
+template <int HD, int HC, bool DET = false>
 int launch_extract_bwd(const float* q, const h16* kv, const float* out, const float* lse, const float* dout, int B, int T, int L, int heads,
                        float* dq, h16* dkv, hipStream_t stream) {
   using Dm = AdDim<HD>;
@@ -1069,10 +1080,10 @@ int launch_extract_bwd(const float* q, const h16* kv, const float* out, const fl
   const size_t shm = sizeof(float) * (2 * TMAX) + sizeof(h16) * ((size_t)2 * TBk * Dm::KP + 2 * HD * Dm::TPV + (size_t)(T + HD) * RSTR);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)extract_attn_bwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)extract_attn_bwd_kernel<HD, HC, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     attr_set = true;
   }
-  hipLaunchKernelGGL((extract_attn_bwd_kernel<HD, HC>), dim3(cdiv(L, EBK * ETILES), heads, B), dim3(256), shm, stream, q, kv, out, lse, dout,
+  hipLaunchKernelGGL((extract_attn_bwd_kernel<HD, HC, DET>), dim3(cdiv(L, EBK * ETILES), heads, B), dim3(256), shm, stream, q, kv, out, lse, dout,
                      T, L, heads, dq, dkv);
   MT_CHECK_LAUNCH();
   return MT_OK;
@@ -1199,6 +1210,40 @@ extern "C" int mt_inject_attn_bwd(const mt_half* q, const mt_half* a, const floa
   return mt_inject_attn_bwd_hd(q, a, lse, da, M, rows_per_pass, k, v, T, 12, 16, dq, dk, dv, stream);
 }
 
+// deterministic twin (det_reduce.hip): partials = dk slots [row blocks][B][T][E], then dv slots likewise; row blocks =
+// cdiv(rows_per_pass, 512), E = heads * head_dim.  Rows t >= T of a slot do not exist.
+extern "C" long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T, int heads, int head_dim) {
+  if (M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim) ||
+      (head_dim != 16 && head_dim != 32 && head_dim != 64))
+    return MT_ERR_BAD_ARG;
+  return 2L * cdiv(rows_per_pass, IBR * ITILES) * (M / rows_per_pass) * T * heads * head_dim;
+}
+
+extern "C" int mt_inject_attn_bwd_hd_det(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M, int rows_per_pass,
+                                         const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq, float* dk,
+                                         float* dv, float* partials, long partials_elems, mt_stream_t stream) {
+  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || !partials) return MT_ERR_BAD_ARG;
+  const long need = mt_inject_attn_bwd_hd_det_elems(M, rows_per_pass, T, heads, head_dim);
+  if (need < 0 || partials_elems < need) return MT_ERR_BAD_ARG;
+  const int slots = cdiv(rows_per_pass, IBR * ITILES), E = heads * head_dim;
+  const long slot = (long)(M / rows_per_pass) * T * E;
+  float* pk = partials;
+  float* pv = partials + slots * slot;
+  int rc = MT_ERR_UNSUPPORTED;
+#define AD_CALL(HD, HC)                                                                                                              \
+  launch_inject_bwd<HD, HC, true>((const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, M / rows_per_pass, k, v, T, heads, \
+                                  (h16*)dq, pk, pv, (hipStream_t)stream)
+  if (head_dim == 16 && heads == 12) rc = AD_CALL(16, 12);
+  else if (head_dim == 16) rc = AD_CALL(16, 0);
+  else if (head_dim == 32) rc = AD_CALL(32, 0);
+  else if (head_dim == 64) rc = AD_CALL(64, 0);
+#undef AD_CALL
+  if (rc != MT_OK) return rc;
+  rc = mt_det_reduce_launch(pk, slots, (M / rows_per_pass) * T, E, slot, dk, E, (hipStream_t)stream);
+  if (rc != MT_OK) return rc;
+  return mt_det_reduce_launch(pv, slots, (M / rows_per_pass) * T, E, slot, dv, E, (hipStream_t)stream);
+}
+
 extern "C" int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
                                       float* lse, float* part_acc, float* part_ml, int nsplit, mt_stream_t stream) {
   if (!q || !kv || !out || !lse || !part_acc || !part_ml || B < 1 || T < 1 || T > TMAX || L < 1 || nsplit < 1 ||
@@ -1224,6 +1269,33 @@ extern "C" int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const f
 #define AD_CALL(HD, HC) launch_extract_bwd<HD, HC>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, dq, (h16*)dkv, (hipStream_t)stream)
   AD_DISPATCH(heads, head_dim, AD_CALL);
 #undef AD_CALL
+}
+
+// deterministic twin: partials = dq slots [key blocks][B][T][E], key blocks = cdiv(L, 512)
+extern "C" long mt_extract_attn_bwd_hd_det_elems(int B, int T, int L, int heads, int head_dim) {
+  if (B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim) || (head_dim != 16 && head_dim != 32 && head_dim != 64))
+    return MT_ERR_BAD_ARG;
+  return (long)cdiv(L, EBK * ETILES) * B * T * heads * head_dim;
+}
+
+extern "C" int mt_extract_attn_bwd_hd_det(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout, int B,
+                                          int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, float* partials,
+                                          long partials_elems, mt_stream_t stream) {
+  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || !partials) return MT_ERR_BAD_ARG;
+  const long need = mt_extract_attn_bwd_hd_det_elems(B, T, L, heads, head_dim);
+  if (need < 0 || partials_elems < need) return MT_ERR_BAD_ARG;
+  const int slots = cdiv(L, EBK * ETILES);
+  const long slot = (long)B * T * heads * head_dim;
+  int rc = MT_ERR_UNSUPPORTED;
+#define AD_CALL(HD, HC) \
+  launch_extract_bwd<HD, HC, true>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, partials, (h16*)dkv, (hipStream_t)stream)
+  if (head_dim == 16 && heads == 12) rc = AD_CALL(16, 12);
+  else if (head_dim == 16) rc = AD_CALL(16, 0);
+  else if (head_dim == 32) rc = AD_CALL(32, 0);
+  else if (head_dim == 64) rc = AD_CALL(64, 0);
+#undef AD_CALL
+  if (rc != MT_OK) return rc;
+  return mt_det_reduce_launch(partials, slots, B * T, heads * head_dim, slot, dq, heads * head_dim, (hipStream_t)stream);
 }
 
 extern "C" int mt_extract_attn_bwd(const float* q, const mt_half* kv, const float* out, const float* lse,

@@ -163,3 +163,6 @@ MT_DEVINL void stg8(h16* p, h16x8 v) { *reinterpret_cast<h16x8*>(p) = v; }
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// det_reduce.hip: dst[r * ldd + c] += sum over slots i = 0 .. nparts - 1, ascending, of partials[i * part_stride + r * cols + c]
+int mt_det_reduce_launch(const float* partials, int nparts, int rows, int cols, long part_stride, float* dst, long ldd, hipStream_t s);

@@ -559,7 +559,12 @@ struct GemmTnArgs {
   float* colsum;      // optional [N1]
 };
 
-template <int TM, int TN>
+// DET (deterministic mode, det_reduce.hip): no atomics.  g.C is the partial workspace [non-empty splits][N1][ldc = N2] and g.colsum
+// (optional) [non-empty splits][N1]: the workgroup of (tile, split) stores its tile -- and its column sums, added up in row order
+// through an LDS image -- to slot split_id with plain stores.  The 32-row steps are dealt out evenly over the first
+// min(steps, launched splits) splits (rows_per_split is not read): every one of those holds rows, the rest return before they store
+// and own no slot -- so the slot count never shrinks as M grows (a workspace sized for a long bag serves every shorter one).
+template <int TM, int TN, bool DET = false>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnArgs g) {
   constexpr int SA = TM + 8, SB = TN + 8;       // halves per LDS row (+16 B: 8-byte aligned tr reads, 16-B aligned writes)
   constexpr int CA = TM / 64, CB = TN / 64;     // 16-byte chunks per thread per step (32 rows x T/8 chunks over 256 threads)
@@ -572,9 +577,17 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnArgs g) {
   const int tiles_x = g.N1 / TM, tiles = tiles_x * (g.N2 / TN);
   const int slot = blockIdx.x >> 3, tile = slot % tiles, split_id = (slot / tiles) * 8 + (blockIdx.x & 7);
   const int n1_0 = (tile % tiles_x) * TM, n2_0 = (tile / tiles_x) * TN;
-  const int mbeg = split_id * g.rows_per_split;
-  const int mend = min(g.M, mbeg + g.rows_per_split);
-  if (mbeg >= mend) return;
+  int mbeg, mend;
+  if constexpr (DET) {
+    const int steps = (g.M + 31) / 32, nsplit = min(steps, (int)(gridDim.x / tiles));
+    if (split_id >= nsplit) return;
+    mbeg = (int)((long)split_id * steps / nsplit) * 32;
+    mend = min(g.M, (int)((long)(split_id + 1) * steps / nsplit) * 32);
+  } else {
+    mbeg = split_id * g.rows_per_split;
+    mend = min(g.M, mbeg + g.rows_per_split);
+    if (mbeg >= mend) return;
+  }
   const bool want_cs = g.colsum != nullptr && n2_0 == 0;
   // staging: chunk c = i * 256 + tid of a 32-row tile: row c / (T / 8), chunk column c % (T / 8)
   h16x8 ra[CA], rb[CB];
@@ -663,9 +676,29 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnArgs g) {
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const int n2 = n2_0 + wn * (TN / 2) + j * 16 + fr;
-        atomicAdd(&g.C[(long)n1 * g.ldc + n2], acc[i][j][r]);
+        if constexpr (DET) g.C[((long)split_id * g.N1 + n1) * g.ldc + n2] = acc[i][j][r];
+        else atomicAdd(&g.C[(long)n1 * g.ldc + n2], acc[i][j][r]);
       }
     }
+  if constexpr (DET) {
+    if (want_cs) {      // [32 rows of a step][TM] image over the A tiles (free behind the loop's last barrier): one thread per column adds
+      float* img = reinterpret_cast<float*>(&As[0][0]);      // its 32 rows in ascending order -- 4-byte reads only
+      static_assert(sizeof(As) >= sizeof(float) * 32 * TM, "column-sum image must fit the A tiles");
+#pragma unroll
+      for (int i = 0; i < CA; ++i) {
+        const int c = i * 256 + tid, row = c / (TM / 8), kc = c % (TM / 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) img[row * TM + kc * 8 + e] = cs[i][e];
+      }
+      __syncthreads();
+      if (tid < TM) {
+        float t = 0.f;
+        for (int r = 0; r < 32; ++r) t += lds_f32(&img[r * TM + tid]);
+        g.colsum[(long)split_id * g.N1 + n1_0 + tid] = t;
+      }
+    }
+    return;
+  }
   if (want_cs) {      // the threads of one chunk column hold partial sums over their rows: meet in LDS, one global atomic per column
 #pragma unroll
     for (int i = 0; i < CA; ++i) {
@@ -679,6 +712,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnArgs g) {
 }
 
 // block = 32 column groups of 8 (16-byte loads) x 8 row lanes over a slab of rows; one atomic per column per block
+// DET (deterministic mode): out is the partial workspace [gridDim.y][N], one plain-stored row per blockIdx.y
+template <bool DET = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const h16* A, long lda, RowMap amap, int M, int N,
                                                      int rows_per_block, float* out) {
   const int cg = threadIdx.x & 31, rl = threadIdx.x >> 5;
@@ -702,7 +737,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const h16* A, long lda, Row
     float t = 0.f;
 #pragma unroll
     for (int r = 0; r < 8; ++r) t += red[r][c];
-    atomicAdd(&out[blockIdx.x * 256 + c], t);
+    if constexpr (DET) out[(long)blockIdx.y * N + blockIdx.x * 256 + c] = t;
+    else atomicAdd(&out[blockIdx.x * 256 + c], t);
   }
 }
 
@@ -951,6 +987,12 @@ extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   }
 }
 
+// 64 x 64 tiles and ~1024 workgroups (512 for the small products), a multiple of the 8 XCDs: see mt_gemm_tn_f16
+static int gemm_tn_split(int M, int tiles) {
+  const int split = max(1, min(cdiv(M, 256), cdiv(tiles >= 16 ? 1024 : 512, tiles)));
+  return cdiv(split, 8) * 8;
+}
+
 extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb,
                               const MtRowMap* bmap, int M, int N1, int N2, float* C, long ldc, float* colsum,
                               mt_stream_t stream) {
@@ -963,22 +1005,75 @@ extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   // share an XCD (tools/experiments/tn_sweep.sh: 63 / 39 / 39 / 19 us for 384x768 / 192x768 / 768x192 / 192x192; the larger
   // tiles the kernel template allows re-read less but need more splits -- more atomics -- for the same number of workgroups)
   const int tiles = (N1 / 64) * (N2 / 64);
-  int split = max(1, min(cdiv(M, 256), cdiv(tiles >= 16 ? 1024 : 512, tiles)));
-  split = cdiv(split, 8) * 8;                                   // a multiple of the 8 XCDs
+  const int split = gemm_tn_split(M, tiles);
   g.rows_per_split = cdiv(cdiv(M, split), 32) * 32;
   hipLaunchKernelGGL((gemm_tn_kernel<64, 64>), dim3(tiles * split), dim3(256), 0, (hipStream_t)stream, g);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
 
+// ---- deterministic twins (det_reduce.hip).  As many splits are launched as the default form launches (same tiles, same XCD rule);
+// slots = min(32-row steps, launched splits): the splits that hold rows (gemm_tn_kernel, DET).
+// partials = [slots][N1][N2], then (with_colsum) [slots][N1].
+static int gemm_tn_det_slots(int M, int N1, int N2, int* split_out) {
+  const int split = gemm_tn_split(M, (N1 / 64) * (N2 / 64));
+  if (split_out) *split_out = split;
+  return min(cdiv(M, 32), split);
+}
+
+extern "C" long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum) {
+  if (M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64) return MT_ERR_BAD_ARG;
+  return (long)gemm_tn_det_slots(M, N1, N2, nullptr) * N1 * ((long)N2 + (with_colsum ? 1 : 0));
+}
+
+extern "C" int mt_gemm_tn_f16_det(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb,
+                                  const MtRowMap* bmap, int M, int N1, int N2, float* C, long ldc, float* colsum, float* partials,
+                                  long partials_elems, mt_stream_t stream) {
+  if (!A || !B || !C || M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64 || lda % 8 || ldb % 8 || ldc < N2 || !partials ||
+      partials_elems < mt_gemm_tn_f16_det_elems(M, N1, N2, colsum != nullptr))
+    return MT_ERR_BAD_ARG;
+  int split;
+  GemmTnArgs g;
+  g.A = (const h16*)A; g.lda = lda; g.amap = make_rowmap(amap);
+  g.B = (const h16*)B; g.ldb = ldb; g.bmap = make_rowmap(bmap);
+  g.M = M; g.N1 = N1; g.N2 = N2; g.rows_per_split = 0;
+  const int slots = gemm_tn_det_slots(M, N1, N2, &split);
+  float* pcs = partials + (long)slots * N1 * N2;
+  g.C = partials; g.ldc = N2; g.colsum = colsum ? pcs : nullptr;
+  const int tiles = (N1 / 64) * (N2 / 64);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL((gemm_tn_kernel<64, 64, true>), dim3(tiles * split), dim3(256), 0, s, g);
+  MT_CHECK_LAUNCH();
+  int rc = mt_det_reduce_launch(partials, slots, N1, N2, (long)N1 * N2, C, ldc, s);
+  if (rc == MT_OK && colsum) rc = mt_det_reduce_launch(pcs, slots, 1, N1, N1, colsum, N1, s);
+  return rc;
+}
+
 extern "C" int mt_colsum_f16(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out,
                              mt_stream_t stream) {
   if (!A || !out || M <= 0 || N <= 0 || (N & 7) || (lda & 7)) return MT_ERR_BAD_ARG;
   const int rows_per_block = 256;
-  hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 256), cdiv(M, rows_per_block)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(colsum_kernel<false>, dim3(cdiv(N, 256), cdiv(M, rows_per_block)), dim3(256), 0, (hipStream_t)stream,
                      (const h16*)A, lda, make_rowmap(amap), M, N, rows_per_block, out);
   MT_CHECK_LAUNCH();
   return MT_OK;
+}
+
+// deterministic twin: partials = [cdiv(M, 256)][N], one row per blockIdx.y
+extern "C" long mt_colsum_f16_det_elems(int M, int N) {
+  if (M <= 0 || N <= 0 || (N & 7)) return MT_ERR_BAD_ARG;
+  return (long)cdiv(M, 256) * N;
+}
+
+extern "C" int mt_colsum_f16_det(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, float* partials,
+                                 long partials_elems, mt_stream_t stream) {
+  if (!A || !out || M <= 0 || N <= 0 || (N & 7) || (lda & 7) || !partials || partials_elems < mt_colsum_f16_det_elems(M, N))
+    return MT_ERR_BAD_ARG;
+  const int rows_per_block = 256, slots = cdiv(M, rows_per_block);
+  hipLaunchKernelGGL(colsum_kernel<true>, dim3(cdiv(N, 256), slots), dim3(256), 0, (hipStream_t)stream, (const h16*)A, lda,
+                     make_rowmap(amap), M, N, rows_per_block, partials);
+  MT_CHECK_LAUNCH();
+  return mt_det_reduce_launch(partials, slots, 1, N, N, out, N, (hipStream_t)stream);
 }
 
 static int sgemm_fill(const MtSgemm& q, SgemmArgs& g) {

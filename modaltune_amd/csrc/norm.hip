@@ -141,7 +141,9 @@ struct LnBwdArgs {
   float* dw; float* db; h16* dx16; DropArgs drop16; int M;
 };
 
-template <int D, typename DyT, typename InT, typename DxT, bool GELU, bool PARAM>
+// DET (deterministic mode, det_reduce.hip): a.dw is the partial workspace [gridDim.x][2][D]; workgroup blockIdx.x stores its dw | db
+// sums to slot blockIdx.x with plain stores
+template <int D, typename DyT, typename InT, typename DxT, bool GELU, bool PARAM, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   constexpr int NC = D / 256;
   constexpr int NP = PARAM ? NC : 1;
@@ -210,8 +212,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
       }
     __syncthreads();
     for (int i = threadIdx.x; i < D; i += 256) {
-      atomicAdd(&a.dw[i], red[0][0][i] + red[0][1][i] + red[0][2][i] + red[0][3][i]);
-      atomicAdd(&a.db[i], red[1][0][i] + red[1][1][i] + red[1][2][i] + red[1][3][i]);
+      if constexpr (DET) {
+        float* slot = a.dw + (long)blockIdx.x * (2 * D);
+        slot[i] = red[0][0][i] + red[0][1][i] + red[0][2][i] + red[0][3][i];
+        slot[D + i] = red[1][0][i] + red[1][1][i] + red[1][2][i] + red[1][3][i];
+      } else {
+        atomicAdd(&a.dw[i], red[0][0][i] + red[0][1][i] + red[0][2][i] + red[0][3][i]);
+        atomicAdd(&a.db[i], red[1][0][i] + red[1][1][i] + red[1][2][i] + red[1][3][i]);
+      }
     }
   }
 }
@@ -405,9 +413,19 @@ int ln_fwd_types(const LnFwdArgs& a, int in_dt, int out_dt, int gelu, hipStream_
   return MT_ERR_UNSUPPORTED;
 }
 
+int ln_param_grid(int M) { return min(ln_grid(M), 512); }      // workgroups (= partial slots) of the PARAM form
+
 template <int D, typename DyT, typename InT, typename DxT, bool GELU>
-int ln_bwd_launch(const LnBwdArgs& a, hipStream_t s) {
+int ln_bwd_launch(const LnBwdArgs& a, hipStream_t s, bool det = false) {
   if (a.dw) {
+    if constexpr ((!GELU && sizeof(DyT) == 4) || (D <= 768 && !GELU)) {
+      if (det) {
+        hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, true, true>), dim3(ln_param_grid(a.M)), dim3(256), 0, s, a);
+        MT_CHECK_LAUNCH();
+        return MT_OK;
+      }
+    }
+    if (det) return MT_ERR_UNSUPPORTED;
     if constexpr (!GELU && sizeof(DyT) == 4) {            // trainable norms: token side (fp32) ...
       hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, true>), dim3(min(ln_grid(a.M), 512)), dim3(256), 0, s, a);
     } else if constexpr (D <= 768 && !GELU) {           // ... and the adapters' 768-wide norms over the patch rows
@@ -520,7 +538,8 @@ struct InjBwdArgs {
   float* dx; long lddx; RowMap dxmap; int dx_accumulate;
   h16* dproj; float* dgamma; int M;
 };
-template <int D>
+// DET (deterministic mode): a.dgamma is the partial workspace [gridDim.x][D], slot = blockIdx.x, plain stores
+template <int D, bool DET = false>
 __global__ __launch_bounds__(256) void inject_resid_bwd_kernel(InjBwdArgs a) {
   constexpr int NC = D / 256;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -556,7 +575,10 @@ __global__ __launch_bounds__(256) void inject_resid_bwd_kernel(InjBwdArgs a) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) red[wave][c * 256 + lane * 4 + e] = gg[c][e];
   __syncthreads();
-  for (int i = threadIdx.x; i < D; i += 256) atomicAdd(&a.dgamma[i], red[0][i] + red[1][i] + red[2][i] + red[3][i]);
+  for (int i = threadIdx.x; i < D; i += 256) {
+    if constexpr (DET) a.dgamma[(long)blockIdx.x * D + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
+    else atomicAdd(&a.dgamma[i], red[0][i] + red[1][i] + red[2][i] + red[3][i]);
+  }
 }
 
 // fp32 [R, C] -> fp16 [R, C] (transpose = 0) or fp16 [C, R] (transpose = 1), 32x32 tiles through LDS
@@ -660,7 +682,7 @@ extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const
 }
 
 template <int D>
-static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int gelu, hipStream_t s) {
+static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int gelu, hipStream_t s, bool det = false) {
   const bool dyh = dy_dt == MT_OUT_F16, inh = in_dt == MT_OUT_F16, dxh = dx_dt == MT_OUT_F16;
   if (gelu) {
     if constexpr (D % 1024 == 0) {
@@ -671,12 +693,12 @@ static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int
         return MT_OK;
       }
     }
-    if (dyh && inh && dxh) return ln_bwd_launch<D, h16, h16, h16, true>(a, s);
+    if (dyh && inh && dxh) return ln_bwd_launch<D, h16, h16, h16, true>(a, s, det);
     return MT_ERR_UNSUPPORTED;
   }
-  if (dyh && !inh && !dxh) return ln_bwd_launch<D, h16, float, float, false>(a, s);
-  if (dyh && !inh && dxh) return ln_bwd_launch<D, h16, float, h16, false>(a, s);
-  if (!dyh && !inh && !dxh) return ln_bwd_launch<D, float, float, float, false>(a, s);
+  if (dyh && !inh && !dxh) return ln_bwd_launch<D, h16, float, float, false>(a, s, det);
+  if (dyh && !inh && dxh) return ln_bwd_launch<D, h16, float, h16, false>(a, s, det);
+  if (!dyh && !inh && !dxh) return ln_bwd_launch<D, float, float, float, false>(a, s, det);
   return MT_ERR_UNSUPPORTED;
 }
 
@@ -697,6 +719,40 @@ extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap
     case 3072: return ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
     default: return MT_ERR_UNSUPPORTED;
   }
+}
+
+// ---- deterministic twins (det_reduce.hip): partials = [slots][2][D] for dw | db, slots = workgroups of the PARAM form
+extern "C" long mt_layernorm_bwd_det_elems(int M, int D) {
+  if (M <= 0 || (D != 256 && D != 768 && D != 2304 && D != 3072)) return MT_ERR_BAD_ARG;
+  return (long)ln_param_grid(M) * 2 * D;
+}
+
+extern "C" int mt_layernorm_bwd_det(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
+                                    const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
+                                    long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
+                                    mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, float* partials, long partials_elems,
+                                    mt_stream_t stream) {
+  if (!dy || !x || !w || !stats || !dx || M <= 0 || !dw || !db || !partials) return MT_ERR_BAD_ARG;
+  if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
+  const long need = mt_layernorm_bwd_det_elems(M, D);
+  if (need < 0) return MT_ERR_UNSUPPORTED;
+  if (partials_elems < need) return MT_ERR_BAD_ARG;
+  LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate, partials,
+              partials + D, (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M};
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  switch (D) {
+    case 256: rc = ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
+    case 768: rc = ln_bwd_types<768>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
+    case 2304: rc = ln_bwd_types<2304>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
+    case 3072: rc = ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
+    default: return MT_ERR_UNSUPPORTED;
+  }
+  if (rc != MT_OK) return rc;
+  const int slots = ln_param_grid(M);
+  rc = mt_det_reduce_launch(partials, slots, 1, D, 2L * D, dw, D, s);
+  if (rc != MT_OK) return rc;
+  return mt_det_reduce_launch(partials + D, slots, 1, D, 2L * D, db, D, s);
 }
 
 extern "C" int mt_cast_f32_to_f16(const float* x, mt_half* y, long n, const MtDropout* drop, int D, mt_stream_t stream) {
@@ -799,4 +855,25 @@ extern "C" int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* d
   hipLaunchKernelGGL(inject_resid_bwd_kernel<768>, dim3(min(cdiv(M, 4), 512)), dim3(256), 0, (hipStream_t)stream, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
+}
+
+// deterministic twin: partials = [slots][D], slots = workgroups
+extern "C" long mt_inject_resid_bwd_det_elems(int M, int D) {
+  if (M <= 0 || D != 768) return MT_ERR_BAD_ARG;
+  return (long)min(cdiv(M, 4), 512) * D;
+}
+
+extern "C" int mt_inject_resid_bwd_det(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
+                                       const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
+                                       const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,
+                                       float* partials, long partials_elems, mt_stream_t stream) {
+  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 || !partials ||
+      partials_elems < mt_inject_resid_bwd_det_elems(M, D))
+    return MT_ERR_BAD_ARG;
+  InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
+               make_rowmap(dxmap), dx_accumulate, (h16*)dproj, partials, M};
+  const int slots = min(cdiv(M, 4), 512);
+  hipLaunchKernelGGL((inject_resid_bwd_kernel<768, true>), dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
+  MT_CHECK_LAUNCH();
+  return mt_det_reduce_launch(partials, slots, 1, D, D, dgamma, D, (hipStream_t)stream);
 }

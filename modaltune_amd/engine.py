@@ -149,8 +149,21 @@ class _W16:
                 ops.pack_weight(full, self.wt, self.N, self.K, transpose=True)
 
 
+def deterministic_default() -> bool:
+    """What `deterministic=None` means: MT_DETERMINISTIC=1 in the environment, or torch.use_deterministic_algorithms(True)."""
+    return os.environ.get("MT_DETERMINISTIC", "0") == "1" or torch.are_deterministic_algorithms_enabled()
+
+
 class Engine:
-    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device="cuda"):
+    DETERMINISTIC_REFUSAL = None      # (a subclass that cannot run the deterministic mode says why: TitanEngine)
+
+    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device="cuda", deterministic: Optional[bool] = None):
+        """deterministic (None: deterministic_default()): the train step runs the `_det` launchers (include/modaltune_hip.h) wherever
+        the default ones sum a parameter gradient over workgroups with fp32 atomics -- the same seed, inputs and pass schedule then
+        give the same bits in every gradient, run after run, eager or replayed.  Fixed at construction."""
+        self.deterministic = deterministic_default() if deterministic is None else bool(deterministic)
+        if self.deterministic and self.DETERMINISTIC_REFUSAL:
+            raise NotImplementedError(self.DETERMINISTIC_REFUSAL)
         cfg.validate()
         self.cfg, self.device = cfg, torch.device(device)
         self.group_sizes = list(group_sizes)
@@ -203,6 +216,14 @@ class Engine:
         self._layer_path_p = [float(v) for v in dpr]          # ENC:37-41
         self.leaf_stream = os.environ.get("MT_LEAF_STREAM", "0") == "1"
         self._side, self._side_refs, self._side_busy = None, [], False
+        if self.deterministic and self.leaf_stream:
+            raise ValueError(self._LEAF_DET)
+
+    # (deterministic mode: ONE partial workspace per workspace store, used launch after launch on the store's stream; a leaf on the side
+    # stream would write it while the main stream's next launch does.  The side stream is an experiment that lost its A/B: it gets no
+    # second buffer, the combination raises.)
+    _LEAF_DET = "MT_LEAF_STREAM=1 / engine.leaf_stream and the deterministic mode exclude each other: the side stream's weight-gradient " \
+                "leaves would share the partial workspace of the main stream's launches"
 
     def _bump_generation(self):
         self.generation += 1
@@ -212,6 +233,8 @@ class Engine:
     # default (MT_LEAF_STREAM=1 / engine.leaf_stream = True): same-box A/B in hipGraph replay 41.73 / 41.99 ms without, 42.21 / 42.30 with
     #  -- the cross-stream edges of the replayed graph cost more than the overlap returns.
     def _leaf(self, fn, *keep):
+        if self.leaf_stream and self.deterministic:
+            raise ValueError(self._LEAF_DET)
         if not self.leaf_stream:
             fn()
             return
@@ -410,7 +433,21 @@ class Engine:
         sp["scratch32"] = (F32, (Mp, D))
         plan = ops.make_plan(branch_table(N, self.seg_lengths, DILATED_RATIOS), N, B)
         sp["attn_ws"] = (H16, (ops.dilated_attn_bwd_workspace_bytes(plan) // 2,))
+        if self.deterministic:
+            sp["det"] = (F32, (self._det_elems(B, Lx),))
         return sp
+
+    def _det_elems(self, B: int, Lx: int) -> int:
+        """Deterministic mode: floats of the partial workspace of one (B, Lx) geometry -- the largest need of the patch-side `_det`
+        launches of a step (they run one after the other on the geometry's stream and share it).  The store holds it like every other
+        buffer: sized for the largest bag seen, moved (generation bumped) when the store grows."""
+        cfg = self.cfg
+        D, E, T, Mp = cfg.embed_dim, cfg.adapter_dim, self.T, B * Lx
+        AHn, AHd = cfg.num_heads, cfg.adapter_head_dim
+        need = [ops.det_elems("gemm_tn_f16", Mp, n1, n2, 1) for n1, n2 in ((D, E), (E, E), (E, D), (2 * E, D))]
+        need += [ops.det_elems("layernorm_bwd", Mp, D), ops.det_elems("inject_resid_bwd", Mp, D),
+                 ops.det_elems("inject_attn_bwd_hd", Mp, Lx, T, AHn, AHd), ops.det_elems("extract_attn_bwd_hd", B, T, Lx, AHn, AHd)]
+        return max(need)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, coords, genes: Sequence[torch.Tensor], task_onehots: torch.Tensor,
@@ -451,6 +488,7 @@ class Engine:
         # its own tape, workspace geometry (B differs) and, through site_group, its own dropout masks)
         self.tape = tape if tape is not None else (Tape(self.device, shared=self._fresh_arenas) if fresh else self._main_tape)
         tape = self.tape
+        tape.deterministic = self.deterministic      # (the token side's trainable LayerNorms: the tape holds their partial workspace)
         if fresh:
             tape.lease = ws["_lease"]             # the backward closures read views of the leased store
             if share is not None:
@@ -859,6 +897,7 @@ class Engine:
                     resid=src, ldr=D, rmap=src_map, colscale=t[pref + "gamma"])
         g = self.store.grads
         ws = ctx["ws"]
+        det = ws.get("det")               # deterministic mode: the workspace's partial buffer (None: the atomic forms)
 
         def bwd():
             dh = ws["dh"]
@@ -867,29 +906,29 @@ class Engine:
             dproj = torch.empty(Mp, D, dtype=H16, device=dev)
             # residual path: dh_patch <- (1+gamma) dh_patch (in place; block 0's input x0 needs no gradient)
             ops.inject_resid_bwd(dh, src, proj, t[pref + "gamma"], dh if not first else ws["scratch32"], dproj,
-                                 g[pref + "gamma"], Mp, D, dymap=pm, xmap=src_map, dxmap=pm if not first else None)
-            self._leaf(lambda: ops.gemm_tn(dproj, o1, g[ap + "output_proj.weight"], Mp, D, E, colsum=g[ap + "output_proj.bias"]), dproj, o1)
+                                 g[pref + "gamma"], Mp, D, dymap=pm, xmap=src_map, dxmap=pm if not first else None, det=det)
+            self._leaf(lambda: ops.gemm_tn(dproj, o1, g[ap + "output_proj.weight"], Mp, D, E, colsum=g[ap + "output_proj.bias"], det=det), dproj, o1)
             do1 = torch.empty(Mp, E, dtype=H16, device=dev)
             ops.gemm_nt(dproj, w16[ap + "output_proj"].wt, do1, Mp, E, D)
-            self._leaf(lambda: ops.gemm_tn(do1, a, g[ap + "multihead_attn.out_proj.weight"], Mp, E, E, colsum=g[ap + "multihead_attn.out_proj.bias"]),
+            self._leaf(lambda: ops.gemm_tn(do1, a, g[ap + "multihead_attn.out_proj.weight"], Mp, E, E, colsum=g[ap + "multihead_attn.out_proj.bias"], det=det),
                        do1, a)
             da = torch.empty(Mp, E, dtype=H16, device=dev)
             ops.gemm_nt(do1, w16[ap + "out_in"].wt, da, Mp, E, E)
             dq2 = torch.empty(Mp, E, dtype=H16, device=dev)
-            ops.inject_attn_bwd(q2, a, alse, da, k.data, v.data, dq2, k.g(), v.g(), Mp, L, T, heads=AHn, head_dim=AHd)
-            self._leaf(lambda: ops.gemm_tn(dq2, q1, g[ap + "multihead_attn.q_proj_weight"], Mp, E, E, colsum=g[ap + "multihead_attn.in_proj_bias"][:E]),
+            ops.inject_attn_bwd(q2, a, alse, da, k.data, v.data, dq2, k.g(), v.g(), Mp, L, T, heads=AHn, head_dim=AHd, det=det)
+            self._leaf(lambda: ops.gemm_tn(dq2, q1, g[ap + "multihead_attn.q_proj_weight"], Mp, E, E, colsum=g[ap + "multihead_attn.in_proj_bias"][:E], det=det),
                        dq2, q1)
             dq1 = torch.empty(Mp, E, dtype=H16, device=dev)
             ops.gemm_nt(dq2, w16[ap + "q_in"].wt, dq1, Mp, E, E)
-            self._leaf(lambda: ops.gemm_tn(dq1, xhat, g[ap + "q_proj.weight"], Mp, E, D, colsum=g[ap + "q_proj.bias"]), dq1, xhat)
+            self._leaf(lambda: ops.gemm_tn(dq1, xhat, g[ap + "q_proj.weight"], Mp, E, D, colsum=g[ap + "q_proj.bias"], det=det), dq1, xhat)
             dxhat = torch.empty(Mp, D, dtype=H16, device=dev)
             ops.gemm_nt(dq1, w16[ap + "q_proj"].wt, dxhat, Mp, D, E)
             if first:
                 ops.layernorm_bwd(dxhat, src, t[ap + "norm.weight"], st, ws["scratch32"], Mp, D, xmap=src_map,
-                                  dw=g[ap + "norm.weight"], db=g[ap + "norm.bias"])
+                                  dw=g[ap + "norm.weight"], db=g[ap + "norm.bias"], det=det)
             else:
                 ops.layernorm_bwd(dxhat, src, t[ap + "norm.weight"], st, dh, Mp, D, xmap=src_map, dxmap=pm, accumulate=True,
-                                  dw=g[ap + "norm.weight"], db=g[ap + "norm.bias"])
+                                  dw=g[ap + "norm.weight"], db=g[ap + "norm.bias"], det=det)
         tape.record(bwd)
 
     # ------------------------------------------------------------------ one frozen LongNet layer (A.4)
@@ -954,17 +993,19 @@ class Engine:
         if wmap is not None:
             ops.extract_attn_probs(q2.data, kv, lse, wmap, B, T, L, heads=AHn, head_dim=AHd)
 
+        det = ws.get("det")               # (deterministic mode, as in the injector)
+
         def bwd_core():
             if out.grad is None:
                 return
             dkv = torch.empty(Mp, 2 * E, dtype=H16, device=dev)
-            ops.extract_attn_bwd(q2.data, kv, out.data, lse, out.grad, q2.g(), dkv, B, T, L, heads=AHn, head_dim=AHd)
+            ops.extract_attn_bwd(q2.data, kv, out.data, lse, out.grad, q2.g(), dkv, B, T, L, heads=AHn, head_dim=AHd, det=det)
             self._leaf(lambda: ops.gemm_tn(dkv, xk, g[ap + "multihead_attn.k_proj_weight"], Mp, 2 * E, D,       # k | v weights are adjacent
-                                           colsum=g[ap + "multihead_attn.in_proj_bias"][E:]), dkv, xk)
+                                           colsum=g[ap + "multihead_attn.in_proj_bias"][E:], det=det), dkv, xk)
             dxk = torch.empty(Mp, D, dtype=H16, device=dev)
             ops.gemm_nt(dkv, w16[ap + "kv"].wt, dxk, Mp, D, 2 * E)
             ops.layernorm_bwd(dxk, hout, t[ap + "norm_kq.weight"], st, ws["dh"], Mp, D, xmap=pm, dxmap=pm, accumulate=True,
-                              dw=g[ap + "norm_kq.weight"], db=g[ap + "norm_kq.bias"])
+                              dw=g[ap + "norm_kq.weight"], db=g[ap + "norm_kq.bias"], det=det)
         tape.record(bwd_core)
         o = tape.linear(out, P(ap + "multihead_attn.out_proj.weight"), P(ap + "multihead_attn.out_proj.bias"))
         # c1 = query + (tgt + output_proj(.)) with tgt == query (AM:231,324): 2 c + output_proj(.) on the product's epilogue

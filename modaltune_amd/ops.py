@@ -94,13 +94,38 @@ def gemm_nt(A, W, out, M, N, K, *, lda=None, amap=None, ldc=None, cmap=None, epi
           "gemm_nt")
 
 
-def gemm_tn(A, B, out, M, N1, N2, *, lda=None, amap=None, ldb=None, bmap=None, ldc=None, colsum=None):
+# Deterministic twins (include/modaltune_hip.h): the six wrappers below that reduce a parameter gradient over workgroups take
+# det=None | a contiguous fp32 cuda tensor, the caller's partial workspace (sized by det_elems); given one, the `_det` launcher runs:
+# no atomics, bit-reproducible sums.
+def det_elems(name: str, *shape) -> int:
+    """Floats of partial workspace the deterministic twin of `name` ("gemm_tn_f16", "colsum_f16", "layernorm_bwd", "inject_resid_bwd",
+    "inject_attn_bwd_hd", "extract_attn_bwd_hd") needs for these shape arguments (include/modaltune_hip.h: mt_<name>_det_elems)."""
+    n = getattr(_lib.load(), f"mt_{name}_det_elems")(*shape)
+    if n < 0:
+        check(int(n), f"{name}_det_elems{shape}")
+    return int(n)
+
+
+def _det(det):
+    _need(det, torch.float32, "det")
+    return det.data_ptr(), det.numel()
+
+
+def gemm_tn(A, B, out, M, N1, N2, *, lda=None, amap=None, ldb=None, bmap=None, ldc=None, colsum=None, det=None):
     """out[N1,N2] += A^T B over M rows (weight gradient); colsum[N1] += column sums of A (the bias gradient) on the same pass."""
+    if det is not None:
+        check(_lib.load().mt_gemm_tn_f16_det(_p(A), lda if lda is not None else N1, _rm(amap), _p(B), ldb if ldb is not None else N2,
+                                             _rm(bmap), M, N1, N2, _p(out), ldc if ldc is not None else N2, _p(colsum), *_det(det), _s()),
+              "gemm_tn_det")
+        return
     check(_lib.load().mt_gemm_tn_f16(_p(A), lda if lda is not None else N1, _rm(amap), _p(B), ldb if ldb is not None else N2,
                                      _rm(bmap), M, N1, N2, _p(out), ldc if ldc is not None else N2, _p(colsum), _s()), "gemm_tn")
 
 
-def colsum(A, out, M, N, *, lda=None, amap=None):
+def colsum(A, out, M, N, *, lda=None, amap=None, det=None):
+    if det is not None:
+        check(_lib.load().mt_colsum_f16_det(_p(A), lda if lda is not None else N, _rm(amap), M, N, _p(out), *_det(det), _s()), "colsum_det")
+        return
     check(_lib.load().mt_colsum_f16(_p(A), lda if lda is not None else N, _rm(amap), M, N, _p(out), _s()), "colsum")
 
 
@@ -152,7 +177,13 @@ def add_layernorm_fwd(x, branch, w, b, h, y, stats, M, D, drop=None, eps=1e-5):
 
 
 def layernorm_bwd(dy, x, w, stats, dx, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None, dxmap=None,
-                  gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None):
+                  gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None, det=None):
+    if det is not None and dw is not None:      # (a frozen norm reduces nothing over workgroups: the default launcher is deterministic)
+        check(_lib.load().mt_layernorm_bwd_det(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x),
+                                               ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats),
+                                               _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate),
+                                               _p(dw), _p(db), _p(dx16), _dr(dx16_drop), M, D, *_det(det), _s()), "layernorm_bwd_det")
+        return
     check(_lib.load().mt_layernorm_bwd(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x),
                                        ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats),
                                        _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate),
@@ -374,7 +405,11 @@ def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None, heads=12, head_di
           "inject_attn_fwd")
 
 
-def inject_attn_bwd(q, a, lse, da, k, v, dq, dk, dv, M, rows_per_pass, T, heads=12, head_dim=16):
+def inject_attn_bwd(q, a, lse, da, k, v, dq, dk, dv, M, rows_per_pass, T, heads=12, head_dim=16, det=None):
+    if det is not None:
+        check(_lib.load().mt_inject_attn_bwd_hd_det(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim,
+                                                    _p(dq), _p(dk), _p(dv), *_det(det), _s()), "inject_attn_bwd_det")
+        return
     check(_lib.load().mt_inject_attn_bwd_hd(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(dq),
                                             _p(dk), _p(dv), _s()), "inject_attn_bwd")
 
@@ -385,7 +420,11 @@ def extract_attn_fwd(q, kv, out, lse, part_acc, part_ml, B, T, L, nsplit, heads=
                                              nsplit, _s()), "extract_attn_fwd")
 
 
-def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L, heads=12, head_dim=16):
+def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L, heads=12, head_dim=16, det=None):
+    if det is not None:
+        check(_lib.load().mt_extract_attn_bwd_hd_det(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, heads, head_dim, _p(dq),
+                                                     _p(dkv), *_det(det), _s()), "extract_attn_bwd_det")
+        return
     check(_lib.load().mt_extract_attn_bwd_hd(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, heads, head_dim, _p(dq), _p(dkv),
                                              _s()), "extract_attn_bwd")
 
@@ -470,7 +509,13 @@ def copy_rows(src, dst, M, D, *, lds=None, smap=None, ldd=None, dmap=None, accum
 
 
 def inject_resid_bwd(dy, x, proj, gamma, dx, dproj, dgamma, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None,
-                     dxmap=None, dx_accumulate=False):
+                     dxmap=None, dx_accumulate=False, det=None):
+    if det is not None:
+        check(_lib.load().mt_inject_resid_bwd_det(_p(dy), lddy if lddy is not None else D, _rm(dymap), _p(x),
+                                                  ldx if ldx is not None else D, _rm(xmap), _p(proj), _p(gamma), _p(dx),
+                                                  lddx if lddx is not None else D, _rm(dxmap), int(dx_accumulate), _p(dproj),
+                                                  _p(dgamma), M, D, *_det(det), _s()), "inject_resid_bwd_det")
+        return
     check(_lib.load().mt_inject_resid_bwd(_p(dy), lddy if lddy is not None else D, _rm(dymap), _p(x),
                                           ldx if ldx is not None else D, _rm(xmap), _p(proj), _p(gamma), _p(dx),
                                           lddx if lddx is not None else D, _rm(dxmap), int(dx_accumulate), _p(dproj),
@@ -586,7 +631,8 @@ def _timed(name_fn):
 
 
 gemm_nt = _timed(lambda A, W, out, M, N, K, **k: f"gemm_nt[{M}x{N}x{K}]")(gemm_nt)
-gemm_tn = _timed(lambda A, B, out, M, N1, N2, **k: f"gemm_tn[{N1}x{N2}]")(gemm_tn)
+_d = lambda k: "_det" if k.get("det") is not None else ""      # the deterministic launches (kernel + reduce) get names of their own
+gemm_tn = _timed(lambda A, B, out, M, N1, N2, **k: f"gemm_tn{_d(k)}[{N1}x{N2}]")(gemm_tn)
 dilated_attn_fwd = _timed(lambda *a, **k: "dilated_attn_fwd")(dilated_attn_fwd)
 dense_attn_fwd = _timed(lambda *a, **k: "dense_attn_fwd")(dense_attn_fwd)
 gelu_f16_fwd = _timed(lambda *a, **k: "gelu_f16_fwd")(gelu_f16_fwd)
@@ -594,15 +640,16 @@ gelu_f16_bwd = _timed(lambda *a, **k: "gelu_f16_bwd")(gelu_f16_bwd)
 dilated_mix_ln_fwd = _timed(lambda *a, **k: "dilated_mix_ln_fwd")(dilated_mix_ln_fwd)
 dilated_mix_ln_bwd = _timed(lambda *a, **k: "dilated_mix_ln_bwd")(dilated_mix_ln_bwd)
 layernorm_fwd = _timed(lambda x, w, b, y, stats, M, D, **k: f"layernorm_fwd[{D}]" if M > 1024 else "token_side")(layernorm_fwd)
-layernorm_bwd = _timed(lambda dy, x, w, stats, dx, M, D, **k: f"layernorm_bwd[{D}]" if M > 1024 else "token_side")(layernorm_bwd)
+layernorm_bwd = _timed(lambda dy, x, w, stats, dx, M, D, **k: (f"layernorm_bwd{_d(k) if k.get('dw') is not None else ''}[{D}]" if M > 1024
+                                                                else "token_side"))(layernorm_bwd)
 add_layernorm_fwd = _timed(lambda x, branch, w, b, h, y, stats, M, D, **k: f"add_layernorm_fwd[{D}]")(add_layernorm_fwd)
 cast_f32_to_f16 = _timed(lambda *a, **k: "cast")(cast_f32_to_f16)
 inject_attn_fwd = _timed(lambda *a, **k: "inject_attn_fwd")(inject_attn_fwd)
-inject_attn_bwd = _timed(lambda *a, **k: "inject_attn_bwd")(inject_attn_bwd)
+inject_attn_bwd = _timed(lambda *a, **k: "inject_attn_bwd" + _d(k))(inject_attn_bwd)
 extract_attn_fwd = _timed(lambda *a, **k: "extract_attn_fwd")(extract_attn_fwd)
-extract_attn_bwd = _timed(lambda *a, **k: "extract_attn_bwd")(extract_attn_bwd)
-inject_resid_bwd = _timed(lambda *a, **k: "inject_resid_bwd")(inject_resid_bwd)
-colsum = _timed(lambda *a, **k: "colsum")(colsum)
+extract_attn_bwd = _timed(lambda *a, **k: "extract_attn_bwd" + _d(k))(extract_attn_bwd)
+inject_resid_bwd = _timed(lambda *a, **k: "inject_resid_bwd" + _d(k))(inject_resid_bwd)
+colsum = _timed(lambda *a, **k: "colsum" + _d(k))(colsum)
 _DETAIL = bool(os.environ.get("MT_TIMER_DETAIL"))
 sgemm_multi = _timed(lambda problems: ("sgemm[" + "+".join(f"{q.M}x{q.N}x{q.K}b{q.batch}" for q in problems) + "]" if _DETAIL else "token_side"))(sgemm_multi)
 adamw_step = _timed(lambda *a, **k: "adamw")(adamw_step)

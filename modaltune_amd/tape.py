@@ -85,6 +85,10 @@ class Tape:
         else:
             self._ones = torch.ones(4096, device=device)
         self.grad_enabled = True
+        # (Engine, deterministic mode: the trainable LayerNorms sum dw / db through a partial workspace of the tape's own -- its launches
+        # run one after the other on the tape's stream; grown to the largest need seen, and like the arena it moves only in an eager step)
+        self.deterministic = False
+        self._det: Optional[torch.Tensor] = None
         self.lease = None         # (Engine: keeps a recycled per-call workspace alive as long as this tape's closures may read it)
         # Zero-initialised gradient storage: one flat buffer cleared with ONE fill per step instead of a fill launch per
         # gradient (~150 per step).  It is sized from the demand of the previous step (the first step falls back to
@@ -93,6 +97,17 @@ class Tape:
         self._arena_used = 0
         self._arena_miss = 0
         self.on_realloc: Optional[Callable[[], None]] = None     # owner hook: captured graphs point into the arena
+
+    def det_partials(self, op: str, *shape) -> Optional[torch.Tensor]:
+        """The partial workspace for the deterministic twin of `op` at `shape` (None outside the deterministic mode)."""
+        if not self.deterministic:
+            return None
+        need = ops.det_elems(op, *shape)
+        if self._det is None or self._det.numel() < need:
+            self._det = torch.empty(need + need // 4, device=self.device, dtype=torch.float32)
+            if self.on_realloc is not None:
+                self.on_realloc()
+        return self._det
 
     def reset(self):
         global _ACTIVE
@@ -295,7 +310,8 @@ class Tape:
             train = w.grad is not None
             dx = x.g() if x.needs_grad else self.new(*x.data.shape)
             ops.layernorm_bwd(y.grad, x.data, w.data, stats, dx, R, D, accumulate=x.needs_grad,
-                              dw=w.grad if train else None, db=b.grad if train else None)
+                              dw=w.grad if train else None, db=b.grad if train else None,
+                              det=self.det_partials("layernorm_bwd", R, D) if train else None)
         self.record(bwd)
         return y
 

@@ -38,7 +38,7 @@ import torch.nn as nn
 from . import init, ops
 from .aggregators import Aggregator, LongNetGeneAdapter, _bridge_backward
 from .config import ModelConfig
-from .engine import Engine, F32, H16, _W16
+from .engine import Engine, F32, H16, _W16, deterministic_default
 from .tape import Param, Var
 
 I32 = torch.int32
@@ -666,8 +666,13 @@ class TitanEngine(Engine):
     """Engine with the frozen image side on a TITAN backbone (NativeBackbone or TorchBackbone); adapters / tokens / head as in
     Engine."""
 
-    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], backbone, device="cuda"):
-        super().__init__(cfg, group_sizes, device)
+    # mt_scatter_rows_f32 builds the feature grid with atomics in the FORWARD: Engine.__init__ refuses the mode
+    DETERMINISTIC_REFUSAL = ("deterministic=True (or MT_DETERMINISTIC=1 / torch.use_deterministic_algorithms(True)): the TITAN configurations "
+                             "accumulate the feature grid with fp32 atomics in the forward (scatter_rows_kernel, csrc/optim.hip) and no ordered "
+                             "form of it exists yet -- the deterministic mode covers the LongNet configurations only")
+
+    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], backbone, device="cuda", deterministic: Optional[bool] = None):
+        super().__init__(cfg, group_sizes, device, deterministic=deterministic)
         self.backbone = backbone
         self._tok = None
         self._titan_err = torch.zeros(1, dtype=I32, device=self.device)
@@ -896,8 +901,11 @@ class TITANGeneAdapter(LongNetGeneAdapter):
     CLINICAL = False
 
     def __init__(self, gene_group_defination: Dict[Any, Sequence[str]] = None, multi_task: int = 1, backbone: Optional[nn.Module] = None,
-                 device="cuda", backbone_impl: str = "native", init_seed: Optional[int] = None, **kwargs):
+                 device="cuda", backbone_impl: str = "native", init_seed: Optional[int] = None, deterministic: Optional[bool] = None,
+                 **kwargs):
         nn.Module.__init__(self)
+        if deterministic or (deterministic is None and deterministic_default()):      # refused before anything is built
+            raise NotImplementedError(TitanEngine.DETERMINISTIC_REFUSAL)
         gene_group_defination = gene_group_defination or {}
         self.backbone_source = "backbone= argument"
         if backbone is None:
@@ -921,7 +929,7 @@ class TITANGeneAdapter(LongNetGeneAdapter):
         object.__setattr__(self, "_backbone_module", backbone)
         object.__setattr__(self, "_backbone_impl_req", backbone_impl)
         sizes = [len(v) for v in gene_group_defination.values()]
-        self.engine = TitanEngine(cfg, sizes, None, device)
+        self.engine = TitanEngine(cfg, sizes, None, device, deterministic=deterministic)
         # trainable side initialised as the reference's constructor leaves it (TA:195-203: same families as the LongNet adapter)
         self.engine.load_state_dict(init.init_state_dict(cfg, sizes, init_seed, trainable_only=True), strict=False)
         self._rebuild_backbone()

@@ -9,6 +9,12 @@ carry no autograd formula: the reference-facing autograd boundary is the nn.Modu
 pairs each forward launcher with its backward launcher; what is registered here is the op-level surface a maintainer can call
 or compose directly.  There is no CPU implementation (the product path has no fallback).
 
+Determinism: every op registered here is bit-reproducible as it stands, so torch.use_deterministic_algorithms(True) needs no switch
+in this file -- none of them forwards to a launcher that sums over workgroups with atomics (`layernorm_bwd` is the frozen form: no dw /
+db).  The six launchers that do (ops.gemm_tn, colsum, layernorm_bwd with dw / db, inject_resid_bwd, inject_attn_bwd, extract_attn_bwd)
+have `_det` twins (ops: det=); an op added here on top of one of them has to pass a partial workspace under torch's flag or raise
+(tests/test_deterministic_cpu.py holds this file to that).
+
     import modaltune_amd.torch_ops        # registers the namespace
     y = torch.ops.modaltune_hip.gemm_nt(a16, w16, bias, True)
 """

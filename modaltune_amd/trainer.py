@@ -108,7 +108,10 @@ class TrainStep:
         # geometry that is about to be CAPTURED (it keeps coming back) is decided by measurement: both schedules run eagerly a few times
         # with update=False semantics (nothing but the dropout counter moves, and that is restored) and the faster one is captured.
         # Geometries that never repeat keep the threshold.  split_passes="auto" (the default) / True (threshold only) / False.
-        self.auto_split = split_passes == "auto" and pass_groups.split_mode() == "auto"
+        # A deterministic engine (Engine(deterministic=True)) runs no trial: a schedule chosen by a stopwatch is not reproducible, and the
+        # batched pass and the groups sum their gradients in different orders -- "auto" then means the threshold rule.
+        self.deterministic = bool(getattr(engine, "deterministic", False))
+        self.auto_split = split_passes == "auto" and pass_groups.split_mode() == "auto" and not self.deterministic
         self.split_decisions: Dict[int, bool] = {}
         self.split_trials: Dict[int, dict] = {}
         # Data-parallel schedule of a long bag (world > 1).  "groups_joined": the two pass groups with PER-BUCKET joins -- their backwards
