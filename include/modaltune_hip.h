@@ -216,6 +216,13 @@ int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDila
 int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
                           const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
                           float* delta_br, mt_stream_t stream);
+/* The two launchers above with the number of workgroups given (tests and tools only; the results do not depend on it):
+ * grid_wgs > 0 = that many workgroups (capped at what the rows need), 0 = the default. */
+int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
+                               const float* ln_b, mt_half* y, float* stats, float* lse_tot, int grid_wgs, mt_stream_t stream);
+int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                               const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                               float* delta_br, int grid_wgs, mt_stream_t stream);
 
 /* Flash-style backward of all branches: dqkv fp16 [B*N, 2304] (overwritten) from qkv, dmixed, lse_tot, delta_br.  The q
  * columns of dqkv are the gradient with respect to the PRE-SCALED q' (what the dX GEMM through the scaled q_proj cache needs).
@@ -227,6 +234,13 @@ long mt_dilated_attn_bwd_workspace_bytes(const MtDilatedPlan* plan);
 enum { MT_ATTN_BWD_KV = 1, MT_ATTN_BWD_Q = 2, MT_ATTN_BWD_COMBINE = 4, MT_ATTN_BWD_ALL = 7 };   /* `phases` mask */
 int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
                         const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, mt_stream_t stream);
+/* The same backward with the dense (ratio 1) branch written IN PLACE: the two kernels store that branch straight into dqkv (its
+ * workspace slot and the dqkv row have the same address arithmetic; its workspace region is left untouched) and the combine
+ * adds the sparse branches only where they cover a (position, head), in the same order and precision as the form above, so
+ * equal inputs give equal dqkv.  KV and Q phases must both have run on dqkv before COMBINE, and COMBINE runs once.  The
+ * workspace keeps its size.  What mt_longnet_layer_bwd uses; a plan without a ratio-1 branch takes the workspace form. */
+int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
+                                const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, mt_stream_t stream);
 
 /* ------------------------------------------------- dense attention with 2-D ALiBi (TITAN blocks) ---- */
 /* The attention of the TITAN slide encoder's ViT blocks (titan_adapter.py:253-293 `get_alibi`, :359-361,394

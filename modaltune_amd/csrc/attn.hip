@@ -260,11 +260,15 @@ MT_DEVINL float half_sum(float v) {       // over the 32 lanes of a row
   return v;
 }
 
+// Both mix kernels: a wave walks the row pairs (blockIdx * 4 + wave) * 2 + k * gridDim * 8, and the grid (mix_grid) is a few
+// workgroups per CU, so the LayerNorm affine in w[] / bb[] is loaded once per wave for several pairs -- with one pair per wave (the
+// grid before) those loads were half of the forward's vector-memory requests.  The pair index is wave-uniform: scalar loop control.
+// The outputs do not depend on the grid (lane-to-column mapping, half_sum and the fmaf chains are per row).
 template <int NB>
 __global__ __launch_bounds__(256) void mix_ln_fwd_kernel(const h16* __restrict__ o_br, const float* __restrict__ lse_br, Plan p,
                                                          const float* __restrict__ ln_w, const float* __restrict__ ln_b,
                                                          h16* __restrict__ y, float* __restrict__ stats, float* __restrict__ lse_tot) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane >> 5, l5 = lane & 31;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = lane >> 5, l5 = lane & 31;
   const long M = (long)p.B * p.N;
   const int h = l5 >> 1, c0 = l5 * MIX_CPL;
   const MixGeom geo(p, h);
@@ -332,7 +336,7 @@ __global__ __launch_bounds__(256) void mix_ln_bwd_kernel(const h16* __restrict__
                                                          const float* __restrict__ lse_br, const float* __restrict__ lse_tot, Plan p,
                                                          const float* __restrict__ ln_w, const float* __restrict__ stats,
                                                          h16* __restrict__ dmixed, float* __restrict__ delta_br) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane >> 5, l5 = lane & 31;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), sub = lane >> 5, l5 = lane & 31;
   const long M = (long)p.B * p.N;
   const int h = l5 >> 1, c0 = l5 * MIX_CPL;
   const MixGeom geo(p, h);
@@ -414,13 +418,24 @@ extern "C" int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan
   return MT_OK;
 }
 
-extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
-                                     const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
-                                     mt_stream_t stream) {
+// Grid of the mix kernels: as many workgroups (four waves, a wave = two rows at a time) per CU as a CU holds at once, never more than
+// the rows need.  That is the kernel's waves per SIMD: 3 for the forward (168 VGPRs), 2 for the backward (219).  The backward at 3
+// per CU runs as one full round and a half-empty one and is no faster than one row pair per wave; at 2 or 4 per CU it is 11 %
+// faster inside the step, the forward at 3 per CU 7 % (rocprofv3, batched schedule, M = 30 003: DESIGN section 5).
+// grid_wgs > 0 overrides it (tests and the sweep only).  MIX_CUS is the MI355X's CU count (8 XCDs x 32), fixed like the other grid
+// caps of this file: on a part with fewer CUs the grid is only more rounds of workgroups per CU.
+constexpr int MIX_CUS = 256, MIX_FWD_WG_PER_CU = 3, MIX_BWD_WG_PER_CU = 2;
+static dim3 mix_grid(long M, int grid_wgs, int wg_per_cu) {
+  return dim3((int)min((M + 7) / 8, (long)(grid_wgs > 0 ? grid_wgs : wg_per_cu * MIX_CUS)));
+}
+
+extern "C" int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
+                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
+                                          int grid_wgs, mt_stream_t stream) {
   if (!o_br || !lse_br || !ln_w || !ln_b || !y || !stats || !lse_tot || !plan_ok(plan)) return MT_ERR_BAD_ARG;
   const Plan p = make_plan(plan, 128);
   const long M = (long)p.B * p.N;
-  const dim3 grid((int)min((M + 7) / 8, 8192L));
+  const dim3 grid = mix_grid(M, grid_wgs, MIX_FWD_WG_PER_CU);
   if (p.nbranch <= 5)
     hipLaunchKernelGGL(mix_ln_fwd_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, (const h16*)o_br, lse_br, p, ln_w, ln_b,
                        (h16*)y, stats, lse_tot);
@@ -431,13 +446,19 @@ extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, c
   return MT_OK;
 }
 
-extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                                     const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                                     float* delta_br, mt_stream_t stream) {
+extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
+                                     const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
+                                     mt_stream_t stream) {
+  return mt_dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, stream);
+}
+
+extern "C" int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                                          float* delta_br, int grid_wgs, mt_stream_t stream) {
   if (!dy || !o_br || !lse_br || !lse_tot || !ln_w || !stats || !dmixed || !delta_br || !plan_ok(plan)) return MT_ERR_BAD_ARG;
   const Plan p = make_plan(plan, 128);
   const long M = (long)p.B * p.N;
-  const dim3 grid((int)min((M + 7) / 8, 8192L));
+  const dim3 grid = mix_grid(M, grid_wgs, MIX_BWD_WG_PER_CU);
   if (p.nbranch <= 5)
     hipLaunchKernelGGL(mix_ln_bwd_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, (const h16*)dy, (const h16*)o_br, lse_br,
                        lse_tot, p, ln_w, stats, (h16*)dmixed, delta_br);
@@ -448,21 +469,47 @@ extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, con
   return MT_OK;
 }
 
+extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                                     const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                                     float* delta_br, mt_stream_t stream) {
+  return mt_dilated_mix_ln_bwd_grid(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, stream);
+}
+
 extern "C" long mt_dilated_attn_bwd_workspace_bytes(const MtDilatedPlan* plan) {
   if (!plan_ok(plan)) return MT_ERR_BAD_ARG;
   const Plan p = make_plan(plan, 128);
   return p.ws_off[p.nbranch] * (long)sizeof(h16);
 }
 
+namespace {
+int attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan,
+             void* workspace, mt_half* dqkv, int phases, bool inplace, mt_stream_t stream) {
+  if (!qkv || !dmixed || !lse_tot || !delta_br || !workspace || !dqkv || !plan_ok(plan) || !(phases & 7)) return MT_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  inplace = inplace && dense_branch_host(plan) >= 0;      // (a plan without a ratio-1 branch has nothing to write in place)
+  if (inplace && (long)plan->B * plan->N >= (1L << 31)) return MT_ERR_UNSUPPORTED;      // (the in-place combine's 32-bit row % N)
+  mt_half* dense_dst = inplace ? dqkv : nullptr;
+  // every (branch, position, head) slot of the workspace (in-place form: of dqkv, for the dense branch) is written exactly once
+  // by each of the two kernels
+  if (phases & MT_ATTN_BWD_KV) mt_attn::launch_bwd_kv(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, s);
+  if (phases & MT_ATTN_BWD_Q) mt_attn::launch_bwd_q(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, s);
+  if (phases & MT_ATTN_BWD_COMBINE) {
+    if (inplace) mt_attn::launch_bwd_combine_inplace(workspace, plan, dqkv, s);
+    else mt_attn::launch_bwd_combine(workspace, plan, dqkv, s);
+  }
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+}  // namespace
+
 extern "C" int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
                                    const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
                                    int phases, mt_stream_t stream) {
-  if (!qkv || !dmixed || !lse_tot || !delta_br || !workspace || !dqkv || !plan_ok(plan) || !(phases & 7)) return MT_ERR_BAD_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  // every (branch, position, head) slot of the workspace is written exactly once by each of the two kernels
-  if (phases & MT_ATTN_BWD_KV) mt_attn::launch_bwd_kv(qkv, dmixed, lse_tot, delta_br, plan, workspace, s);
-  if (phases & MT_ATTN_BWD_Q) mt_attn::launch_bwd_q(qkv, dmixed, lse_tot, delta_br, plan, workspace, s);
-  if (phases & MT_ATTN_BWD_COMBINE) mt_attn::launch_bwd_combine(workspace, plan, dqkv, s);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, false, stream);
+}
+
+extern "C" int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
+                                           const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
+                                           int phases, mt_stream_t stream) {
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, stream);
 }

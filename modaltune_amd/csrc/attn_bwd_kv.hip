@@ -19,7 +19,7 @@ namespace {
 // (launch bound: 3 waves per SIMD = 168 VGPRs; the prefetched fragments would otherwise push the kernel to 175 and a wave per SIMD less)
 __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* __restrict__ qkv, const h16* __restrict__ dmixed,
                                                                   const float* __restrict__ lse_tot, const float* __restrict__ delta_br,
-                                                                  Plan p, h16* __restrict__ ws) {
+                                                                  Plan p, h16* __restrict__ ws, DenseDst dd) {
   // Q and dO tiles in LDS-DMA images (attn_common.h: img_off: each read both by rows and transposed), double-buffered
   // together with the per-query constants; one barrier per tile
   __shared__ __attribute__((aligned(16))) h16 smem[4 * IMG_HALVES];      // Q0 | Q1 | D0 | D1
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* 
     __syncthreads();           // ... for everybody, and everybody has left tile t
   }
   if (kvalid) {
-    h16* outk = ws + ws_slot(p, w, krow) + ws_which_stride(p, w.br);
+    h16* outk = ws_base(ws, dd, w) + ws_slot(p, w, krow) + ws_which_stride(p, w.br);
     h16* outv = outk + ws_which_stride(p, w.br);
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* 
 
 }  // namespace
 
-void mt_attn::launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, hipStream_t s) {
+void mt_attn::launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s) {
   const Plan p = make_plan(plan, 128);
-  hipLaunchKernelGGL(dilated_attn_bwd_kv_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws);
+  hipLaunchKernelGGL(dilated_attn_bwd_kv_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
 }

@@ -16,7 +16,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __restrict__ qkv, const h16* __restrict__ dmixed,
                                                                  const float* __restrict__ lse_tot, const float* __restrict__ delta_br,
-                                                                 Plan p, h16* __restrict__ ws) {
+                                                                 Plan p, h16* __restrict__ ws, DenseDst dd) {
   // K and V tiles in LDS-DMA images (attn_common.h: img_off), double-buffered, one barrier per tile; the K image serves
   // both the row reads (S) and the transposed reads (dQ): one image instead of two, no staging stores
   __shared__ __attribute__((aligned(16))) h16 smem[4 * IMG_HALVES];      // K0 | K1 | V0 | V1
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __re
   for (int t = 0; t < nplain; ++t) tile(t, std::false_type{});
   if (tail_last) tile(ntile - 1, std::true_type{});
   if (qvalid) {
-    h16* out = ws + ws_slot(p, w, qrow);
+    h16* out = ws_base(ws, dd, w) + ws_slot(p, w, qrow);
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
       const h16x4 v = {(h16)dq0[4 * gq], (h16)dq0[4 * gq + 1], (h16)dq0[4 * gq + 2], (h16)dq0[4 * gq + 3]};
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __re
 
 }  // namespace
 
-void mt_attn::launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, hipStream_t s) {
+void mt_attn::launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s) {
   const Plan p = make_plan(plan, 128);
-  hipLaunchKernelGGL(dilated_attn_bwd_q_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws);
+  hipLaunchKernelGGL(dilated_attn_bwd_q_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
 }

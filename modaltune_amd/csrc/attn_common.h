@@ -56,6 +56,14 @@ Plan make_plan(const MtDilatedPlan* p, int qtile) {
   return d;
 }
 
+// the dense branch (ratio 1: it covers every (position, head)); the LAST one if several, as the device-side dense_branch()
+// of attn.hip; -1 when the plan has none
+int dense_branch_host(const MtDilatedPlan* p) {
+  int d = -1;
+  for (int b = 0; b < p->nbranch; ++b) if (p->ratio[b] == 1) d = b;
+  return d;
+}
+
 bool plan_ok(const MtDilatedPlan* p) {
   if (!p || p->nbranch < 1 || p->nbranch > MT_MAX_BRANCHES || p->N < 1 || p->B < 1) return false;
   for (int i = 0; i < p->nbranch; ++i) {
@@ -199,6 +207,15 @@ MT_DEVINL long ws_slot(const Plan& p, const WorkItem& w, long token_row) {
   return p.ws_off[w.br] + (token_row * 3) * (hb * HD) + (w.h % hb) * HD;
 }
 MT_DEVINL int ws_which_stride(const Plan& p, int br) { return (H / p.ratio[br]) * HD; }
+// Base the epilogues add ws_slot() to: the workspace, or for branch `dense_br` the base the launcher derived from dense_dst
+// (dense_base + ws_off[dense_br] = dense_dst; dense_br = -1: every branch goes to the workspace).  w.br is wave-uniform: one
+// scalar select.
+struct DenseDst { h16* base; int br; };
+DenseDst make_dense_dst(const MtDilatedPlan* plan, const Plan& p, mt_half* dense_dst) {
+  const int db = dense_dst ? dense_branch_host(plan) : -1;
+  return DenseDst{db >= 0 ? (h16*)dense_dst - p.ws_off[db] : nullptr, db};
+}
+MT_DEVINL h16* ws_base(h16* ws, const DenseDst& dd, const WorkItem& w) { return w.br == dd.br ? dd.base : ws; }
 
 MT_DEVINL Seq make_seq(const Plan& p, const WorkItem& w) {
   Seq q;
@@ -301,7 +318,12 @@ struct StageRow {       // eight lanes per row
 // rebuild one kernel).  mt_dilated_attn_bwd (attn.hip) calls these launchers.
 namespace mt_attn {
 // (C-ABI types only: the device-side Plan lives in each unit's anonymous namespace and has no linkage)
-void launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, hipStream_t s);
-void launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, hipStream_t s);
+// dense_dst: where the dense branch's gradients go.  nullptr = its region of the workspace (the workspace form); the dense
+// [B*N, 2304] dqkv = the in-place form: the dense branch's slot of (token, which, head) has exactly the address arithmetic of
+// the dqkv row (ws_slot with 16 heads per `which`), so the epilogues only select another base.  Needs a plan with a dense branch.
+void launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s);
+void launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s);
 void launch_bwd_combine(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, hipStream_t s);
+// in-place form: dqkv already holds the dense branch; adds the sparse branches where they cover a head, touches nothing else
+void launch_bwd_combine_inplace(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, hipStream_t s);
 }  // namespace mt_attn

@@ -73,7 +73,7 @@ extern "C" int mt_longnet_layer_bwd(const MtLongNetLayerWeights* w, const MtLong
                                        MT_OUT_F32, 1, nullptr, nullptr, b->dh16, drop_attn, M, D, s));
   MT_STEP(MT_LNB_OUT, mt_gemm_nt_f16(b->dh16, D, nullptr, w->wt_out, M, D, D, MT_EPI_BIAS, &none, b->u16, D, nullptr, MT_OUT_F16, s));
   MT_STEP(MT_LNB_MIX, mt_dilated_mix_ln_bwd(b->u16, b->o_br, b->lse_br, b->lse_tot, plan, w->inner_ln_w, b->stin, b->dmixed, b->delta, s));
-  MT_STEP(MT_ATTN_BWD_ALL << MT_LNB_ATTN_SHIFT, mt_dilated_attn_bwd(b->qkv, b->dmixed, b->lse_tot, b->delta, plan, b->attn_ws, b->dqkv16,
+  MT_STEP(MT_ATTN_BWD_ALL << MT_LNB_ATTN_SHIFT, mt_dilated_attn_bwd_inplace(b->qkv, b->dmixed, b->lse_tot, b->delta, plan, b->attn_ws, b->dqkv16,
                                                                     (steps >> MT_LNB_ATTN_SHIFT) & MT_ATTN_BWD_ALL, s));
   MT_STEP(MT_LNB_QKV, mt_gemm_nt_f16(b->dqkv16, 3 * D, nullptr, w->wt_qkv, M, D, 3 * D, MT_EPI_BIAS, &none, b->dy16, D, nullptr, MT_OUT_F16, s));
   MT_STEP(MT_LNB_LN1, mt_layernorm_bwd(b->dy16, D, nullptr, MT_OUT_F16, b->hin, D, nullptr, MT_OUT_F32, 0, w->ln1_w, b->st1, b->dh, D, nullptr,

@@ -204,6 +204,17 @@ def dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, del
                                             _p(dmixed), _p(delta_br), _s()), "dilated_mix_ln_bwd")
 
 
+def dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs=0):
+    """dilated_mix_ln_fwd with the number of workgroups given (tests, tools/mix_microbench.py): the results do not depend on it."""
+    check(_lib.load().mt_dilated_mix_ln_fwd_grid(_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats),
+                                                 _p(lse_tot), int(grid_wgs), _s()), "dilated_mix_ln_fwd_grid")
+
+
+def dilated_mix_ln_bwd_grid(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, grid_wgs=0):
+    check(_lib.load().mt_dilated_mix_ln_bwd_grid(_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats),
+                                                 _p(dmixed), _p(delta_br), int(grid_wgs), _s()), "dilated_mix_ln_bwd_grid")
+
+
 def dilated_attn_bwd_workspace_bytes(plan) -> int:
     n = _lib.load().mt_dilated_attn_bwd_workspace_bytes(C.byref(plan))
     if n < 0:
@@ -223,6 +234,13 @@ def dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqk
     """Selected phases (ATTN_BWD_KV | ATTN_BWD_Q | ATTN_BWD_COMBINE) of the backward: the sequence-parallel path fills parts of
     the workspace from another plan's launches before the combine."""
     _dilated_attn_bwd_phase(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases)
+
+
+def dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases=ATTN_BWD_ALL):
+    """The form the layer launcher uses: the dense (ratio 1) branch is written straight into dqkv16 by the KV and Q phases, the
+    COMBINE phase (once, after both) adds the sparse branches in place.  Equal inputs give the dqkv16 of dilated_attn_bwd."""
+    check(_lib.load().mt_dilated_attn_bwd_inplace(_p(qkv), _p(dmixed), _p(lse_tot), _p(delta_br), C.byref(plan), _p(workspace),
+                                                  _p(dqkv16), phases, _s()), "dilated_attn_bwd_inplace")
 
 
 def dilated_attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16):

@@ -30,4 +30,7 @@ def t(fn, n=8):
 out = {"fwd": t(lambda: ops.dilated_attn_fwd(qkv, plan, o_br, lse_br))}
 for name, ph in (("kv", ops.ATTN_BWD_KV), ("q", ops.ATTN_BWD_Q), ("comb", ops.ATTN_BWD_COMBINE)):
     out[name] = t(lambda: ops.dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta, plan, wsb, dqkv, ph))
+if hasattr(ops, "dilated_attn_bwd_inplace_phases"):      # the form the layer launcher uses (dense branch straight into dqkv)
+    for name, ph in (("kv_inplace", ops.ATTN_BWD_KV), ("q_inplace", ops.ATTN_BWD_Q), ("comb_inplace", ops.ATTN_BWD_COMBINE)):
+        out[name] = t(lambda: ops.dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta, plan, wsb, dqkv, ph))
 print(" ".join(f"{k} {v:.4f}" for k, v in out.items()))

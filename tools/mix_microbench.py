@@ -1,4 +1,6 @@
-"""Branch mix + inner LayerNorm (forward, backward) and the backward's combine kernel at L = 10 000 (for rocprofv3 --pmc runs)."""
+"""Branch mix + inner LayerNorm (forward, backward) and the backward's combine kernel at L = 10 000 (for rocprofv3 --pmc runs).
+The in-place combine and --sweep (the mix kernels over a range of grids) need a library that has those entries; with an older
+library they are left out."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from modaltune_amd import ops
@@ -29,3 +31,13 @@ fwd = t(lambda: ops.dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats,
 bwd = t(lambda: ops.dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta))
 comb = t(lambda: ops.dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta, plan, ws, dqkv, ops.ATTN_BWD_COMBINE))
 print(f"mix_fwd {fwd:.4f} mix_bwd {bwd:.4f} combine {comb:.4f} ms  checksum {float(y.float().abs().sum()):.6e} {float(dmixed.float().abs().sum()):.6e} {float(delta.abs().sum()):.6e}")
+if hasattr(ops, "dilated_attn_bwd_inplace_phases"):
+    ops.dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta, plan, ws, dqkv, ops.ATTN_BWD_KV | ops.ATTN_BWD_Q)
+    # (repeated in-place combines keep adding into dqkv until it overflows: the traffic and the time do not change, the values mean
+    # nothing -- the checksum line above is printed before this on purpose, and nothing reads dqkv after it)
+    print("combine_inplace " + " ".join(f"{t(lambda: ops.dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta, plan, ws, dqkv, ops.ATTN_BWD_COMBINE)):.4f}" for _ in range(3)) + " ms")
+if "--sweep" in sys.argv and hasattr(ops, "dilated_mix_ln_fwd_grid"):
+    for grid in (256, 512, 768, 1024, 1536, 2048, 4096):
+        f = t(lambda: ops.dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid))
+        b = t(lambda: ops.dilated_mix_ln_bwd_grid(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta, grid))
+        print(f"sweep grid {grid}: mix_fwd {f:.4f} mix_bwd {b:.4f} ms")
