@@ -112,6 +112,13 @@ class _Lease:
 QK_SCALE_LOG2 = 0.14433756729740643 * 1.4426950408889634      # 48^-1/2 * log2(e) (include/modaltune_hip.h: MT_QK_SCALE_LOG2)
 
 
+def flatten_genes(genes) -> torch.Tensor:
+    """The gene values of a slide -- one tensor, or the per-group tensors -- as one flat tensor: a view where there is a single tensor
+    (dtype and device are the caller's business)."""
+    gl = [genes] if torch.is_tensor(genes) else list(genes)
+    return gl[0].reshape(-1) if len(gl) == 1 else torch.cat([g.reshape(-1) for g in gl])
+
+
 def _scaled_copy(t: torch.Tensor, alpha: float) -> torch.Tensor:
     """alpha * t as a new fp32 tensor (mt_axpy_dev; the scale factor of the attention's q projection)."""
     out = torch.empty_like(t)
@@ -752,10 +759,7 @@ class Engine:
         if not torch.is_tensor(genes) and len(genes) != G:
             raise ValueError(f"expected {G} gene groups, got {len(genes)}")
         # all pathway networks in one launch per direction (the reference loops over 2 G nn.Linear modules)
-        if torch.is_tensor(genes):
-            gflat = genes.to(self.device, F32).reshape(-1)
-        else:
-            gflat = torch.cat([gi.reshape(-1) for gi in genes]).to(self.device, F32)
+        gflat = flatten_genes(genes).to(self.device, F32)
         if gflat.numel() != self._gene_total:
             raise ValueError(f"expected {self._gene_total} gene values in {G} groups, got {gflat.numel()}")
         # train mode: AlphaDropout after each ELU (GE:178-181) and Dropout in the mixer.  The reference calls the model once per

@@ -8,7 +8,7 @@ The probes themselves (sklearn LogisticRegression / lifelines Cox, TM:329-458) a
 """
 from __future__ import annotations
 
-from collections import OrderedDict
+from types import SimpleNamespace
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -16,7 +16,8 @@ import torch
 
 from . import pass_groups
 from .config import attention_sites, coords_to_rowcol
-from .engine import Engine, F32
+from .engine import Engine, F32, flatten_genes
+from .graph_cache import GraphCache
 
 
 def multitask_forward(model, task_ids: Optional[Sequence[int]] = None, num_tasks: Optional[int] = None, **kwargs) -> torch.Tensor:
@@ -32,15 +33,18 @@ def multitask_forward(model, task_ids: Optional[Sequence[int]] = None, num_tasks
 
 
 class EmbeddingExtractor:
-    """Forward-only pass over slides with static buffers + hipGraph replay per bag geometry: an LRU of captured geometries, a
-    geometry is captured once it has come back `capture_after` times (real data has a new bag length almost every slide: those run
-    the eager schedule).  TITAN configuration: the gridding and its one host read-back (the token count) run eagerly into static
-    buffers, the capture starts at the token gather and is keyed on (patches, TOKENS) -- as TrainStep.step_graphed does.
+    """Forward-only pass over slides with static buffers + hipGraph replay per bag geometry (graph_cache.py: captured once it has
+    come back `capture_after` times, up to `graph_cache_size` of them).  TITAN configuration: the gridding and its one host read-back
+    (the token count) run eagerly into static buffers, the capture starts at the token gather and is keyed on (patches, TOKENS) -- as
+    TrainStep.step_graphed does.
 
     attention: None (default: logits only), True (every site of config.attention_sites) or a list of site names -- the reference's
     module paths of the adapter attentions.  With a request, a call returns (logits, {site: map}): the head-averaged attention
     weights that a forward hook on those nn.MultiheadAttention modules reads as output[1] in the reference, computed by the same
     forward (batched, two pass groups or graph replay alike) right behind each attention core.  Not for TITAN models."""
+
+    graph_cache_size = property(lambda o: o._cache.size, lambda o, v: setattr(o._cache, "size", int(v)))
+    capture_after = property(lambda o: o._cache.capture_after, lambda o, v: setattr(o._cache, "capture_after", int(v)))
 
     def __init__(self, engine: Engine, task_ids: Sequence[int] = (0, 1, 2), graphed: bool = True, graph_cache_size: int = 8,
                  capture_after: int = 1, attention=None):
@@ -55,11 +59,8 @@ class EmbeddingExtractor:
                 raise ValueError(f"unknown attention site(s) {bad}; this model has {every}")
         nt = max(1, engine.cfg.multi_task)
         self.onehots = torch.eye(nt, dtype=F32, device=self.dev)[list(task_ids)].contiguous()
-        self.graph_cache_size, self.capture_after = int(graph_cache_size), int(capture_after)
-        self._cache: "OrderedDict[tuple, dict]" = OrderedDict()
-        self._visits: Dict[tuple, int] = {}
+        self._cache = GraphCache(graph_cache_size, capture_after)      # key -> SimpleNamespace(graph, out, generation)
         self._static_key = None
-        self._pool = None
         self.graph_replays = 0
         self.patch_size_lv0 = 1024          # TITAN configuration only (titan_adapter.py:335)
         self.split_passes = pass_groups.split_mode() != "off"
@@ -101,8 +102,8 @@ class EmbeddingExtractor:
     @property
     def _graph(self):
         """The most recently used captured graph (None while nothing is captured)."""
-        live = [e["graph"] for e in self._cache.values() if e.get("graph") is not None]
-        return live[-1] if live else None
+        live = list(self._cache.entries.values())
+        return live[-1].graph if live else None
 
     @torch.no_grad()
     def __call__(self, x, coords, genes: Sequence[torch.Tensor], clinical=None):
@@ -126,7 +127,7 @@ class EmbeddingExtractor:
             maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None
             lg = eng.forward(x, coords, list(genes), self.onehots, need_grad=False, clinical=clinical, attn_maps=maps)
             return (lg, maps) if maps else lg
-        gflat = genes.reshape(-1) if torch.is_tensor(genes) else torch.cat([g.reshape(-1) for g in genes])
+        gflat = flatten_genes(genes)
         if titan:
             Lv = eng.stage_slide(x, coords, self.patch_size_lv0)      # eager gridding + the one read-back -> token count
             eng._workspace(B, Lv)                                     # (may grow the workspace: bumps eng.generation)
@@ -150,8 +151,8 @@ class EmbeddingExtractor:
         # the engine's generation is part of the key: a workspace that grew under another user of the engine (the trainer
         # shares the B = 3 storage), rebuilt weight caches (load_state_dict) or a stochastic toggle retire the captures
         key = (L, Lv, eng.generation, self.sites)           # (the maps are static outputs of the capture, like the logits)
-        for k in [k for k in self._cache if k[2] != eng.generation]:
-            del self._cache[k]
+        cache = self._cache
+        cache.sync(eng.generation)
         if titan:
             run = lambda: eng.forward_slide(None, None, self._sgenes, self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=False,
                                             clinical=self._sclin, staged=True)
@@ -159,31 +160,22 @@ class EmbeddingExtractor:
             run = lambda: self._forward_groups(B, L)
         else:
             run = lambda: self._forward_batched(B, L)
-        ent = self._cache.get(key)
+        ent = cache.get(key)
         if ent is None:
-            seen = self._visits.get(key, 0)
-            if seen < self.capture_after:
-                if len(self._visits) > 4096:
-                    self._visits.clear()
-                self._visits[key] = seen + 1
+            if not cache.admit(key):
                 return run()
             torch.cuda.synchronize()
-            if self._pool is None or not self._cache:
-                self._pool = torch.cuda.graph_pool_handle()           # one pool for all captures (they never run concurrently)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+            with torch.cuda.graph(g, pool=cache.pool_for(g), capture_error_mode="thread_local"):
                 out = run()
-            ent = self._cache[key] = {"graph": g, "out": out}
-            while len(self._cache) > max(1, self.graph_cache_size):
-                self._cache.popitem(last=False)
-        else:
-            self._cache.move_to_end(key)
-        ent["graph"].replay()
+            ent = SimpleNamespace(graph=g, out=out, generation=key[2])
+            cache.put(key, ent)
+        ent.graph.replay()
         self.graph_replays += 1
         if self.sites:
-            lg, maps = ent["out"]
+            lg, maps = ent.out
             return lg.clone(), {s: w.clone() for s, w in maps.items()}
-        return ent["out"].clone()
+        return ent.out.clone()
 
 
 def attention_to_grid(weights, coords, tile: float = 256.0) -> np.ndarray:

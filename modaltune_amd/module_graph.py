@@ -16,17 +16,15 @@ regenerates them from the same state).
 """
 from __future__ import annotations
 
-import gc
 import os
 import weakref
-from collections import OrderedDict
 from typing import Optional
 
 import torch
 
 from . import ops, pass_groups
-
-F32 = torch.float32
+from .engine import F32, flatten_genes
+from .graph_cache import GraphCache
 
 
 class _Lease:
@@ -39,23 +37,22 @@ class _Lease:
 
 
 class _Entry:
-    __slots__ = ("gf", "gb", "logits", "dl", "split")
+    __slots__ = ("gf", "gb", "logits", "dl", "split", "generation")
 
-    def __init__(self):
+    def __init__(self, generation: int):
         self.gf = self.gb = self.logits = self.dl = None
-        self.split = False
+        self.split, self.generation = False, generation
 
 
 class ModuleReplay:
+    cache_size = property(lambda o: o.graphs.size, lambda o, v: setattr(o.graphs, "size", int(v)))
+    capture_after = property(lambda o: o.graphs.capture_after, lambda o, v: setattr(o.graphs, "capture_after", int(v)))
+    visits = property(lambda o: o.graphs.visits, lambda o, v: setattr(o.graphs, "visits", v))      # (the priming visits are counted here too)
+
     def __init__(self, module, capture_after: int = 2, cache_size: int = 4):
         self.module = module
-        self.capture_after, self.cache_size = int(capture_after), int(cache_size)
         self.enabled = os.environ.get("MT_MODULE_GRAPH", "1") not in ("0", "off")
-        self.cache: "OrderedDict[tuple, _Entry]" = OrderedDict()
-        self.visits = {}
-        self.gen = -1
-        self.pool = None
-        self.stream = None
+        self.graphs = GraphCache(cache_size, capture_after)      # key -> _Entry
         self.static_key = None
         self.sgenes = self.sonehots = self.sclin = None
         self.lease = None                 # weakref to the _Lease of the replayed forward whose backward is still to come
@@ -96,12 +93,10 @@ class ModuleReplay:
         ngenes = int(sum(g.numel() for g in gl))
         split = pass_groups.eligible(eng, B, L, m.split_min_patches, m.split_passes)
         key = (L, B, ngenes, split, bool(eng.stochastic), None if clinical is None else tuple(clinical.shape))
-        ent = self.cache.get(key)
+        graphs = self.graphs
+        ent = graphs.get(key)
         seen = self.visits.get(key, 0)
-        if (ent is None or ent.gf is None) and seen < self.capture_after:
-            if len(self.visits) > 4096:
-                self.visits.clear()
-            self.visits[key] = seen + 1
+        if (ent is None or ent.gf is None) and not graphs.admit(key):
             return None
         if self._busy():
             self.eager_fallbacks += 1
@@ -115,28 +110,22 @@ class ModuleReplay:
             self.sgenes = torch.empty(ngenes, dtype=F32, device=dev)
             self.sonehots = torch.empty(B, int(onehots.shape[1]), dtype=F32, device=dev)
             self.sclin = torch.empty(1, int(clinical.numel()), dtype=F32, device=dev) if clinical is not None else None
-            self.cache.clear()
+            graphs.clear()
         groups = pass_groups.group_bounds(B, singles=os.environ.get("MT_MODULE_GROUPS") == "singles") if split else [(0, B)]      # (experiments)
         slots = pass_groups.group_slots(groups, base=self.SLOT0)
         for (a, b), sl in list(zip(groups, slots))[1:]:
             eng._workspace(b - a, L, slot=sl)                       # (all workspaces exist -- and have grown -- before anything is captured)
         eng.stage_inputs(x2, coords, eng._workspace(groups[0][1] - groups[0][0], L, slot=slots[0]))      # (may grow the workspace: bumps eng.generation)
-        self.sgenes.copy_(torch.cat([g.reshape(-1) for g in gl]).to(F32) if len(gl) > 1 else gl[0].reshape(-1), non_blocking=True)
+        gflat = flatten_genes(gl)
+        self.sgenes.copy_(gflat.to(F32) if len(gl) > 1 else gflat, non_blocking=True)
         self.sonehots.copy_(onehots, non_blocking=True)
         if self.sclin is not None:
             self.sclin.copy_(clinical.reshape(1, -1), non_blocking=True)
-        if self.gen != eng.generation:            # buffers the old captures point to are gone
-            for e in self.cache.values():
-                e.gf = e.gb = None
-            self.gen = eng.generation
-        ent = self.cache.get(key)
+        graphs.sync(eng.generation)               # buffers the old captures point to are gone
+        ent = graphs.get(key)
         if ent is None:
-            ent = _Entry()
-            self.cache[key] = ent
-            while len(self.cache) > max(1, self.cache_size):
-                self.cache.popitem(last=False)
-        else:
-            self.cache.move_to_end(key)
+            ent = _Entry(eng.generation)
+            graphs.put(key, ent)
         self._buffers(ent, B)
         calls = None
         if ent.gf is None and seen < self.capture_after + 2:
@@ -151,12 +140,10 @@ class ModuleReplay:
         else:
             if ent.gf is None:
                 self.ncap[key] = self.ncap.get(key, 0) + 1
-                if self.ncap[key] >= 2 and self.cache_size < 16 and len(self.cache) >= self.cache_size:
+                if self.ncap[key] >= 2 and self.cache_size < 16 and len(graphs.entries) >= self.cache_size:
                     self.cache_size *= 2      # more recurring geometries than entries (a rotation would recapture on every visit)
                 self._capture(ent, L, B, groups, slots, split)
-                if self.gen != eng.generation:    # the capture itself moved a buffer: these graphs are stale -- prime and capture again
-                    ent.gf = ent.gb = None
-                    self.gen = eng.generation
+                if graphs.sync(eng.generation):   # the capture itself moved a buffer: these graphs are stale -- prime and capture again
                     self.visits[key] = self.capture_after
                     return None
             ent.gf.replay()
@@ -206,38 +193,17 @@ class ModuleReplay:
 
     def _capture(self, ent, L, B, groups, slots, split):
         eng = self.module.engine
-        if self.stream is None:
-            self.stream = torch.cuda.Stream(device=eng.device)
         ent.split = split
         self._resources(groups)
-        main, side = torch.cuda.current_stream(), self.stream
-        gc.collect()          # (dead models' hipGraphs are finalised here, not inside the capture: see TrainStep._capture)
-        side.wait_stream(main)
-        if self.pool is None or not any(e.gf is not None for e in self.cache.values()):
-            self.pool = torch.cuda.graph_pool_handle()      # (a pool dies with the last graph captured into it)
         hook, eng.grad_ready_hook = eng.grad_ready_hook, None
         try:
-            with torch.cuda.stream(side):
-                graphs = []
-                for body in (lambda: self._forward_body(ent, L, B, groups, slots, split),
-                             lambda: self._backward_body(ent, graphs[0][1], groups, split)):
-                    g = torch.cuda.CUDAGraph()
-                    g.capture_begin(pool=self.pool, capture_error_mode="thread_local")
-                    try:
-                        out = body()
-                    except BaseException:
-                        try:
-                            g.capture_end()
-                        except Exception:
-                            pass
-                        raise
-                    g.capture_end()
-                    graphs.append((g, out))
-                gf, gb = graphs[0][0], graphs[1][0]
+            with self.graphs.capture() as cap:
+                calls = self._forward_body(ent, L, B, groups, slots, split)
+                cap.cut()
+                self._backward_body(ent, calls, groups, split)
         finally:
             eng.grad_ready_hook = hook
-        main.wait_stream(side)
-        ent.gf, ent.gb = gf, gb
+        ent.gf, ent.gb = cap.graphs
         self.captures += 1
 
     # ---------------------------------------------------------------- backward

@@ -10,9 +10,7 @@ for just before AdamW -- the collectives of the upper blocks run under the backw
 """
 from __future__ import annotations
 
-import gc
 import os
-from collections import OrderedDict
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -20,7 +18,8 @@ import torch
 
 from . import dp, ops, pass_groups
 from ._lib import rowmap
-from .engine import Engine, F32
+from .engine import Engine, F32, flatten_genes
+from .graph_cache import GraphCache
 from .tape import Param, Var
 
 
@@ -28,13 +27,16 @@ class _Captured:
     """The hipGraphs of one bag geometry: `segs` = [(graph, bucket or None)] replayed in order; after a segment with a
     bucket index the reducer starts that bucket (world_size > 1 cuts the backward at the bucket boundaries; on one GPU
     the whole step, optimiser included, is a single segment)."""
-    __slots__ = ("segs", "visits", "logits")
+    __slots__ = ("segs", "logits", "generation")
 
-    def __init__(self):
-        self.segs, self.visits, self.logits = None, 0, None
+    def __init__(self, generation: int):
+        self.segs, self.logits, self.generation = None, None, generation
 
 
 class TrainStep:
+    graph_cache_size = property(lambda o: o._gcache.size, lambda o, v: setattr(o._gcache, "size", int(v)))      # (both live on the cache: assigned after construction too)
+    capture_after = property(lambda o: o._gcache.capture_after, lambda o, v: setattr(o._gcache, "capture_after", int(v)))
+
     def __init__(self, engine: Engine, lr: float = 1e-4 / 20, weight_decay: float = 0.01, betas=(0.9, 0.999),
                  eps: float = 1e-8, init_scale: float = 2.0 ** 15, growth_interval: int = 2000,
                  process_group=None, task_ids: Sequence[int] = (0, 1, 2), text_rows: Sequence[int] = (0, 1, 3),
@@ -72,17 +74,9 @@ class TrainStep:
         self.reducer = dp.GradReducer(engine.store.flat_grad, dp.grad_buckets(engine.store.slots, nint, n), process_group,
                                       flat_param=engine.store.flat)
         engine.store.sync = self.reducer.wait_params      # state_dict() / a forward outside the step see complete parameters
-        # captured graphs: LRU over bag geometries (real data has a new length almost every slide: a geometry is captured
-        # only once it has been seen `capture_after` times, everything else runs the eager schedule)
-        self.graph_cache_size, self.capture_after = int(graph_cache_size), int(capture_after)
-        self._gcache: "OrderedDict[tuple, _Captured]" = OrderedDict()      # LRU over geometries that HOLD captured graphs
-        self._visits: Dict[tuple, int] = {}        # eager visits of not-yet-captured geometries (never evicts a capture)
-        self._ggen = -1
-        self._opt_graph = None
-        self._pool = None                   # graph memory pool shared by all captures (see _capture)
-        self._cap_stream = None
-        self._cap = None                    # state of a segmented capture in progress
-        self._trial_keep: list = []         # captures a schedule trial holds outside the LRU (they keep the shared graph pool alive)
+        self._gcache = GraphCache(graph_cache_size, capture_after)      # the captured bag geometries: key -> _Captured
+        self._opt_graph, self._opt_gen = None, -1      # world > 1: the optimiser's graph and the generation it was captured under
+        self._cap, self._cap_buckets = None, []      # the graph_cache.Capture of a step in progress, the bucket behind each of its cuts
         self._static_key = None
         self.graph_replays = 0
         self.eager_steps = 0
@@ -427,7 +421,7 @@ class TrainStep:
         x = x.reshape(-1, x.shape[-1])
         L = x.shape[0]
         B = self.onehots.shape[0]
-        gflat = genes.reshape(-1) if torch.is_tensor(genes) else torch.cat([g.reshape(-1) for g in genes])
+        gflat = flatten_genes(genes)
         skey = (int(gflat.numel()), tuple(text.shape))
         if self._static_key != skey:
             self._static_key = skey
@@ -456,16 +450,15 @@ class TrainStep:
         if self._sclin is not None:
             self._sclin.copy_(clinical.reshape(1, -1), non_blocking=True)
         world, dp_on = self._world(), self._dp()
-        if self._ggen != eng.generation:          # buffers the old captures point to are gone (visit counts stay)
-            for e in self._gcache.values():
-                e.segs = e.logits = None
+        cache, gen = self._gcache, eng.generation
+        cache.sync(gen)                           # buffers the old captures point to are gone
+        if self._opt_gen != gen:
             self._opt_graph = None
-            self._ggen = eng.generation
         # (the data-parallel schedule is part of the key: bench.py --gpus N times the three schedules one after the other)
         key = (L, Lv, world, bool(eng.stochastic), self.dp_schedule if dp_on else None, self.force_bucket_joins)
-        ent = self._gcache.get(key)
+        ent = cache.get(key)
         if (self.auto_split and not dp_on and Lv not in self.split_decisions and B >= 3 and Lv >= 2048 and self._can_split()
-                and (ent is None or ent.segs is None) and self._visits.get(key, 0) >= self.capture_after
+                and (ent is None or ent.segs is None) and cache.visits.get(key, 0) >= cache.capture_after
                 and not torch.cuda.is_current_stream_capturing()):
             self._trial_split(x, coords, genes, text, clinical, Lv, key)     # (sets split_decisions[Lv]; training state untouched)
             return self.step_graphed(x, coords, genes, text, clinical=clinical)
@@ -473,26 +466,16 @@ class TrainStep:
         def fwd_bwd():
             self._fwd_bwd(None, None, self._sgenes, self._stext, self._sclin, staged_geometry=(B, Lv))
 
-        # Visit counts live OUTSIDE the LRU: on ragged data almost every slide has a new length, and a stream of one-off
-        # lengths must neither evict the captured graphs of a hot geometry nor reset its count.
         if ent is None or ent.segs is None:
-            seen = self._visits.get(key, 0)
-            if seen < self.capture_after:         # eager visits (allocator, lazy kernel attributes, the tape's gradient arena
-                if len(self._visits) > 4096:      # sized from the last step)
-                    self._visits.clear()
-                self._visits[key] = seen + 1
-                fwd_bwd()
+            if not cache.admit(key):              # eager visits (allocator, lazy kernel attributes, the tape's gradient arena
+                fwd_bwd()                         # sized from the last step)
                 self.eager_steps += 1
                 self.optimizer_step()
                 return self.loss
             if ent is None:
-                ent = _Captured()
-                self._gcache[key] = ent
-                while len(self._gcache) > max(1, self.graph_cache_size):
-                    self._gcache.popitem(last=False)
+                ent = _Captured(gen)
+                cache.put(key, ent)               # (evicts BEFORE the capture: it may reuse the evicted graphs' blocks)
             self._capture(ent, fwd_bwd, world)
-        else:
-            self._gcache.move_to_end(key)
         for g, bucket in ent.segs:
             g.replay()
             if bucket is not None:
@@ -526,7 +509,7 @@ class TrainStep:
         try:
             for split in (False, True):
                 self.split_decisions[L] = split
-                self._gcache.pop(key, None)       # (same key for both schedules: capture afresh)
+                self._gcache.pop(key)             # (same key for both schedules: capture afresh)
                 for i in range(reps + 2):         # capture (visit counts are already past capture_after), one untimed replay, reps timed
                     if i == 2:
                         torch.cuda.synchronize()
@@ -535,10 +518,7 @@ class TrainStep:
                 torch.cuda.synchronize()
                 res["groups" if split else "batched"] = round(1e3 * (time.perf_counter() - t0) / reps, 3)
                 caps[split] = self._gcache.get(key)
-                if caps[split] is not None:
-                    self._trial_keep.append(caps[split])
         finally:
-            self._trial_keep = []
             self.auto_split = was_auto
             self.graph_replays, self.eager_steps = counters
             for t, c in saved:
@@ -548,70 +528,35 @@ class TrainStep:
         self.split_decisions[L] = win
         self.split_trials[L] = res
         if caps.get(win) is not None:
-            self._gcache[key] = caps[win]
+            self._gcache.put(key, caps[win])      # (if the generation moved while it was held outside, get() never returns it and the next sync drops it)
 
     @property
     def _graphs(self):
         """Captured segment lists of the cached geometries (None when nothing is captured yet)."""
-        segs = [e.segs for e in self._gcache.values() if e.segs is not None]
+        segs = [e.segs for e in self._gcache.entries.values() if e.segs is not None]
         return segs or None
 
     def _capture(self, ent: _Captured, fwd_bwd, world: int):
-        # Dead models that sit in reference cycles (a module and its ModuleReplay point at each other) keep their hipGraphs until the
-        # cyclic collector runs -- on whatever allocation, and a graph finalised INSIDE a capture aborts the process.  Collect them
-        # here, as torch.cuda.graph does on entry.
-        gc.collect()
         torch.cuda.synchronize()
-        main = torch.cuda.current_stream()
-        if self._cap_stream is None:          # ONE capture stream: the allocator hands a freed block only to the stream it was
-            self._cap_stream = torch.cuda.Stream()      # allocated on, and torch.cuda.Stream() walks a ring of 32 streams
-        side = self._cap_stream
-        side.wait_stream(main)
-        # ONE private pool for every capture of this TrainStep: the graphs never run concurrently, so a later capture may reuse the
-        # blocks an evicted (or still cached) geometry's temporaries occupied.  A fresh pool per capture left every evicted graph's
-        # segments reserved-but-unusable until the allocator's out-of-memory sweep: +0.24 GiB per recapture at L ~ 4 000 when more
-        # lengths rotate than the LRU holds (tools/soak.py).
-        if self._pool is None or not (self._opt_graph is not None or any(e.segs for e in list(self._gcache.values()) + self._trial_keep)):
-            self._pool = torch.cuda.graph_pool_handle()      # (a pool dies with the last graph captured into it: take a fresh handle)
-        pool = self._pool
-        segs = []
-        with torch.cuda.stream(side):
-            g = torch.cuda.CUDAGraph()          # (thread_local: RCCL's watchdog thread must not invalidate the capture)
-            g.capture_begin(pool=pool, capture_error_mode="thread_local")
-            self._cap = {"segs": segs, "cur": g, "pool": pool}
+        with self._gcache.capture() as cap:
+            self._cap, self._cap_buckets = cap, []
             try:
                 fwd_bwd()
                 if not self._dp():
                     self.optimizer_step()
-            except BaseException:
-                try:
-                    self._cap["cur"].capture_end()
-                except Exception:
-                    pass
+            finally:
                 self._cap = None
-                raise
-            self._cap["cur"].capture_end()
-            segs.append((self._cap["cur"], None))
-            self._cap = None
-            if self._dp() and self._opt_graph is None:
-                og = torch.cuda.CUDAGraph()
-                og.capture_begin(pool=pool, capture_error_mode="thread_local")
-                try:
-                    self._adam_and_refresh(world, check=not self.reducer.sharded)
-                finally:
-                    og.capture_end()
-                self._opt_graph = og
-        main.wait_stream(side)
-        ent.segs, ent.logits = segs, self.last_logits
+        segs, logits = list(zip(cap.graphs, self._cap_buckets + [None])), self.last_logits
+        if self._dp() and self._opt_graph is None:
+            with self._gcache.capture() as cap:
+                self._adam_and_refresh(world, check=not self.reducer.sharded)
+            self._opt_graph, self._opt_gen = cap.graphs[0], ent.generation
+        ent.segs, ent.logits = segs, logits
 
     def _segment_break(self, bucket: int):
         """Inside a capture with world_size > 1: close the current graph at a gradient-bucket boundary, open the next."""
-        cap = self._cap
-        cap["cur"].capture_end()
-        cap["segs"].append((cap["cur"], bucket))
-        g = torch.cuda.CUDAGraph()
-        g.capture_begin(pool=cap["pool"], capture_error_mode="thread_local")
-        cap["cur"] = g
+        self._cap.cut()
+        self._cap_buckets.append(bucket)
 
     def loss_value(self) -> float:
         """The last step's loss on the host.  This is where the trainer synchronises anyway (`loss.item()`, TM:239), so the

@@ -27,5 +27,5 @@ for i in range(16):
         loss = logit.float().square().mean()
     scaler.scale(loss).backward()
     scaler.step(opt); scaler.update(); opt.zero_grad()
-    print(i, "primed", rp.primed, "captures", rp.captures, "replays", rp.replays, "fallbacks", rp.eager_fallbacks, "gen", model.engine.generation, rp.gen,
+    print(i, "primed", rp.primed, "captures", rp.captures, "replays", rp.replays, "fallbacks", rp.eager_fallbacks, "gen", model.engine.generation, rp.graphs.generation,
           "visits", dict(rp.visits), "nosync", model._nosync_rows is not None, flush=True)
