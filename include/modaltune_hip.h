@@ -416,6 +416,28 @@ int mt_gene_snn_bwd(const float* params, float* grads, const long* offs, const i
                     const float* genes, int G, int latent, int passes, const float* a1, const float* a2, const float* dz,
                     const MtDropout* alpha_drop, mt_stream_t stream);
 
+/* Integrated Gradients over the gene inputs (modaltune_amd/attribution.py): the pass axis carries `points` (1..4) quadrature points
+ * of the straight path, point p seeing the input baseline + alphas[p] (genes - baseline); baseline NULL = zeros; alphas [points] is
+ * read on the DEVICE.  No dropout (IG is defined with the stochastic layers off).  The weights are streamed once for all points: the
+ * first layer is affine in alpha, so b1 + W1 genes and b1 + W1 baseline are formed once (in mt_gene_snn_fwd's summation order) and
+ * point p takes alpha_p of the first and (1 - alpha_p) of the second -- alpha = 1 and alpha = 0 give mt_gene_snn_fwd's bits at genes
+ * and at baseline.  a1, a2, z are [G, points, latent] (a1 differs per point here).  One workgroup per pathway, any n_i >= 1. */
+int mt_gene_snn_fwd_points(const float* params, const long* offs, const int* sizes, const long* goff, const float* genes,
+                           const float* baseline, const float* alphas, int G, int latent, int points, float* a1, float* a2, float* z,
+                           mt_stream_t stream);
+/* The INPUT gradient of the pathway networks at those points, summed with the quadrature weights (weights [points], device):
+ *   dgenes[goff_i + k] (+)= unscale * sum_r W1_i[r][k] * sum_p weights[p] * elu'(a1_p[r]) * (W2_i^T (dz_p * elu'(a2_p)))[r]
+ * unscale: device scalar or NULL (= 1), the reciprocal of the caller's gradient scale; accumulate != 0: += into dgenes [sum n_i].
+ * Writes NO parameter gradient.  Every output element has one writer thread and one summation order (p ascending, then r
+ * ascending): no atomics, bit-reproducible by construction. */
+int mt_gene_snn_bwd_input(const float* params, const long* offs, const int* sizes, const long* goff, int G, int latent, int points,
+                          const float* a1, const float* a2, const float* dz, const float* weights, const float* unscale,
+                          float* dgenes, int accumulate, mt_stream_t stream);
+/* attr = (genes - baseline) * dgenes (all [sum n_i]; baseline NULL = zeros) and pathway[i] = sum_k attr[goff_i + k] in a fixed
+ * order (the same bits on every call). */
+int mt_ig_finalize(const float* genes, const float* baseline, const float* dgenes, const int* sizes, const long* goff, int G,
+                   float* attr, float* pathway, mt_stream_t stream);
+
 /* Small dense multi-head attention over tokens (prompt self-attention AM:87): q,k,v fp32 [B,T,E], heads h; the head dim
  * E / h must be 16, 32 or 64 (MT_ERR_UNSUPPORTED otherwise). */
 int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,

@@ -405,3 +405,200 @@ extern "C" int mt_gene_snn_bwd(const float* params, float* grads, const long* of
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
+
+// ---- Integrated Gradients over the gene inputs (attribution.py): the pass axis carries P quadrature points of the straight path
+// g_p = baseline + alpha_p (genes - baseline) instead of P dropout draws.  Forward = the networks at all P points with the weights
+// streamed once; backward = the INPUT gradient only (no parameter-gradient slot is touched); finalize = (genes - baseline) * dF/dgenes
+// and its per-pathway sums.  One workgroup per pathway throughout: these launches sit beside a full backbone pass.
+namespace {
+
+struct GenePointArgs {
+  const float* params;
+  const long* offs; const int* sizes; const long* goff;      // as GeneArgs
+  const float* genes; const float* baseline;                 // baseline may be null (= zeros)
+  const float* alphas;                                       // [P] device: position of each point on the path
+  const float* weights;                                      // [P] device: quadrature weight of each point (backward)
+  const float* unscale;                                      // device scalar or null (= 1): undoes the caller's gradient scaling
+  float* a1; float* a2; float* z;                            // [G][P][latent] each: the first layer differs per point here
+  const float* dz;                                           // [G][P][latent]
+  float* dgenes;                                             // [total]
+  int G, accumulate;
+};
+
+template <int P>
+__global__ __launch_bounds__(GL) void gene_snn_fwd_points_kernel(GenePointArgs a) {
+  __shared__ float Ws[GL][GC + 1];
+  __shared__ float xs[P < 2 ? 2 : P][GL];      // first layer: row 0 = genes, row 1 = baseline; second layer: h1 of point p
+  const int i = blockIdx.x, j = threadIdx.x;
+  const int n = a.sizes[i];
+  const long* o = a.offs + 4L * i;
+  const float* g = a.genes + a.goff[i];
+  const float* bl = a.baseline ? a.baseline + a.goff[i] : nullptr;
+  // The first layer is affine in alpha: b1 + W1 genes and b1 + W1 baseline are formed ONCE (each in the summation order of
+  // gene_snn_fwd_kernel: bias first, k ascending -- alpha = 1 / alpha = 0 reproduce its bits) and combined per point below
+  float accg = a.params[o[1] + j], accb = accg;
+  for (int p0 = 0; p0 < n; p0 += GL) {
+    const int pn = min(GL, n - p0);
+    __syncthreads();
+    if (j < pn) {
+      xs[0][j] = g[p0 + j];
+      xs[1][j] = bl ? bl[p0 + j] : 0.f;
+    }
+    __syncthreads();
+    for (int k0 = 0; k0 < pn; k0 += GC) {
+      const int kc = min(GC, pn - k0);
+      __syncthreads();
+      for (int t = j; t < GL * GC; t += GL) {
+        const int r = t / GC, c = t - r * GC;
+        Ws[r][c] = c < kc ? a.params[o[0] + (long)r * n + p0 + k0 + c] : 0.f;
+      }
+      __syncthreads();
+#pragma unroll 8
+      for (int c = 0; c < GC; ++c) {
+        const float w = lds_f32(&Ws[j][c]);
+        const bool in = k0 + c < pn;
+        accg = fmaf(w, in ? lds_f32(&xs[0][k0 + c]) : 0.f, accg);
+        accb = fmaf(w, in ? lds_f32(&xs[1][k0 + c]) : 0.f, accb);
+      }
+    }
+  }
+  __syncthreads();
+  float acc2[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const float al = a.alphas[p];
+    const float pre1 = fmaf(al, accg, (1.f - al) * accb);      // exact at alpha = 0 and alpha = 1
+    a.a1[((long)i * P + p) * GL + j] = pre1;
+    xs[p][j] = elu(pre1);
+    acc2[p] = a.params[o[3] + j];
+  }
+  gemv_rows<P>(a.params + o[2], GL, xs, Ws, acc2);
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const long e = ((long)i * P + p) * GL + j;
+    a.a2[e] = acc2[p];
+    a.z[e] = elu(acc2[p]);
+  }
+}
+
+template <int P>
+__global__ __launch_bounds__(GL) void gene_snn_bwd_input_kernel(GenePointArgs a) {
+  __shared__ float Ws[GC][GL + 1];   // 32 rows x 256 columns of W2
+  __shared__ float da2s[P][GL], ss[GL];
+  const int i = blockIdx.x, j = threadIdx.x;
+  const int n = a.sizes[i];
+  const long* o = a.offs + 4L * i;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const long e = ((long)i * P + p) * GL + j;
+    da2s[p][j] = a.dz[e] * elu_grad(a.a2[e]);
+  }
+  // dh1_p[k] = sum_r W2[r][k] da2_p[r] (thread k): W2 streamed ONCE for all points, 32 rows at a time, coalesced
+  float dh1[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) dh1[p] = 0.f;
+  for (int r0 = 0; r0 < GL; r0 += GC) {
+    __syncthreads();
+    for (int t = j; t < GC * GL; t += GL) {
+      const int r = t / GL, c = t - r * GL;
+      Ws[r][c] = a.params[o[2] + (long)(r0 + r) * GL + c];
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int r = 0; r < GC; ++r) {
+      const float w = lds_f32(&Ws[r][j]);
+#pragma unroll
+      for (int p = 0; p < P; ++p) dh1[p] = fmaf(w, lds_f32(&da2s[p][r0 + r]), dh1[p]);
+    }
+  }
+  // s[k] = sum_p w_p da1_p[k], p ascending: the input gradient is linear in da1, so the quadrature sum is taken before W1^T
+  float s = 0.f;
+#pragma unroll
+  for (int p = 0; p < P; ++p) s = fmaf(a.weights[p], dh1[p] * elu_grad(a.a1[((long)i * P + p) * GL + j]), s);
+  ss[j] = s;
+  __syncthreads();
+  // dgenes[k] (+)= unscale * sum_r W1[r][k] s[r]: ONE thread per input k (coalesced along the rows of W1), r ascending -- no atomics,
+  // every element has one writer and one summation order
+  const float us = a.unscale ? a.unscale[0] : 1.f;
+  float* dg = a.dgenes + a.goff[i];
+  const float* W1 = a.params + o[0];
+  for (int k = j; k < n; k += GL) {
+    float acc = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < GL; ++r) acc = fmaf(W1[(long)r * n + k], lds_f32(&ss[r]), acc);
+    acc *= us;
+    dg[k] = a.accumulate ? dg[k] + acc : acc;
+  }
+}
+
+struct IgFinalArgs {
+  const float* genes; const float* baseline; const float* dgenes;
+  const int* sizes; const long* goff;
+  float* attr; float* pathway;
+};
+
+// attr = (genes - baseline) * dgenes; pathway[i] = sum of its attr: per thread k ascending in steps of 256, then the wave butterfly,
+// then the four wave sums in order -- a fixed order
+__global__ __launch_bounds__(GL) void ig_finalize_kernel(IgFinalArgs a) {
+  __shared__ float part[GL / MT_WAVE];
+  const int i = blockIdx.x, j = threadIdx.x;
+  const int n = a.sizes[i];
+  const long g0 = a.goff[i];
+  float sum = 0.f;
+  for (int k = j; k < n; k += GL) {
+    const float d = a.genes[g0 + k] - (a.baseline ? a.baseline[g0 + k] : 0.f);
+    const float v = d * a.dgenes[g0 + k];
+    a.attr[g0 + k] = v;
+    sum += v;
+  }
+  sum = wave_sum(sum);
+  if ((j & (MT_WAVE - 1)) == 0) part[j / MT_WAVE] = sum;
+  __syncthreads();
+  if (j == 0) a.pathway[i] = ((lds_f32(&part[0]) + lds_f32(&part[1])) + lds_f32(&part[2])) + lds_f32(&part[3]);
+}
+
+}  // namespace
+
+extern "C" int mt_gene_snn_fwd_points(const float* params, const long* offs, const int* sizes, const long* goff, const float* genes,
+                                      const float* baseline, const float* alphas, int G, int latent, int points, float* a1, float* a2,
+                                      float* z, mt_stream_t stream) {
+  if (!params || !offs || !sizes || !goff || !genes || !alphas || !a1 || !a2 || !z || G < 1 || points < 1) return MT_ERR_BAD_ARG;
+  if (latent != GL || points > GP_MAX) return MT_ERR_UNSUPPORTED;
+  GenePointArgs a{params, offs, sizes, goff, genes, baseline, alphas, nullptr, nullptr, a1, a2, z, nullptr, nullptr, G, 0};
+  hipStream_t s = (hipStream_t)stream;
+  switch (points) {
+    case 1: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
+    case 3: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
+    default: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
+  }
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_gene_snn_bwd_input(const float* params, const long* offs, const int* sizes, const long* goff, int G, int latent,
+                                     int points, const float* a1, const float* a2, const float* dz, const float* weights,
+                                     const float* unscale, float* dgenes, int accumulate, mt_stream_t stream) {
+  if (!params || !offs || !sizes || !goff || !a1 || !a2 || !dz || !weights || !dgenes || G < 1 || points < 1) return MT_ERR_BAD_ARG;
+  if (latent != GL || points > GP_MAX) return MT_ERR_UNSUPPORTED;
+  GenePointArgs a{params, offs, sizes, goff, nullptr, nullptr, nullptr, weights, unscale, const_cast<float*>(a1), const_cast<float*>(a2),
+                  nullptr, dz, dgenes, G, accumulate != 0};
+  hipStream_t s = (hipStream_t)stream;
+  switch (points) {
+    case 1: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
+    case 3: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
+    default: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
+  }
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_ig_finalize(const float* genes, const float* baseline, const float* dgenes, const int* sizes, const long* goff, int G,
+                              float* attr, float* pathway, mt_stream_t stream) {
+  if (!genes || !dgenes || !sizes || !goff || !attr || !pathway || G < 1) return MT_ERR_BAD_ARG;
+  IgFinalArgs a{genes, baseline, dgenes, sizes, goff, attr, pathway};
+  hipLaunchKernelGGL(ig_finalize_kernel, dim3(G), dim3(GL), 0, (hipStream_t)stream, a);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}

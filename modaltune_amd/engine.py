@@ -156,6 +156,18 @@ class _W16:
                 ops.pack_weight(full, self.wt, self.N, self.K, transpose=True)
 
 
+class GenePoints:
+    """The task passes of one forward as POINTS of the straight path baseline -> genes (attribution.IntegratedGradients): pass p runs
+    the gene encoder at baseline + alphas[p] (genes - baseline), and the recorded backward adds
+    unscale * sum_p weights[p] dF_p/dgenes to `dgenes` instead of forming the pathway networks' parameter gradients.
+    baseline: flat fp32 [total genes] on the device or None (zeros); alphas, weights: fp32 [B] on the device; dgenes: the caller's
+    fp32 [total genes] accumulator; unscale: device scalar or None."""
+    __slots__ = ("baseline", "alphas", "weights", "dgenes", "unscale")
+
+    def __init__(self, baseline, alphas, weights, dgenes, unscale=None):
+        self.baseline, self.alphas, self.weights, self.dgenes, self.unscale = baseline, alphas, weights, dgenes, unscale
+
+
 def deterministic_default() -> bool:
     """What `deterministic=None` means: MT_DETERMINISTIC=1 in the environment, or torch.use_deterministic_algorithms(True)."""
     return os.environ.get("MT_DETERMINISTIC", "0") == "1" or torch.are_deterministic_algorithms_enabled()
@@ -460,7 +472,8 @@ class Engine:
     def forward(self, x: torch.Tensor, coords, genes: Sequence[torch.Tensor], task_onehots: torch.Tensor,
                 need_grad: bool = True, fresh: bool = False, staged: bool = False, geometry=None,
                 clinical: Optional[torch.Tensor] = None, share: Optional[dict] = None, tape: Optional[Tape] = None,
-                site_group: int = 0, ws_slot: int = 0, attn_maps: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+                site_group: int = 0, ws_slot: int = 0, attn_maps: Optional[Dict[str, torch.Tensor]] = None,
+                points: Optional[GenePoints] = None, stochastic: Optional[bool] = None) -> torch.Tensor:
         """x [L, in_chans] (or [1,L,in]); coords [L,2] (host or device); genes: list of [1, n_i]; task_onehots [B, num_tasks].
         Returns logits [B, output_dim] (fp32, device).  fresh=True gives this call its own tape and workspace so that
         several forwards can precede one backward (the reference calls the model 3x before loss.backward(), TM:175-177);
@@ -470,8 +483,16 @@ class Engine:
         task-independent patch embedding in it (`x0`: input cast + patch-embed GEMM + positional term, LVA:232-242), the later
         ones take it from there instead of recomputing it (the reference recomputes it for every task id).
         attn_maps (forward-only calls): {site: destination} for some of attention_sites(cfg) -- each named adapter attention writes
-        its head-averaged softmax there right behind its attention core (shapes: attention_map_shapes)."""
+        its head-averaged softmax there right behind its attention core (shapes: attention_map_shapes).
+        points: the B passes evaluate the gene encoder at B points between a baseline and `genes` and the backward writes the gene
+        INPUT gradient (GenePoints).  stochastic=False runs this call -- a need_grad=True one too -- with every Dropout / DropPath
+        site off, without set_stochastic(): the engine's mode, dropout counters and generation stay (None / True: the engine's mode)."""
         cfg, dev, t = self.cfg, self.device, self.store.tensors
+        drop_now = bool(self.stochastic and need_grad and stochastic is not False)
+        if points is not None:
+            if drop_now:
+                raise ValueError("points: the path points are evaluated with the stochastic sites off (stochastic=False)")
+            self._check_points(points, int(task_onehots.shape[0]))
         if self.store.sync is not None:
             self.store.sync()         # parameters complete on this rank before anything reads them (no-op when nothing is pending)
         if not self._caches_ready:
@@ -502,7 +523,7 @@ class Engine:
                 share.setdefault("_leases", []).append(ws["_lease"])      # (x0 of the first call serves the later calls of the slide)
         tape.grad_enabled = need_grad
         tape.reset()
-        self._drop_now = bool(self.stochastic and need_grad)
+        self._drop_now = drop_now
         self._ext_calls = 0
         if fresh and self._drop_now:     # several forwards may precede one backward (TM:175-177): the masks of a call are
             self._fresh_calls += 1       # tied to the call, not to the device step counter alone
@@ -523,7 +544,7 @@ class Engine:
 
         # ---- token side: gene encoder (one pass when dropout is off, own masks per task pass otherwise) + task token per pass
         # (LVA:257-266)
-        gene = self._gene_encoder(genes, passes=int(task_onehots.shape[0]))  # Var [1, G64, P, D]
+        gene = self._gene_encoder(genes, passes=int(task_onehots.shape[0]), points=points)  # Var [1, G64, P, D]
         c = self._assemble_tokens(gene, task_onehots, clinical)            # Var [B, T, D]
         pe = P("gene_pe")
 
@@ -751,9 +772,24 @@ class Engine:
             raise ValueError("coords outside the slide_ngrids x slide_ngrids positional grid (or not finite) in an earlier slide")
 
     # ------------------------------------------------------------------ token-side pieces
-    def _gene_encoder(self, genes: Sequence[torch.Tensor], passes: int = 1) -> Var:
+    def _check_points(self, points: "GenePoints", B: int):
+        if hasattr(self, "forward_slide"):
+            raise NotImplementedError("input gradients of the TITAN configuration are not supported")
+        if B > ops.GENE_POINTS_MAX:
+            raise ValueError(f"points: at most {ops.GENE_POINTS_MAX} points per engine pass, got {B}")
+        n = self._gene_total
+        for nm, tns, want in (("baseline", points.baseline, n), ("alphas", points.alphas, B), ("weights", points.weights, B),
+                              ("dgenes", points.dgenes, n), ("unscale", points.unscale, 1)):
+            if tns is None and nm in ("baseline", "unscale"):
+                continue
+            if tns is None or tns.dtype != F32 or tns.device.type != self.device.type or not tns.is_contiguous() or tns.numel() != want:
+                raise ValueError(f"points.{nm}: expected a contiguous fp32 tensor of {want} element(s) on {self.device}")
+
+    def _gene_encoder(self, genes: Sequence[torch.Tensor], passes: int = 1, points: Optional[GenePoints] = None) -> Var:
         """GeneEncoder_Group.gene_encode (gene_encoder.py:194-215) of one slide for `passes` task passes: returns the gene tokens
-        [1, G64, P, D] with P = passes in train mode with dropout (own masks per pass), else 1 (shared)."""
+        [1, G64, P, D] with P = passes in train mode with dropout (own masks per pass), else 1 (shared).
+        points (GenePoints): P = passes, pass p at its own point of the path baseline -> genes; the pathway networks' recorded backward
+        is the input gradient into points.dgenes.  The mixer and everything above run the per-pass path that dropout uses."""
         tape, P, g = self.tape, self.store.param, self.cfg.gene
         G = len(self.group_sizes)
         if not torch.is_tensor(genes) and len(genes) != G:
@@ -768,22 +804,39 @@ class Engine:
         # with dropout off the passes are identical and ONE is computed and broadcast.
         gp = float(g.dropout)
         adrop = self._drop(300, gp)
-        Pn = passes if adrop is not None else 1
+        Pn = passes if (adrop is not None or points is not None) else 1
         z = Var(tape.new(1, G, Pn, g.latent_dim))
-        a1, a2 = tape.new(G, g.latent_dim), tape.new(G, Pn, g.latent_dim)
         st = self.store
+        if points is not None:
+            a1, a2 = tape.new(G, Pn, g.latent_dim), tape.new(G, Pn, g.latent_dim)
+            ops.gene_snn_fwd_points(st.flat, self._gene_offs, self._gene_sizes, self._gene_goff, gflat, points.baseline, points.alphas,
+                                    G, g.latent_dim, a1, a2, z.data, Pn)
+
+            def bwd_input():
+                if z.grad is None:
+                    return
+                ops.gene_snn_bwd_input(st.flat, self._gene_offs, self._gene_sizes, self._gene_goff, G, g.latent_dim, a1, a2, z.grad,
+                                       points.weights, points.dgenes, Pn, unscale_dev=points.unscale, accumulate=True)
+            tape.record(bwd_input)
+            return self._gene_mixer(z)
+        a1, a2 = tape.new(G, g.latent_dim), tape.new(G, Pn, g.latent_dim)
         ops.gene_snn_fwd(st.flat, self._gene_offs, self._gene_sizes, self._gene_goff, gflat, G, g.latent_dim, a1, a2, z.data,
                          alpha_drop=adrop, passes=Pn)
-        z0 = z          # (closures bind late: `z` is rebound by the mixer loop below)
 
         fgrad = st.flat_grad      # (bound NOW: the store's gradient side may point elsewhere by the time the backward runs)
 
         def bwd_networks():
-            if z0.grad is None:
+            if z.grad is None:
                 return
             ops.gene_snn_bwd(st.flat, fgrad, self._gene_offs, self._gene_sizes, self._gene_goff, gflat, G, g.latent_dim,
-                             a1, a2, z0.grad, alpha_drop=adrop, passes=Pn)
+                             a1, a2, z.grad, alpha_drop=adrop, passes=Pn)
         tape.record(bwd_networks)
+        return self._gene_mixer(z)
+
+    def _gene_mixer(self, z: Var) -> Var:
+        """MLP-mixer over the pathway outputs z [1, G, P, latent], final norm / projection and pathway_compression: [1, G64, P, D]."""
+        tape, P, g = self.tape, self.store.param, self.cfg.gene
+        gp = float(g.dropout)
         for k in range(g.depth):
             p = f"gene_encoder.mlp_mixer.{k}."
             n1 = tape.layernorm(z, P(p + "0.norm.weight"), P(p + "0.norm.bias"))

@@ -418,6 +418,26 @@ def gene_snn_bwd(params, grads, offs, sizes, goff, genes, G, latent, a1, a2, dz,
 
 
 # Adapter attention cores: `heads` heads of dim `head_dim` (16 / 32 / 64), E = heads * head_dim; the defaults are the shipped 12 x 16.
+GENE_POINTS_MAX = 4      # points (and passes) per launch of the pathway-network kernels (csrc/gene.hip: GP_MAX)
+
+
+def gene_snn_fwd_points(params, offs, sizes, goff, genes, baseline, alphas_dev, G, latent, a1, a2, z, points):
+    """The pathway networks at `points` inputs baseline + alphas_dev[p] (genes - baseline); baseline None = zeros (mt_gene_snn_fwd_points)."""
+    check(_lib.load().mt_gene_snn_fwd_points(_p(params), _p(offs), _p(sizes), _p(goff), _p(genes), _p(baseline), _p(alphas_dev), G, latent,
+                                             points, _p(a1), _p(a2), _p(z), _s()), "gene_snn_fwd_points")
+
+
+def gene_snn_bwd_input(params, offs, sizes, goff, G, latent, a1, a2, dz, weights_dev, dgenes, points, unscale_dev=None, accumulate=True):
+    """dgenes (+)= unscale * the input gradient of the pathway networks, summed over the points with weights_dev (mt_gene_snn_bwd_input)."""
+    check(_lib.load().mt_gene_snn_bwd_input(_p(params), _p(offs), _p(sizes), _p(goff), G, latent, points, _p(a1), _p(a2), _p(dz),
+                                            _p(weights_dev), _p(unscale_dev), _p(dgenes), int(accumulate), _s()), "gene_snn_bwd_input")
+
+
+def ig_finalize(genes, baseline, dgenes, sizes, goff, G, attr, pathway):
+    """attr = (genes - baseline) * dgenes, pathway[i] = its sum over pathway i (mt_ig_finalize)."""
+    check(_lib.load().mt_ig_finalize(_p(genes), _p(baseline), _p(dgenes), _p(sizes), _p(goff), G, _p(attr), _p(pathway), _s()), "ig_finalize")
+
+
 def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None, heads=12, head_dim=16):
     check(_lib.load().mt_inject_attn_fwd_hd(_p(q), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(a), _p(lse), _s()),
           "inject_attn_fwd")
@@ -686,6 +706,8 @@ act_fwd = _timed(lambda x, y, act, n=None: _small(n if n is not None else x.nume
 act_bwd = _timed(lambda x, dy, dx, act, n=None: _small(n if n is not None else x.numel()))(act_bwd)
 gene_snn_fwd = _timed(lambda *a, **k: "token_side")(gene_snn_fwd)
 gene_snn_bwd = _timed(lambda *a, **k: "token_side")(gene_snn_bwd)
+gene_snn_fwd_points = _timed(lambda *a, **k: "token_side")(gene_snn_fwd_points)
+gene_snn_bwd_input = _timed(lambda *a, **k: "token_side")(gene_snn_bwd_input)
 l2norm_row = _timed(lambda *a, **k: "token_side")(l2norm_row)
 distill_loss = _timed(lambda *a, **k: "token_side")(distill_loss)
 
