@@ -75,6 +75,22 @@ int mt_dropout_f32(const float* x, long ldx, const MtRowMap* xmap, float* y, int
 /* in place on rows: x(m,:) *= DropPath factor of pass m / rows_per_pass (token-side residual branches) */
 int mt_droppath_rows_f32(float* x, int M, int D, const MtDropout* drop, mt_stream_t stream);
 
+/* DropPath live table.  A residual branch whose DropPath draw is 0 for a task pass contributes exact zeros for that pass, forward
+ * and backward, so the kernels of the branch may leave the pass out.  mt_droppath_live evaluates the draw of every (site, pass) ON
+ * THE DEVICE -- the host never sees it, a captured graph replays with whatever the rng holds -- and stores, per site i, table[2 i],
+ * table[2 i + 1] = {b0, b1}: the contiguous hull of the live passes (first live pass, last live pass + 1; {0, 0} when none is live;
+ * {0, B} for path_p = 0).  A hull is the exact live set for B <= 2; a dead pass inside it (B = 3, only the middle one dropped) is
+ * computed as if live and discarded by the DropPath factor, as without a table.  path_sites / path_ps: HOST arrays of n <=
+ * MT_LIVE_SITES_MAX entries (MtDropout.path_site / .path_p of the branches); rng as in MtDropout; table: device int[2 n].  Launch it
+ * after the step's mt_rng_advance and before the first consumer; forward and backward read the same table.
+ * The `_live` launchers below take `const int* live` = one site's {b0, b1} (device): work of the passes outside [b0, b1) is not
+ * done and its outputs keep whatever bytes they held -- the consumers of a branch select a dropped pass to 0 and never multiply it
+ * (mt_add_layernorm_fwd, the BIAS_RESID epilogue), and mt_layernorm_bwd_live counts its dy as zero.  live == NULL: every pass is
+ * live, the launcher without the suffix.  Correctness never depends on a pass having been left out. */
+#define MT_LIVE_SITES_MAX 64
+int mt_droppath_live(const unsigned* path_sites, const float* path_ps, int n, int B, const unsigned* rng, int* table,
+                     mt_stream_t stream);
+
 typedef struct {
   const float* bias;           /* [N] or NULL */
   const float* resid;          /* fp32 [*, ldr] (BIAS_RESID, INJECT) */
@@ -94,6 +110,15 @@ typedef struct {
 int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
                    int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap, int out_dtype,
                    mt_stream_t stream);
+/* The same over the rows of the live passes only (live: one entry of a DropPath live table -- mt_droppath_live above --, live_rows rows
+ * per pass; NULL = every row): M_eff = (b1 - b0) * live_rows rows starting at row b0 * live_rows are computed, in row tiles laid from
+ * that row on, and stored; every other row of C keeps its bytes.  A row's result does not depend on where the tiles lie, and whatever
+ * in an epilogue depends on the row (the head-major row of MT_EPI_QKV_HM, row maps) takes the global row: kept rows keep their bits.
+ * For MT_EPI_BIAS and MT_EPI_QKV_HM (the products inside a residual branch); the epilogues that carry the residual stream
+ * (BIAS_RESID, INJECT, POSEMB) run over every row: MT_ERR_UNSUPPORTED with a table. */
+int mt_gemm_nt_f16_live(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
+                        int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap, int out_dtype,
+                        const int* live, int live_rows, mt_stream_t stream);
 
 /* C[N1,N2] (fp32) += sum_m A[m,N1] * B[m,N2] over M rows (split over workgroups, fp32 atomics): the weight
  * gradient of a big-M nn.Linear (autograd of AM:154-164 etc.).  N1 % 64 == 0, N2 % 64 == 0.
@@ -153,6 +178,11 @@ int mt_sgemm_multi(const MtSgemm* probs, int n, mt_stream_t stream);
 int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
                      const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
                      int out_dtype, float* stats, int M, int D, mt_stream_t stream);
+/* mt_layernorm_fwd restricted to the rows of the live passes (live_rows rows per pass): the fp16 GELU form (D = 3072: the FFN's
+ * sub-LayerNorm, a LayerNorm INSIDE a branch); every other form with a table: MT_ERR_UNSUPPORTED */
+int mt_layernorm_fwd_live(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
+                          const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
+                          int out_dtype, float* stats, int M, int D, const int* live, int live_rows, mt_stream_t stream);
 /* h = x + drop(branch) ; y = fp16(LN(h) * w + b): the residual add of a backbone sub-layer (ENC:95-97,121-123 --
  * x = residual stream fp32 [M, D], branch = fp16 output of the out_proj / fc2 GEMM, drop = that branch's Dropout +
  * DropPath, same counters as the BIAS_RESID GEMM epilogue) riding on the LayerNorm that consumes the sum.
@@ -178,6 +208,17 @@ int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dt
                      const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
                      long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
                      mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, mt_stream_t stream);
+
+/* mt_layernorm_bwd with the live table entry of the residual branch this LayerNorm closes (live_rows rows per pass): dy of a row
+ * outside the live passes counts as ZERO whatever its bytes are -- then an accumulating dx passes through unchanged and dx_f16 is
+ * still written, which is what exact-zero dy rows give.  The fp16 GELU form (the FFN's sub-LayerNorm) instead walks the live rows
+ * only and leaves the other rows of dx untouched; the other GELU forms and a trainable norm (dw / db) take no table:
+ * MT_ERR_UNSUPPORTED. */
+int mt_layernorm_bwd_live(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
+                          const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
+                          long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
+                          mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, const int* live, int live_rows,
+                          mt_stream_t stream);
 
 /* ------------------------------------------------------- dilated attention ------------------------- */
 #define MT_MAX_BRANCHES 8
@@ -205,6 +246,10 @@ typedef struct {
 int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br,
                         mt_stream_t stream);
 
+/* the same with a live table entry: workgroups of the passes outside [live[0], live[1]) exit before they touch anything */
+int mt_dilated_attn_fwd_live(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const int* live,
+                             mt_stream_t stream);
+
 /* Branch mix + inner_attn_ln: w_b = softmax_b(lse_b) per (position, head) (constant in backward, DA:132-137),
  * mixed = sum_b w_b O_b, y = LN(mixed) (DA:257-258).  Writes y fp16 [B*N,768], LN stats, and
  * lse_tot = logsumexp_b(lse_b) fp32 [B*N,16] for the backward. */
@@ -216,6 +261,12 @@ int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDila
 int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
                           const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
                           float* delta_br, mt_stream_t stream);
+/* mix forward / backward over the rows of the live passes only */
+int mt_dilated_mix_ln_fwd_live(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
+                               const float* ln_b, mt_half* y, float* stats, float* lse_tot, const int* live, mt_stream_t stream);
+int mt_dilated_mix_ln_bwd_live(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                               const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                               float* delta_br, const int* live, mt_stream_t stream);
 /* The two launchers above with the number of workgroups given (tests and tools only; the results do not depend on it):
  * grid_wgs > 0 = that many workgroups (capped at what the rows need), 0 = the default. */
 int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
@@ -241,6 +292,12 @@ int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* 
  * workspace keeps its size.  What mt_longnet_layer_bwd uses; a plan without a ratio-1 branch takes the workspace form. */
 int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
                                 const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, mt_stream_t stream);
+
+/* the in-place backward over the live passes only (all three phases; a plan without a ratio-1 branch runs the
+ * workspace-form combine over every row: the dqkv rows of a dropped pass then hold undefined values, which no consumer reads) */
+int mt_dilated_attn_bwd_inplace_live(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
+                                     const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, const int* live,
+                                     mt_stream_t stream);
 
 /* ------------------------------------------------- dense attention with 2-D ALiBi (TITAN blocks) ---- */
 /* The attention of the TITAN slide encoder's ViT blocks (titan_adapter.py:253-293 `get_alibi`, :359-361,394
@@ -304,7 +361,10 @@ int mt_pool_attn_bwd(const float* q, const mt_half* kv, const float* scores, con
  * forward: pend_x / pend_branch / pend_drop: the residual stream, fp16 fc2 branch and its dropout of the layer BELOW whose add is
  * still outstanding (hin is then written here) or NULL; defer != 0: leave this layer's fc2 add to the layer above (br16 holds the
  * branch, `out` is not written).  backward: dh (fp32 [M, D]) in / out; dh16_valid: the layer above left fp16(dh) in dh16;
- * feeds_lower: leave fp16(dh) (masked with drop_lower_ffn) for the layer below. */
+ * feeds_lower: leave fp16(dh) (masked with drop_lower_ffn) for the layer below.
+ * live_attn / live_ffn (one pass = plan->N rows): the kernels inside a branch -- its GEMMs (mt_gemm_nt_f16_live), attention, mix, combine,
+ * the FFN's sub-LayerNorm -- leave the dropped passes of the branch out, forward and backward; the kernels that carry the residual
+ * stream (the add + LayerNorm forward, the LayerNorm backward, the cast, the BIAS_RESID product) run over all rows. */
 typedef struct {
   const float *ln1_w, *ln1_b, *inner_ln_w, *inner_ln_b, *ln2_w, *ln2_b, *ffn_ln_w, *ffn_ln_b;
   const float *b_qkv, *b_out, *b_fc1, *b_fc2;
@@ -315,6 +375,7 @@ typedef struct {
   float *hin, *hmid; mt_half *qkv, *o_br; float *lse_br, *lse_tot; mt_half* a1; float *st1, *stin, *st2, *stf;
   mt_half *u16, *br16, *t16;
   float* dh; mt_half *dy16, *dh16, *dt16, *da1, *dmixed, *dqkv16; float* delta; void* attn_ws;
+  const int *live_attn, *live_ffn;   /* live table entries (mt_droppath_live) of the layer's attention / FFN branch, or NULL: all passes */
 } MtLongNetLayerBuffers;
 enum { MT_LAYER_ALL = 0x7fffffff };
 /* forward, in launch order: self_attn_layer_norm (mt_layernorm_fwd; with pend_x: mt_add_layernorm_fwd, which also writes hin) ->

@@ -59,7 +59,7 @@ class MtLongNetLayerWeights(C.Structure):
 
 class MtLongNetLayerBuffers(C.Structure):
     _fields_ = [(n, P) for n in ("hin", "hmid", "qkv", "o_br", "lse_br", "lse_tot", "a1", "st1", "stin", "st2", "stf", "u16", "br16", "t16",
-                                 "dh", "dy16", "dh16", "dt16", "da1", "dmixed", "dqkv16", "delta", "attn_ws")]
+                                 "dh", "dy16", "dh16", "dt16", "da1", "dmixed", "dqkv16", "delta", "attn_ws", "live_attn", "live_ffn")]
 
 
 class MtVitBlockWeights(C.Structure):
@@ -93,6 +93,15 @@ SIGNATURES = {
     "mt_layernorm_fwd_eps": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, F, P],
     "mt_add_layernorm_fwd_eps": [P, P, DR, P, P, P, P, P, I, I, F, P],
     "mt_layernorm_bwd": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P],
+    # DropPath live table and the `_live` twins: the plain form's arguments + (live[, live_rows]) in front of the stream
+    "mt_droppath_live": [P, P, I, I, P, P, P],
+    "mt_gemm_nt_f16_live": [P, L, RM, P, I, I, I, I, EP, P, L, RM, I, P, I, P],
+    "mt_layernorm_fwd_live": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, P, I, P],
+    "mt_layernorm_bwd_live": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P, I, P],
+    "mt_dilated_attn_fwd_live": [P, PL, P, P, P, P],
+    "mt_dilated_mix_ln_fwd_live": [P, P, PL, P, P, P, P, P, P, P],
+    "mt_dilated_mix_ln_bwd_live": [P, P, P, P, PL, P, P, P, P, P, P],
+    "mt_dilated_attn_bwd_inplace_live": [P, P, P, P, PL, P, P, I, P, P],
     "mt_dilated_attn_fwd": [P, PL, P, P, P],
     "mt_dilated_mix_ln_fwd": [P, P, PL, P, P, P, P, P, P],
     "mt_dilated_mix_ln_bwd": [P, P, P, P, PL, P, P, P, P, P],

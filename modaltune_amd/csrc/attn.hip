@@ -21,6 +21,9 @@ namespace {
 // t + 1 is issued at the top of tile t and awaited at its end.  No staging registers, stores or per-tile address
 // arithmetic; the only tile variant is the last one of a sequence whose length is not a multiple of 64.
 // ------------------------------------------------------------------------------------------------
+// LIVE (p.live != nullptr; the launcher picks): without it the kernel is what it was before the live table existed -- no null check of
+// p.live, which costs one more serialised kernel-argument fetch in front of every workgroup
+template <bool LIVE>
 __global__ __launch_bounds__(256) void dilated_attn_fwd_kernel(const h16* __restrict__ qkv, Plan p, h16* __restrict__ o_br,
                                                                float* __restrict__ lse_br) {
   __shared__ __attribute__((aligned(16))) h16 smem[4 * IMG_HALVES];      // K0 | K1 | V0 | V1
@@ -36,7 +39,7 @@ __global__ __launch_bounds__(256) void dilated_attn_fwd_kernel(const h16* __rest
   // made only of padding are not computed -- their sum(P) share is added in closed form after the loop.
   const int nv = __builtin_amdgcn_readfirstlane(sq.nvalid());
   const int nvq = min(nv, p.qlimit[w.br]);                 // entries that act as queries (sequence-parallel plans: a prefix)
-  if (w.qt * 128 >= nvq) return;
+  if (w.qt * 128 >= nvq || (LIVE && pass_dead(p, w.b))) return;      // (a pass DropPath dropped: its output is never read)
 
   // constant chunks of the V images: logical chunk 6 = ones at d = 48 and 52 (O^T row 48 of both lane halves accumulates
   // sum(P)), chunk 7 = zeros; written once (the DMA never touches them)
@@ -276,9 +279,11 @@ __global__ __launch_bounds__(256) void mix_ln_fwd_kernel(const h16* __restrict__
   float w[MIX_CPL], bb[MIX_CPL];
 #pragma unroll
   for (int e = 0; e < MIX_CPL; ++e) { w[e] = ln_w[c0 + e]; bb[e] = ln_b[c0 + e]; }
-  for (long m2 = ((long)blockIdx.x * 4 + wave) * 2; m2 < M; m2 += (long)gridDim.x * 8) {
-    const bool live = m2 + sub < M;
-    const long m = live ? m2 + sub : M - 1;
+  const LivePasses lp = live_passes(p);      // rows of the live passes only
+  const long m_end = min(M, (long)lp.b1 * p.N);
+  for (long m2 = (long)lp.b0 * p.N + ((long)blockIdx.x * 4 + wave) * 2; m2 < m_end; m2 += (long)gridDim.x * 8) {
+    const bool live = m2 + sub < m_end;
+    const long m = live ? m2 + sub : m_end - 1;
     const int pos = (int)(m % p.N);
     bool cov[NB];
     float lse[NB];
@@ -344,9 +349,11 @@ __global__ __launch_bounds__(256) void mix_ln_bwd_kernel(const h16* __restrict__
   float w[MIX_CPL];
 #pragma unroll
   for (int e = 0; e < MIX_CPL; ++e) w[e] = ln_w[c0 + e];
-  for (long m2 = ((long)blockIdx.x * 4 + wave) * 2; m2 < M; m2 += (long)gridDim.x * 8) {
-    const bool live = m2 + sub < M;
-    const long m = live ? m2 + sub : M - 1;
+  const LivePasses lp = live_passes(p);      // rows of the live passes only
+  const long m_end = min(M, (long)lp.b1 * p.N);
+  for (long m2 = (long)lp.b0 * p.N + ((long)blockIdx.x * 4 + wave) * 2; m2 < m_end; m2 += (long)gridDim.x * 8) {
+    const bool live = m2 + sub < m_end;
+    const long m = live ? m2 + sub : m_end - 1;
     const int pos = (int)(m % p.N);
     const float tot = lse_tot[m * H + h];
     const float mean = stats[2 * m], rstd = stats[2 * m + 1];
@@ -407,15 +414,22 @@ __global__ __launch_bounds__(256) void mix_ln_bwd_kernel(const h16* __restrict__
 
 }  // namespace
 
-extern "C" int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br,
-                                   mt_stream_t stream) {
+extern "C" int mt_dilated_attn_fwd_live(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const int* live,
+                                        mt_stream_t stream) {
   if (!qkv || !o_br || !lse_br || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128);
+  const Plan p = make_plan(plan, 128, live);
   const int nblk = p.blk_off[p.nbranch];
-  hipLaunchKernelGGL(dilated_attn_fwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv, p,
+  if (p.live) hipLaunchKernelGGL(dilated_attn_fwd_kernel<true>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv, p,
+                     (h16*)o_br, lse_br);
+  else hipLaunchKernelGGL(dilated_attn_fwd_kernel<false>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv, p,
                      (h16*)o_br, lse_br);
   MT_CHECK_LAUNCH();
   return MT_OK;
+}
+
+extern "C" int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br,
+                                   mt_stream_t stream) {
+  return mt_dilated_attn_fwd_live(qkv, plan, o_br, lse_br, nullptr, stream);
 }
 
 // Grid of the mix kernels: as many workgroups (four waves, a wave = two rows at a time) per CU as a CU holds at once, never more than
@@ -429,11 +443,11 @@ static dim3 mix_grid(long M, int grid_wgs, int wg_per_cu) {
   return dim3((int)min((M + 7) / 8, (long)(grid_wgs > 0 ? grid_wgs : wg_per_cu * MIX_CUS)));
 }
 
-extern "C" int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
-                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
-                                          int grid_wgs, mt_stream_t stream) {
+namespace {
+int mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w, const float* ln_b, mt_half* y,
+               float* stats, float* lse_tot, int grid_wgs, const int* live, mt_stream_t stream) {
   if (!o_br || !lse_br || !ln_w || !ln_b || !y || !stats || !lse_tot || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128);
+  const Plan p = make_plan(plan, 128, live);
   const long M = (long)p.B * p.N;
   const dim3 grid = mix_grid(M, grid_wgs, MIX_FWD_WG_PER_CU);
   if (p.nbranch <= 5)
@@ -445,18 +459,31 @@ extern "C" int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
+}  // namespace
+
+extern "C" int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
+                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
+                                          int grid_wgs, mt_stream_t stream) {
+  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs, nullptr, stream);
+}
 
 extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
                                      const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
                                      mt_stream_t stream) {
-  return mt_dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, stream);
+  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, nullptr, stream);
 }
 
-extern "C" int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                                          float* delta_br, int grid_wgs, mt_stream_t stream) {
+extern "C" int mt_dilated_mix_ln_fwd_live(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
+                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
+                                          const int* live, mt_stream_t stream) {
+  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, live, stream);
+}
+
+namespace {
+int mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot, const MtDilatedPlan* plan,
+               const float* ln_w, const float* stats, mt_half* dmixed, float* delta_br, int grid_wgs, const int* live, mt_stream_t stream) {
   if (!dy || !o_br || !lse_br || !lse_tot || !ln_w || !stats || !dmixed || !delta_br || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128);
+  const Plan p = make_plan(plan, 128, live);
   const long M = (long)p.B * p.N;
   const dim3 grid = mix_grid(M, grid_wgs, MIX_BWD_WG_PER_CU);
   if (p.nbranch <= 5)
@@ -468,11 +495,24 @@ extern "C" int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
+}  // namespace
+
+extern "C" int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                                          float* delta_br, int grid_wgs, mt_stream_t stream) {
+  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, grid_wgs, nullptr, stream);
+}
 
 extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
                                      const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
                                      float* delta_br, mt_stream_t stream) {
-  return mt_dilated_mix_ln_bwd_grid(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, stream);
+  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, nullptr, stream);
+}
+
+extern "C" int mt_dilated_mix_ln_bwd_live(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                                          float* delta_br, const int* live, mt_stream_t stream) {
+  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, live, stream);
 }
 
 extern "C" long mt_dilated_attn_bwd_workspace_bytes(const MtDilatedPlan* plan) {
@@ -483,7 +523,7 @@ extern "C" long mt_dilated_attn_bwd_workspace_bytes(const MtDilatedPlan* plan) {
 
 namespace {
 int attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan,
-             void* workspace, mt_half* dqkv, int phases, bool inplace, mt_stream_t stream) {
+             void* workspace, mt_half* dqkv, int phases, bool inplace, const int* live, mt_stream_t stream) {
   if (!qkv || !dmixed || !lse_tot || !delta_br || !workspace || !dqkv || !plan_ok(plan) || !(phases & 7)) return MT_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   inplace = inplace && dense_branch_host(plan) >= 0;      // (a plan without a ratio-1 branch has nothing to write in place)
@@ -491,10 +531,10 @@ int attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, co
   mt_half* dense_dst = inplace ? dqkv : nullptr;
   // every (branch, position, head) slot of the workspace (in-place form: of dqkv, for the dense branch) is written exactly once
   // by each of the two kernels
-  if (phases & MT_ATTN_BWD_KV) mt_attn::launch_bwd_kv(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, s);
-  if (phases & MT_ATTN_BWD_Q) mt_attn::launch_bwd_q(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, s);
+  if (phases & MT_ATTN_BWD_KV) mt_attn::launch_bwd_kv(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, live, s);
+  if (phases & MT_ATTN_BWD_Q) mt_attn::launch_bwd_q(qkv, dmixed, lse_tot, delta_br, plan, workspace, dense_dst, live, s);
   if (phases & MT_ATTN_BWD_COMBINE) {
-    if (inplace) mt_attn::launch_bwd_combine_inplace(workspace, plan, dqkv, s);
+    if (inplace) mt_attn::launch_bwd_combine_inplace(workspace, plan, dqkv, live, s);
     else mt_attn::launch_bwd_combine(workspace, plan, dqkv, s);
   }
   MT_CHECK_LAUNCH();
@@ -505,11 +545,19 @@ int attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, co
 extern "C" int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
                                    const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
                                    int phases, mt_stream_t stream) {
-  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, false, stream);
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, false, nullptr, stream);
 }
 
 extern "C" int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
                                            const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
                                            int phases, mt_stream_t stream) {
-  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, stream);
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, nullptr, stream);
+}
+
+extern "C" int mt_dilated_attn_bwd_inplace_live(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
+                                                const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
+                                                int phases, const int* live, mt_stream_t stream) {
+  // (a plan without a ratio-1 branch runs the workspace-form combine, which walks every row: the dqkv rows of a dropped pass are then
+  // formed from stale workspace bytes -- like every buffer of the branch they are never read for such a pass)
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, live, stream);
 }

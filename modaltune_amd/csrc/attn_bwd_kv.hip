@@ -17,6 +17,9 @@ namespace {
 // converts per element pair.
 // ------------------------------------------------------------------------------------------------
 // (launch bound: 3 waves per SIMD = 168 VGPRs; the prefetched fragments would otherwise push the kernel to 175 and a wave per SIMD less)
+// LIVE (p.live != nullptr; the launcher picks): without it the kernel is what it was before the live table existed -- no null check of
+// p.live, which costs one more serialised kernel-argument fetch in front of every workgroup
+template <bool LIVE>
 __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* __restrict__ qkv, const h16* __restrict__ dmixed,
                                                                   const float* __restrict__ lse_tot, const float* __restrict__ delta_br,
                                                                   Plan p, h16* __restrict__ ws, DenseDst dd) {
@@ -35,7 +38,7 @@ __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* 
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   // padded keys get no gradient; padded queries read as Q = dO = 0 (range check of the DMA descriptor) and add nothing
   const int nv = __builtin_amdgcn_readfirstlane(sq.nvalid());
-  if (w.qt * 128 >= nv) return;
+  if (w.qt * 128 >= nv || (LIVE && pass_dead(p, w.b))) return;      // (a pass DropPath dropped: its gradient is never read)
 
   {   // the zero columns d = 48..63 (logical chunks 6, 7) of all four images, written once: 4 x 64 x 2 chunks, two per thread
     const int img = tid >> 6, row = tid & 63;
@@ -188,7 +191,8 @@ __global__ __launch_bounds__(256, 3) void dilated_attn_bwd_kv_kernel(const h16* 
 
 }  // namespace
 
-void mt_attn::launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s) {
-  const Plan p = make_plan(plan, 128);
-  hipLaunchKernelGGL(dilated_attn_bwd_kv_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
+void mt_attn::launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, const int* live, hipStream_t s) {
+  const Plan p = make_plan(plan, 128, live);
+  if (p.live) hipLaunchKernelGGL(dilated_attn_bwd_kv_kernel<true>, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
+  else hipLaunchKernelGGL(dilated_attn_bwd_kv_kernel<false>, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
 }

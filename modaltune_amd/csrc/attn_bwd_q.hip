@@ -14,6 +14,9 @@ namespace {
 // The elementwise block is written with packed fp32 ops (v_pk_fma/add/mul_f32): these kernels issue about as many
 // VALU cycles as MFMA cycles, and the two did not overlap (PMC: VALU 49 %, MFMA 37 % busy before this form).
 // ------------------------------------------------------------------------------------------------
+// LIVE (p.live != nullptr; the launcher picks): without it the kernel is what it was before the live table existed -- no null check of
+// p.live, which costs one more serialised kernel-argument fetch in front of every workgroup
+template <bool LIVE>
 __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __restrict__ qkv, const h16* __restrict__ dmixed,
                                                                  const float* __restrict__ lse_tot, const float* __restrict__ delta_br,
                                                                  Plan p, h16* __restrict__ ws, DenseDst dd) {
@@ -31,7 +34,7 @@ __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __re
   // padded queries get no gradient; padded keys have K = 0 and add nothing to dQ: neither is computed
   const int nv = __builtin_amdgcn_readfirstlane(sq.nvalid());
   const int nvq = min(nv, p.qlimit[w.br]);
-  if (w.qt * 128 >= nvq) return;
+  if (w.qt * 128 >= nvq || (LIVE && pass_dead(p, w.b))) return;      // (a pass DropPath dropped: its gradient is never read)
 
   {   // constant chunks 6, 7 (zeros, read as d rows 48..63 of K^T) of both K images; written once
     const int buf = tid >> 7, row = (tid >> 1) & 63, which = 6 + (tid & 1);
@@ -163,7 +166,8 @@ __global__ __launch_bounds__(256) void dilated_attn_bwd_q_kernel(const h16* __re
 
 }  // namespace
 
-void mt_attn::launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s) {
-  const Plan p = make_plan(plan, 128);
-  hipLaunchKernelGGL(dilated_attn_bwd_q_kernel, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
+void mt_attn::launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, const int* live, hipStream_t s) {
+  const Plan p = make_plan(plan, 128, live);
+  if (p.live) hipLaunchKernelGGL(dilated_attn_bwd_q_kernel<true>, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
+  else hipLaunchKernelGGL(dilated_attn_bwd_q_kernel<false>, dim3(p.blk_off[p.nbranch]), dim3(256), 0, s, (const h16*)qkv, (const h16*)dmixed, lse_tot, delta_br, p, (h16*)ws, make_dense_dst(plan, p, dense_dst));
 }

@@ -58,7 +58,9 @@ template <int NB>
 __global__ __launch_bounds__(256) void dilated_attn_bwd_combine_inplace_kernel(const h16* __restrict__ ws, Plan p, int db, h16* dqkv) {
   const long M = (long)p.B * p.N;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (long m = (long)blockIdx.x * 4 + wave; m < M; m += (long)gridDim.x * 4) {
+  const LivePasses lp = live_passes(p);      // rows of the live passes only (the others' gradients are never read)
+  const long m_end = min(M, (long)lp.b1 * p.N);
+  for (long m = (long)lp.b0 * p.N + (long)blockIdx.x * 4 + wave; m < m_end; m += (long)gridDim.x * 4) {
     const int pos = (int)((unsigned)m % (unsigned)p.N);      // (M < 2^31: checked by the caller)
     h16* row = dqkv + m * QKV_LD;
     int lo[NB], hbs[NB], str[NB];
@@ -117,8 +119,8 @@ void mt_attn::launch_bwd_combine(const void* ws, const MtDilatedPlan* plan, mt_h
   hipLaunchKernelGGL(dilated_attn_bwd_combine_kernel, dim3((int)min(M, 16384L)), dim3(192), 0, s, (const h16*)ws, p, (h16*)dqkv);
 }
 
-void mt_attn::launch_bwd_combine_inplace(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, hipStream_t s) {
-  const Plan p = make_plan(plan, 128);
+void mt_attn::launch_bwd_combine_inplace(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, const int* live, hipStream_t s) {
+  const Plan p = make_plan(plan, 128, live);
   const long M = (long)p.B * p.N;
   const int db = dense_branch_host(plan);
   const dim3 grid((int)min((M + 3) / 4, (long)CMB_GRID_MAX));

@@ -30,11 +30,12 @@ struct Plan {
   long ws_off[MT_MAX_BRANCHES + 1];   // backward workspace: per-branch compact, TOKEN-major [pass][token][q|k|v][16 / ratio heads][48] fp16
   float inv_seg[MT_MAX_BRANCHES];     // 1 / seg (position -> segment index without an integer division per row)
   int qlimit[MT_MAX_BRANCHES];        // sparse entries [0, qlimit) act as queries (= n unless sequence-parallel)
+  const int* live;                    // device {b0, b1}: only the passes [b0, b1) are computed (mt_droppath_live), or nullptr = all B
 };
 
-Plan make_plan(const MtDilatedPlan* p, int qtile) {
+Plan make_plan(const MtDilatedPlan* p, int qtile, const int* live = nullptr) {
   Plan d;
-  d.nbranch = p->nbranch; d.N = p->N; d.B = p->B;
+  d.nbranch = p->nbranch; d.N = p->N; d.B = p->B; d.live = live;
   for (int i = 0; i < p->nbranch; ++i) {
     d.seg[i] = p->seg[i]; d.ratio[i] = p->ratio[i]; d.nseg[i] = p->nseg[i]; d.n[i] = p->n[i];
     d.order[i] = i;
@@ -103,6 +104,19 @@ MT_DEVINL WorkItem decode(const Plan& p, int bid) {
   w.h = __builtin_amdgcn_readfirstlane(w.h); w.j = __builtin_amdgcn_readfirstlane(w.j);
   w.b = __builtin_amdgcn_readfirstlane(w.b);
   return w;
+}
+
+// The passes a launch computes: the live hull [b0, b1) of the DropPath draws of its residual branch (include/modaltune_hip.h:
+// mt_droppath_live), clamped to the plan; every pass without a table.  p.live is a kernel argument: two scalar loads.
+struct LivePasses { int b0, b1; };
+MT_DEVINL LivePasses live_passes(const Plan& p) {
+  LivePasses r = {0, p.B};
+  if (p.live) { r.b0 = max(p.live[0], 0); r.b1 = min(p.live[1], p.B); }
+  return r;
+}
+MT_DEVINL bool pass_dead(const Plan& p, int b) {
+  const LivePasses r = live_passes(p);
+  return b < r.b0 || b >= r.b1;
 }
 
 // single-branch launches (backward): same XCD-balanced walk over one branch
@@ -318,12 +332,13 @@ struct StageRow {       // eight lanes per row
 // rebuild one kernel).  mt_dilated_attn_bwd (attn.hip) calls these launchers.
 namespace mt_attn {
 // (C-ABI types only: the device-side Plan lives in each unit's anonymous namespace and has no linkage)
+// live: the branch's live table entry (device {b0, b1}) or nullptr: workgroups / rows of the passes outside [b0, b1) do nothing.
 // dense_dst: where the dense branch's gradients go.  nullptr = its region of the workspace (the workspace form); the dense
 // [B*N, 2304] dqkv = the in-place form: the dense branch's slot of (token, which, head) has exactly the address arithmetic of
 // the dqkv row (ws_slot with 16 heads per `which`), so the epilogues only select another base.  Needs a plan with a dense branch.
-void launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s);
-void launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, hipStream_t s);
+void launch_bwd_kv(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, const int* live, hipStream_t s);
+void launch_bwd_q(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br, const MtDilatedPlan* plan, void* ws, mt_half* dense_dst, const int* live, hipStream_t s);
 void launch_bwd_combine(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, hipStream_t s);
 // in-place form: dqkv already holds the dense branch; adds the sparse branches where they cover a head, touches nothing else
-void launch_bwd_combine_inplace(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, hipStream_t s);
+void launch_bwd_combine_inplace(const void* ws, const MtDilatedPlan* plan, mt_half* dqkv, const int* live, hipStream_t s);
 }  // namespace mt_attn

@@ -141,6 +141,24 @@ MT_DEVINL f32x4 drop_elem4(const DropArgs& d, uint64_t idx4, float pf) {
   }
   return s;
 }
+// v * s with a dropped element SELECTED to 0, never formed as 0 * v: the rows of a pass DropPath dropped may hold stale bytes (the
+// kernels that would have written them skip such a pass, include/modaltune_hip.h: mt_droppath_live), and 0 * NaN is NaN
+MT_DEVINL f32x4 drop_apply4(f32x4 v, f32x4 s) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = s[e] != 0.f ? v[e] * s[e] : 0.f;
+  return v;
+}
+// rows [first, end) of the passes a live table entry names (include/modaltune_hip.h: mt_droppath_live), clamped to the M rows there
+// are (first <= end always); all M rows without a table.  `live` is a kernel argument: two scalar loads.
+struct RowRange { int first, end; };
+MT_DEVINL RowRange live_rows_of(const int* live, int rows_per_pass, int M) {
+  RowRange r = {0, M};
+  if (live) {
+    r.first = (int)min((long)max(live[0], 0) * rows_per_pass, (long)M);
+    r.end = max(r.first, (int)min((long)max(live[1], 0) * rows_per_pass, (long)M));
+  }
+  return r;
+}
 MT_DEVINL f32x4 drop_scale4(const DropArgs& d, uint64_t idx4, int m) {
   return drop_elem4(d, idx4, drop_path_factor(d, m / d.rows_per_pass));
 }

@@ -14,7 +14,8 @@
 #include "common.h"
 
 // gemm_ps.hip: persistent form for the backbone shapes (returns MT_ERR_UNSUPPORTED for shapes it does not serve)
-int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int K, int epilogue, const float* bias, void* C, long ldc, hipStream_t s);
+int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int K, int epilogue, const float* bias, void* C, long ldc,
+                      const int* live, int live_rows, hipStream_t s);
 
 namespace {
 
@@ -40,6 +41,10 @@ struct GemmNtArgs {
   const float* pos_table; const int* pos_row; const int* pos_col;
   void* C; long ldc; RowMap cmap;
   DropArgs drop;          // BIAS_RESID: C = resid + drop(acc + bias)
+  // live table entry (include/modaltune_hip.h: mt_droppath_live) of the branch this product belongs to, live_rows rows per pass, or
+  // nullptr: only the rows of the live passes are computed and stored.  The tile kernels lay their row tiles over the live rows
+  // (tile rows start at the first live row); every row-dependent term of the epilogues takes the GLOBAL row m, as without a table.
+  const int* live; int live_rows;
 };
 
 // LDS-DMA staging (global_load_lds_dwordx4): each wave-instruction drops 64 x 16 B = 1 KiB = 8 tile rows of 128 B
@@ -70,7 +75,7 @@ constexpr int erows_h16(int bm, int csh, int lds_bytes) {
   return e;
 }
 template <int BM, int BN, int WM, int WN, int EPI, int LDS_BYTES>
-MT_DEVINL void gemm_epilogue_h16(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], h16* smem, int m0, int n0) {
+MT_DEVINL void gemm_epilogue_h16(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], h16* smem, int m0, int n0, int m_end) {
   constexpr int NT = WM * WN * 64;
   constexpr int TM = BM / WM, TN = BN / WN, MI = TM / 16, NI = TN / 16;
   constexpr int CSH = BN + 4;
@@ -110,7 +115,7 @@ MT_DEVINL void gemm_epilogue_h16(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16]
 #pragma unroll 4
     for (int rr = r0; rr < EROWS; rr += RPP) {
       const int m = m0 + rbase + rr;
-      if (m >= g.m_end || n >= g.N) continue;
+      if (m >= m_end || n >= g.N) continue;
       const h16x4 lo = *reinterpret_cast<const h16x4*>(&smem[rr * CSH + cc]), hi = *reinterpret_cast<const h16x4*>(&smem[rr * CSH + cc + 4]);
       h16* dst = EPI == MT_EPI_QKV_HM ? C + ((long)(n / 48) * g.M + m) * 48 + (n % 48)      // 8 | 48: chunks never straddle a head
                                       : C + g.cmap.map(m) * g.ldc + n;
@@ -123,10 +128,10 @@ MT_DEVINL void gemm_epilogue_h16(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16]
 }
 
 template <int BM, int BN, int WM, int WN, int EPI, typename OutT, int LDS_BYTES>
-MT_DEVINL void gemm_epilogue(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], h16* smem, int m0, int n0) {
+MT_DEVINL void gemm_epilogue(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], h16* smem, int m0, int n0, int m_end) {
   if constexpr (sizeof(OutT) == 2 && (EPI == MT_EPI_BIAS || EPI == MT_EPI_QKV_HM)) {
     if ((g.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(g.C) & 15) == 0) {      // 16-byte row segments need aligned rows
-      gemm_epilogue_h16<BM, BN, WM, WN, EPI, LDS_BYTES>(g, acc, smem, m0, n0);
+      gemm_epilogue_h16<BM, BN, WM, WN, EPI, LDS_BYTES>(g, acc, smem, m0, n0, m_end);
       return;
     }
   }
@@ -171,13 +176,13 @@ MT_DEVINL void gemm_epilogue(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN 
 #pragma unroll 4
     for (int rr = r0; rr < EROWS; rr += RPP) {
       const int m = m0 + rbase + rr;
-      if (m >= g.m_end || n >= g.N) continue;
+      if (m >= m_end || n >= g.N) continue;
       f32x4 v = *reinterpret_cast<const f32x4*>(&Cs[rr * CS + cc]);
       v += bias4;
       if (EPI == MT_EPI_BIAS_RESID) {
         if (dropping)       // dropout / DropPath of the branch
-          v *= dfast ? drop_elem4(g.drop, ((uint64_t)m * g.N + n) >> 2, m < dsplit ? dpf0 : dpf1)
-                     : drop_scale4(g.drop, ((uint64_t)m * g.N + n) >> 2, m);
+          v = drop_apply4(v, dfast ? drop_elem4(g.drop, ((uint64_t)m * g.N + n) >> 2, m < dsplit ? dpf0 : dpf1)
+                                   : drop_scale4(g.drop, ((uint64_t)m * g.N + n) >> 2, m));
         v += *reinterpret_cast<const f32x4*>(g.resid + g.rmap.map(m) * g.ldr + n);
       }
       if (EPI == MT_EPI_INJECT) {
@@ -206,7 +211,7 @@ MT_DEVINL void gemm_epilogue(const GemmNtArgs& g, f32x4 (&acc)[BM / WM / 16][BN 
 // ping-pong kernel below (8 waves, 128 KB of LDS, one workgroup per CU) for N >= 2304 or K >= 2304.  A K-tile of the 128^2
 // form moves 32 KB for 1024 MFMA cycles per SIMD, i.e. it wants ~134 GB/s per CU from L2 at full MFMA rate against
 // ~70 GB/s deliverable (MI355X_MICROARCH.md, gather into LDS from L2), and it ends every K-tile on a vmcnt(0) + barrier.
-template <int BM, int BN, int WM, int WN, int EPI, typename OutT>
+template <int BM, int BN, int WM, int WN, int EPI, typename OutT, bool LIVE = false>
 __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmNtArgs g) {
   constexpr int NT = WM * WN * 64;              // threads
   constexpr int TM = BM / WM, TN = BN / WN;     // wave tile
@@ -230,7 +235,18 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmNtArgs g) {
     const int q = nwg / 8, r = nwg % 8, x = bid % 8;
     bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
   }
-  const int m0 = g.m_begin + (bid / nbn) * BM, n0 = (bid % nbn) * BN;
+  // LIVE (g.live != nullptr; the launcher picks): tile rows count from the first live row, and a workgroup whose tile lies past the last
+  // live row of this launch leaves here, before its first DMA, LDS write or barrier.  Without it the kernel is what it was before the
+  // table existed: a null check of g.live in front of everything serialises one more kernel-argument fetch per workgroup (4 us on the
+  // 61 us launch of the 128 x 256 tiles, three rounds of workgroups).
+  int m0 = g.m_begin + (bid / nbn) * BM, m_end = g.m_end;
+  if constexpr (LIVE) {
+    const RowRange lr = live_rows_of(g.live, g.live_rows, g.M);
+    m_end = min(g.m_end, lr.end - lr.first);
+    if (m0 >= m_end) return;
+    m0 += lr.first; m_end += lr.first;
+  }
+  const int n0 = (bid % nbn) * BN;
 
   // per-thread DMA sources: chunk id c = i * 256 + tid -> tile row c >> 3, physical chunk c & 7, logical chunk
   // (c & 7) ^ (row & 7); rows past the edge are clamped (their products are never stored)
@@ -293,7 +309,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_nt_kernel(GemmNtArgs g) {
     __syncthreads();
   }
 
-  gemm_epilogue<BM, BN, WM, WN, EPI, OutT, 2 * (BM + BN) * BK * 2>(g, acc, smem, m0, n0);
+  gemm_epilogue<BM, BN, WM, WN, EPI, OutT, 2 * (BM + BN) * BK * 2>(g, acc, smem, m0, n0, m_end);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -321,7 +337,7 @@ template <int N> MT_DEVINL void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)
 MT_DEVINL void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // RH = rows per A half-tile = rows per wave group: 128 (256 x 256 tile) or 64 (128 x 256 tile for the last partial round)
-template <int RH, int EPI, typename OutT>
+template <int RH, int EPI, typename OutT, bool LIVE = false>
 __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNtArgs g) {
   constexpr int BM = 2 * RH, BN = 256, WM = 2, WN = 4;
   constexpr int AH = RH * BK, HALF = 128 * BK;   // halves per A / B half-tile
@@ -339,7 +355,18 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNtArgs g) {
     const int q = nwg / 8, r = nwg % 8, x = bid % 8;
     bid = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + bid / 8;
   }
-  const int m0 = g.m_begin + (bid / nbn) * BM, n0 = (bid % nbn) * BN;
+  // LIVE (g.live != nullptr; the launcher picks): tile rows count from the first live row, and a workgroup whose tile lies past the last
+  // live row of this launch leaves here, before its first DMA, LDS write or barrier.  Without it the kernel is what it was before the
+  // table existed: a null check of g.live in front of everything serialises one more kernel-argument fetch per workgroup (4 us on the
+  // 61 us launch of the 128 x 256 tiles, three rounds of workgroups).
+  int m0 = g.m_begin + (bid / nbn) * BM, m_end = g.m_end;
+  if constexpr (LIVE) {
+    const RowRange lr = live_rows_of(g.live, g.live_rows, g.M);
+    m_end = min(g.m_end, lr.end - lr.first);
+    if (m0 >= m_end) return;
+    m0 += lr.first; m_end += lr.first;
+  }
+  const int n0 = (bid % nbn) * BN;
 
   // DMA pieces: 64 rows x 8 chunks of 16 B per piece (one per thread): row = tid >> 3, physical chunk tid & 7, logical
   // chunk (tid & 7) ^ (row & 7); an A half-tile is AP pieces, a B half-tile 2
@@ -451,14 +478,17 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNtArgs g) {
   MT_STAMP(t2);
   MT_STAMP_ADD(g, 0, t0, t1);
   MT_STAMP_ADD(g, 1, t1, t2);
-  gemm_epilogue<BM, BN, WM, WN, EPI, OutT, 2 * TILE * 2>(g, acc, smem, m0, n0);
+  gemm_epilogue<BM, BN, WM, WN, EPI, OutT, 2 * TILE * 2>(g, acc, smem, m0, n0, m_end);
   MT_STAMP(t3);
   MT_STAMP_ADD(g, 4, t2, t3);
   MT_STAMP_ADD(g, 5, t3 - 1, t3);
 }
 
-template <int BN, int EPI, typename OutT>
+template <int BN, int EPI, typename OutT, bool LIVE = false>
 int launch_nt(const GemmNtArgs& a, hipStream_t s) {
+  if constexpr (!LIVE && (EPI == MT_EPI_BIAS || EPI == MT_EPI_QKV_HM)) {      // (the epilogues a table goes with: mt_gemm_nt_f16_live)
+    if (a.live) return launch_nt<BN, EPI, OutT, true>(a, s);
+  }
   if constexpr (BN == 256) {
     // Ping-pong 256 x 256 tiles, one workgroup per CU.  When the tile count leaves a short last round, the rows of that
     // round are covered by 128 x 256 tiles instead (half the time per tile): e.g. N = 768, M = 30003 is 354 tiles on
@@ -488,11 +518,11 @@ int launch_nt(const GemmNtArgs& a, hipStream_t s) {
     if (force && !strcmp(force, "pp_small")) big_rt = 0;
     GemmNtArgs g1 = a;
     g1.m_begin = 0; g1.m_end = min(a.M, big_rt * 256);
-    if (big_rt > 0) hipLaunchKernelGGL((gemm_nt_pp_kernel<128, EPI, OutT>), dim3(big_rt * nbn), dim3(512), 0, s, g1);
+    if (big_rt > 0) hipLaunchKernelGGL((gemm_nt_pp_kernel<128, EPI, OutT, LIVE>), dim3(big_rt * nbn), dim3(512), 0, s, g1);
     if (g1.m_end < a.M) {
       GemmNtArgs g2 = a;
       g2.m_begin = g1.m_end; g2.m_end = a.M;
-      hipLaunchKernelGGL((gemm_nt_pp_kernel<64, EPI, OutT>), dim3(cdiv(a.M - g1.m_end, 128) * nbn), dim3(512), 0, s, g2);
+      hipLaunchKernelGGL((gemm_nt_pp_kernel<64, EPI, OutT, LIVE>), dim3(cdiv(a.M - g1.m_end, 128) * nbn), dim3(512), 0, s, g2);
     }
     MT_CHECK_LAUNCH();
     return MT_OK;
@@ -500,9 +530,9 @@ int launch_nt(const GemmNtArgs& a, hipStream_t s) {
     constexpr int BM = 128;
     const int nwg = cdiv(a.M, BM) * cdiv(a.N, BN);
     if (BN == 128)
-      hipLaunchKernelGGL((gemm_nt_kernel<BM, 128, 2, 2, EPI, OutT>), dim3(nwg), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((gemm_nt_kernel<BM, 128, 2, 2, EPI, OutT, LIVE>), dim3(nwg), dim3(256), 0, s, a);
     else
-      hipLaunchKernelGGL((gemm_nt_kernel<BM, 64, 4, 1, EPI, OutT>), dim3(nwg), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((gemm_nt_kernel<BM, 64, 4, 1, EPI, OutT, LIVE>), dim3(nwg), dim3(256), 0, s, a);
     MT_CHECK_LAUNCH();
     return MT_OK;
   }
@@ -937,10 +967,12 @@ __global__ __launch_bounds__(256) void sgemm_multi_kernel(SgemmMulti mm) {
 
 }  // namespace
 
-extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
-                              int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
-                              int out_dtype, mt_stream_t stream) {
-  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return MT_ERR_BAD_ARG;
+extern "C" int mt_gemm_nt_f16_live(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
+                                   int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
+                                   int out_dtype, const int* live, int live_rows, mt_stream_t stream) {
+  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
+  // (a table goes with the products INSIDE a branch; the epilogues that carry the residual stream run over every row)
+  if (live && epilogue != MT_EPI_BIAS && epilogue != MT_EPI_QKV_HM) return MT_ERR_UNSUPPORTED;
   if (K % BK != 0 || lda % 8 != 0 || (N % 64) != 0 || (ldc % 4) != 0) return MT_ERR_BAD_ARG;
   if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 7)) return MT_ERR_BAD_ARG;
   if (epi && epi->resid && (((uintptr_t)epi->resid & 15) || (epi->ldr % 4))) return MT_ERR_BAD_ARG;
@@ -948,6 +980,7 @@ extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   a.A = (const h16*)A; a.lda = lda; a.amap = make_rowmap(amap);
   a.W = (const h16*)W; a.M = M; a.N = N; a.K = K;
   a.m_begin = 0; a.m_end = M;
+  a.live = live; a.live_rows = live_rows;
   a.bias = epi ? epi->bias : nullptr;
   a.resid = epi ? epi->resid : nullptr; a.ldr = epi ? epi->ldr : 0;
   a.rmap = make_rowmap(epi ? &epi->rmap : nullptr);
@@ -964,7 +997,7 @@ extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   const char* ps_env = getenv("MT_GEMM_PS");
   if (!(ps_env && ps_env[0] == '0') && !f32 && (epilogue == MT_EPI_BIAS || epilogue == MT_EPI_QKV_HM) && a.amap.seg_rows <= 0 &&
       a.cmap.seg_rows <= 0 && (ldc % 8) == 0 && !((uintptr_t)C & 15) && (epilogue != MT_EPI_QKV_HM || a.bias) && !a.drop.active()) {
-    const int rc = mt_gemm_ps_launch(A, lda, W, M, N, K, epilogue, a.bias, C, ldc, s);
+    const int rc = mt_gemm_ps_launch(A, lda, W, M, N, K, epilogue, a.bias, C, ldc, live, live_rows, s);
     if (rc != MT_ERR_UNSUPPORTED) return rc;
   }
   switch (epilogue) {
@@ -985,6 +1018,12 @@ extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, 
     default:
       return MT_ERR_BAD_ARG;
   }
+}
+
+extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
+                              int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
+                              int out_dtype, mt_stream_t stream) {
+  return mt_gemm_nt_f16_live(A, lda, amap, W, M, N, K, epilogue, epi, C, ldc, cmap, out_dtype, nullptr, 0, stream);
 }
 
 // 64 x 64 tiles and ~1024 workgroups (512 for the small products), a multiple of the 8 XCDs: see mt_gemm_tn_f16

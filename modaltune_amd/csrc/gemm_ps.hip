@@ -52,6 +52,10 @@ struct GemmPsArgs {
   int M, N, K;
   int nbm, nbn;            // tiles along M / N
   int gc;                  // column tiles per group of the tile order (see tile_of)
+  // live table entry of the branch (include/modaltune_hip.h: mt_droppath_live), live_rows rows per pass, or nullptr.  The row tiles are
+  // laid over the live rows [row0, row_end) only: the tile COUNT shrinks (found before the first DMA), the list walk and the ring are as
+  // ever.  A descriptors / C offsets stay global: row = row0 + tile row.
+  const int* live; int live_rows;
 };
 
 #ifdef PS_STAMP      // diagnostic build (tools/experiments/gemm_ps_stamp.py): phase durations of the steady-state slice, wave 0 of every workgroup
@@ -90,13 +94,12 @@ MT_DEVINL __amdgpu_buffer_rsrc_t ps_rsrc(const void* base, unsigned bytes) {
 // Tile order: column tiles in groups of `gc`; inside a group row-major (row tile, then the group's columns).  The tiles in flight on
 // an XCD at one time are a run of this order: with gc * 256 rows of W (gc * K * 512 bytes) instead of all of W they keep hitting the
 // XCD's 4 MB L2, and every A row block is still shared by gc workgroups while it is hot.
-template <typename Args>
-MT_DEVINL void tile_of(const Args& g, int idx, int& mt, int& nt) {
-  const int per = g.nbm * g.gc;
+MT_DEVINL void tile_of(int nbm, int nbn, int gc, int idx, int& mt, int& nt) {
+  const int per = nbm * gc;
   const int cg = idx / per, rem = idx - cg * per;
-  const int w = min(g.gc, g.nbn - cg * g.gc);      // (the last group may be narrower)
+  const int w = min(gc, nbn - cg * gc);      // (the last group may be narrower)
   mt = rem / w;
-  nt = cg * g.gc + (rem - mt * w);
+  nt = cg * gc + (rem - mt * w);
 }
 
 // (all operand / output extents are below 4 GiB: byte offsets are 32-bit, the bases live in buffer descriptors / scalar registers)
@@ -110,7 +113,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
   // ---- this workgroup's tile list: XCD x = blockIdx & 7 owns a contiguous range of the row-major tile order; its workgroups take
   // that range strided by their count, so the tiles in flight on an XCD are neighbours (same A rows, neighbouring W rows in its L2)
-  const int ntiles = g.nbm * g.nbn;
+  // (g.nbm counts the row tiles of all M rows: the grid was sized for them.  Unlike the tile kernels of gemm.hip this kernel has no LIVE
+  // instantiation: the null check of g.live is paid once per PERSISTENT workgroup -- one round of ~100 us, not a prologue per tile and
+  // round -- and a second instantiation of a kernel that sits at the register limit would be one more allocation to keep spill-free.
+  // Measured without a table against the kernel before the table existed: 97.8 against 98.4 us per launch, inside the run-to-run spread.)
+  const RowRange lr = live_rows_of(g.live, g.live_rows, g.M);
+  const int row0 = lr.first, row_end = lr.end;
+  const int nbm = (row_end - row0 + PS_BM - 1) / PS_BM;
+  const int ntiles = nbm * g.nbn;
   const int xcd = blockIdx.x & 7, slot_id = blockIdx.x >> 3, nslot = gridDim.x >> 3;
   const int tq = ntiles / 8, trm = ntiles % 8;
   const int t_begin = xcd * tq + min(xcd, trm), t_count = tq + (xcd < trm ? 1 : 0);
@@ -133,9 +143,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   int d_tile = 0, d_ks = 0;                    // tile (index into my list) and slice of the next DMA group
   auto dma_tile_setup = [&](int t) {
     const int idx = t_begin + slot_id + min(t, my_tiles - 1) * nslot;
-    int mt, nt; tile_of(g, idx, mt, nt);
+    int mt, nt; tile_of(nbm, g.nbn, g.gc, idx, mt, nt);
 #pragma unroll
-    for (int p = 0; p < 3; ++p) voffA[p] = (unsigned)min(mt * PS_BM + wave * 48 + p * 16 + prow, g.M - 1) * lda2 + lchunk * 16;
+    for (int p = 0; p < 3; ++p) voffA[p] = (unsigned)min(row0 + mt * PS_BM + wave * 48 + p * 16 + prow, row_end - 1) * lda2 + lchunk * 16;
     soffW = (unsigned)(nt * PS_BN + wave * 64) * K2;
     soffB = (unsigned)(nt * PS_BN) * 4u;
   };
@@ -336,9 +346,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // the conversions -- left free, the scheduler starts them above the conversions and the allocator has to find 192 more registers.)
     {
       const int idx = t_begin + slot_id + t * nslot;
-      int mt, nt; tile_of(g, idx, mt, nt);
-      const int m = mt * PS_BM + wr * 96 + fq, n = nt * PS_BN + wc * 128 + fr * 8;
-      held_rows_left = g.M - m;
+      int mt, nt; tile_of(nbm, g.nbn, g.gc, idx, mt, nt);
+      const int m = row0 + mt * PS_BM + wr * 96 + fq, n = nt * PS_BN + wc * 128 + fr * 8;
+      held_rows_left = row_end - m;
       held_off = EPI == MT_EPI_QKV_HM ? (unsigned)(((n / 48) * g.M + m) * 48 + n % 48) * 2u
                                        : (unsigned)m * (unsigned)(g.ldc * 2) + (unsigned)n * 2u;
     }
@@ -374,17 +384,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 }  // namespace
 
-int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int K, int epilogue, const float* bias, void* C, long ldc, hipStream_t s);
+int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int K, int epilogue, const float* bias, void* C, long ldc,
+                      const int* live, int live_rows, hipStream_t s);
 #ifdef PS_STAMP
 extern "C" int mt_gemm_ps_set_stamps(void* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(ps_stamp_buf), &buf, sizeof(buf)) == hipSuccess ? 0 : -1; }
 extern "C" int mt_gemm_ps_stamp_launch(const void* A, long lda, const void* W, int M, int N, int K, const float* bias, void* C, long ldc) {
-  return mt_gemm_ps_launch(A, lda, W, M, N, K, MT_EPI_BIAS, bias, C, ldc, nullptr);
+  return mt_gemm_ps_launch(A, lda, W, M, N, K, MT_EPI_BIAS, bias, C, ldc, nullptr, 0, nullptr);
 }
 #endif
 
 // C-ABI-internal entry (called by mt_gemm_nt_f16 in gemm.hip for the shapes this kernel serves).  Returns MT_OK or a negative status.
 int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int K, int epilogue, const float* bias, void* C, long ldc,
-                      hipStream_t s) {
+                      const int* live, int live_rows, hipStream_t s) {
   if (N % 256 != 0 || K % 64 != 0 || K < 768 || M < 256) return MT_ERR_UNSUPPORTED;      // (K >= 768: a tile is at least 24 slices, the drain window is 9)
   static int ncu = 0;
   if (!ncu) {
@@ -394,7 +405,7 @@ int mt_gemm_ps_launch(const void* A, long lda, const void* W, int M, int N, int 
   }
   GemmPsArgs g;
   g.A = (const h16*)A; g.lda = lda; g.W = (const h16*)W; g.bias = bias; g.C = (h16*)C; g.ldc = ldc;
-  g.M = M; g.N = N; g.K = K;
+  g.M = M; g.N = N; g.K = K; g.live = live; g.live_rows = live_rows;
   g.nbm = cdiv(M, PS_BM); g.nbn = N / PS_BN;
   {
     const char* e = getenv("MT_GEMM_GC");      // experiments: column tiles per group of the tile order (0 / unset: the default below)

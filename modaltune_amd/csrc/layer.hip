@@ -34,20 +34,22 @@ extern "C" int mt_longnet_layer_fwd(const MtLongNetLayerWeights* w, const MtLong
   else
     MT_STEP(MT_LNF_LN1, mt_add_layernorm_fwd(pend_x, pend_branch, pend_drop, w->ln1_w, w->ln1_b, b->hin, b->u16, b->st1, M, D, s));
   MtGemmEpilogue e = epi_bias(w->b_qkv);
-  MT_STEP(MT_LNF_QKV, mt_gemm_nt_f16(b->u16, D, nullptr, w->w_qkv, M, 3 * D, D, MT_EPI_QKV_HM, &e, b->qkv, 3 * D, nullptr, MT_OUT_F16, s));
-  MT_STEP(MT_LNF_ATTN, mt_dilated_attn_fwd(b->qkv, plan, b->o_br, b->lse_br, s));
-  MT_STEP(MT_LNF_MIX, mt_dilated_mix_ln_fwd(b->o_br, b->lse_br, plan, w->inner_ln_w, w->inner_ln_b, b->u16, b->stin, b->lse_tot, s));
+  MT_STEP(MT_LNF_QKV, mt_gemm_nt_f16_live(b->u16, D, nullptr, w->w_qkv, M, 3 * D, D, MT_EPI_QKV_HM, &e, b->qkv, 3 * D, nullptr, MT_OUT_F16, b->live_attn,
+                                          plan->N, s));
+  MT_STEP(MT_LNF_ATTN, mt_dilated_attn_fwd_live(b->qkv, plan, b->o_br, b->lse_br, b->live_attn, s));
+  MT_STEP(MT_LNF_MIX, mt_dilated_mix_ln_fwd_live(b->o_br, b->lse_br, plan, w->inner_ln_w, w->inner_ln_b, b->u16, b->stin, b->lse_tot, b->live_attn, s));
   e = epi_bias(w->b_out);
-  MT_STEP(MT_LNF_OUT, mt_gemm_nt_f16(b->u16, D, nullptr, w->w_out, M, D, D, MT_EPI_BIAS, &e, b->br16, D, nullptr, MT_OUT_F16, s));
+  MT_STEP(MT_LNF_OUT, mt_gemm_nt_f16_live(b->u16, D, nullptr, w->w_out, M, D, D, MT_EPI_BIAS, &e, b->br16, D, nullptr, MT_OUT_F16, b->live_attn, plan->N, s));
   MT_STEP(MT_LNF_LN2, mt_add_layernorm_fwd(b->hin, b->br16, drop_attn, w->ln2_w, w->ln2_b, b->hmid, b->u16, b->st2, M, D, s));
   e = epi_bias(w->b_fc1);
-  MT_STEP(MT_LNF_FC1, mt_gemm_nt_f16(b->u16, D, nullptr, w->w_fc1, M, F, D, MT_EPI_BIAS, &e, b->a1, F, nullptr, MT_OUT_F16, s));
+  MT_STEP(MT_LNF_FC1, mt_gemm_nt_f16_live(b->u16, D, nullptr, w->w_fc1, M, F, D, MT_EPI_BIAS, &e, b->a1, F, nullptr, MT_OUT_F16, b->live_ffn, plan->N, s));
   MT_STEP(MT_LNF_FFN_LN,
-          mt_layernorm_fwd(b->a1, F, nullptr, MT_OUT_F16, 1, w->ffn_ln_w, w->ffn_ln_b, nullptr, 0, b->t16, F, nullptr, MT_OUT_F16, b->stf, M, F, s));
+          mt_layernorm_fwd_live(b->a1, F, nullptr, MT_OUT_F16, 1, w->ffn_ln_w, w->ffn_ln_b, nullptr, 0, b->t16, F, nullptr, MT_OUT_F16, b->stf, M, F,
+                                b->live_ffn, plan->N, s));
   e = epi_bias(w->b_fc2);
   if (defer) {
-    MT_STEP(MT_LNF_FC2, mt_gemm_nt_f16(b->t16, F, nullptr, w->w_fc2, M, D, F, MT_EPI_BIAS, &e, b->br16, D, nullptr, MT_OUT_F16, s));
-  } else {
+    MT_STEP(MT_LNF_FC2, mt_gemm_nt_f16_live(b->t16, F, nullptr, w->w_fc2, M, D, F, MT_EPI_BIAS, &e, b->br16, D, nullptr, MT_OUT_F16, b->live_ffn, plan->N, s));
+  } else {      // (the BIAS_RESID form carries the residual stream: every row, the epilogue selects a dropped pass to 0)
     e.resid = b->hmid; e.ldr = D;
     if (drop_ffn) e.drop = *drop_ffn;
     MT_STEP(MT_LNF_FC2, mt_gemm_nt_f16(b->t16, F, nullptr, w->w_fc2, M, D, F, MT_EPI_BIAS_RESID, &e, out, D, nullptr, MT_OUT_F32, s));
@@ -65,20 +67,24 @@ extern "C" int mt_longnet_layer_bwd(const MtLongNetLayerWeights* w, const MtLong
     MT_STEP(MT_LNB_CAST, mt_cast_f32_to_f16(b->dh, b->dy16, (long)M * D, drop_ffn, D, s));
     src16 = b->dy16;
   }
-  MT_STEP(MT_LNB_FC2, mt_gemm_nt_f16(src16, D, nullptr, w->wt_fc2, M, F, D, MT_EPI_BIAS, &none, b->dt16, F, nullptr, MT_OUT_F16, s));
-  MT_STEP(MT_LNB_FFN_LN, mt_layernorm_bwd(b->dt16, F, nullptr, MT_OUT_F16, b->a1, F, nullptr, MT_OUT_F16, 1, w->ffn_ln_w, b->stf, b->da1, F,
-                                          nullptr, MT_OUT_F16, 0, nullptr, nullptr, nullptr, nullptr, M, F, s));
-  MT_STEP(MT_LNB_FC1, mt_gemm_nt_f16(b->da1, F, nullptr, w->wt_fc1, M, D, F, MT_EPI_BIAS, &none, b->dy16, D, nullptr, MT_OUT_F16, s));
-  MT_STEP(MT_LNB_LN2, mt_layernorm_bwd(b->dy16, D, nullptr, MT_OUT_F16, b->hmid, D, nullptr, MT_OUT_F32, 0, w->ln2_w, b->st2, b->dh, D, nullptr,
-                                       MT_OUT_F32, 1, nullptr, nullptr, b->dh16, drop_attn, M, D, s));
-  MT_STEP(MT_LNB_OUT, mt_gemm_nt_f16(b->dh16, D, nullptr, w->wt_out, M, D, D, MT_EPI_BIAS, &none, b->u16, D, nullptr, MT_OUT_F16, s));
-  MT_STEP(MT_LNB_MIX, mt_dilated_mix_ln_bwd(b->u16, b->o_br, b->lse_br, b->lse_tot, plan, w->inner_ln_w, b->stin, b->dmixed, b->delta, s));
-  MT_STEP(MT_ATTN_BWD_ALL << MT_LNB_ATTN_SHIFT, mt_dilated_attn_bwd_inplace(b->qkv, b->dmixed, b->lse_tot, b->delta, plan, b->attn_ws, b->dqkv16,
-                                                                    (steps >> MT_LNB_ATTN_SHIFT) & MT_ATTN_BWD_ALL, s));
-  MT_STEP(MT_LNB_QKV, mt_gemm_nt_f16(b->dqkv16, 3 * D, nullptr, w->wt_qkv, M, D, 3 * D, MT_EPI_BIAS, &none, b->dy16, D, nullptr, MT_OUT_F16, s));
-  MT_STEP(MT_LNB_LN1, mt_layernorm_bwd(b->dy16, D, nullptr, MT_OUT_F16, b->hin, D, nullptr, MT_OUT_F32, 0, w->ln1_w, b->st1, b->dh, D, nullptr,
-                                       MT_OUT_F32, 1, nullptr, nullptr, feeds_lower ? b->dh16 : nullptr,
-                                       feeds_lower ? drop_lower_ffn : nullptr, M, D, s));
+  MT_STEP(MT_LNB_FC2, mt_gemm_nt_f16_live(src16, D, nullptr, w->wt_fc2, M, F, D, MT_EPI_BIAS, &none, b->dt16, F, nullptr, MT_OUT_F16, b->live_ffn, plan->N, s));
+  // (the live_* entries: the kernels of a branch -- its GEMMs included -- leave its dropped passes out; the LayerNorm backward that closes
+  // the branch reads their stale dy as zero)
+  MT_STEP(MT_LNB_FFN_LN, mt_layernorm_bwd_live(b->dt16, F, nullptr, MT_OUT_F16, b->a1, F, nullptr, MT_OUT_F16, 1, w->ffn_ln_w, b->stf, b->da1, F,
+                                               nullptr, MT_OUT_F16, 0, nullptr, nullptr, nullptr, nullptr, M, F, b->live_ffn, plan->N, s));
+  MT_STEP(MT_LNB_FC1, mt_gemm_nt_f16_live(b->da1, F, nullptr, w->wt_fc1, M, D, F, MT_EPI_BIAS, &none, b->dy16, D, nullptr, MT_OUT_F16, b->live_ffn, plan->N, s));
+  MT_STEP(MT_LNB_LN2, mt_layernorm_bwd_live(b->dy16, D, nullptr, MT_OUT_F16, b->hmid, D, nullptr, MT_OUT_F32, 0, w->ln2_w, b->st2, b->dh, D, nullptr,
+                                            MT_OUT_F32, 1, nullptr, nullptr, b->dh16, drop_attn, M, D, b->live_ffn, plan->N, s));
+  MT_STEP(MT_LNB_OUT, mt_gemm_nt_f16_live(b->dh16, D, nullptr, w->wt_out, M, D, D, MT_EPI_BIAS, &none, b->u16, D, nullptr, MT_OUT_F16, b->live_attn, plan->N, s));
+  MT_STEP(MT_LNB_MIX, mt_dilated_mix_ln_bwd_live(b->u16, b->o_br, b->lse_br, b->lse_tot, plan, w->inner_ln_w, b->stin, b->dmixed, b->delta,
+                                                 b->live_attn, s));
+  MT_STEP(MT_ATTN_BWD_ALL << MT_LNB_ATTN_SHIFT, mt_dilated_attn_bwd_inplace_live(b->qkv, b->dmixed, b->lse_tot, b->delta, plan, b->attn_ws, b->dqkv16,
+                                                                         (steps >> MT_LNB_ATTN_SHIFT) & MT_ATTN_BWD_ALL, b->live_attn, s));
+  MT_STEP(MT_LNB_QKV, mt_gemm_nt_f16_live(b->dqkv16, 3 * D, nullptr, w->wt_qkv, M, D, 3 * D, MT_EPI_BIAS, &none, b->dy16, D, nullptr, MT_OUT_F16, b->live_attn,
+                                          plan->N, s));
+  MT_STEP(MT_LNB_LN1, mt_layernorm_bwd_live(b->dy16, D, nullptr, MT_OUT_F16, b->hin, D, nullptr, MT_OUT_F32, 0, w->ln1_w, b->st1, b->dh, D, nullptr,
+                                            MT_OUT_F32, 1, nullptr, nullptr, feeds_lower ? b->dh16 : nullptr,
+                                            feeds_lower ? drop_lower_ffn : nullptr, M, D, b->live_attn, plan->N, s));
   return MT_OK;
 }
 

@@ -25,6 +25,7 @@ struct LnFwdArgs {
   void* y; long ldy; RowMap ymap;
   float* stats; int M;
   float eps;
+  const int* live; int live_rows;      // ln_gelu_fwd_kernel: only the rows of the passes [live[0], live[1]) (live_rows rows each); nullptr = all
 };
 
 template <int D, typename InT, typename OutT, bool GELU>
@@ -109,7 +110,8 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(AddLnArgs a) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int col = c * 256 + lane * 4;
-      if (dropping) bv[c] *= drop_elem4(a.drop, ((uint64_t)m * D + col) >> 2, pf);
+      // (a dropped pass -- wave-uniform -- is selected to 0, not multiplied by it: its branch rows may never have been written)
+      if (dropping) bv[c] = pf != 0.f ? bv[c] * drop_elem4(a.drop, ((uint64_t)m * D + col) >> 2, pf) : (f32x4){0.f, 0.f, 0.f, 0.f};
       v[c] += bv[c];
       Vec4<float>::store(hrow + col, v[c]);
       s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
@@ -139,11 +141,16 @@ struct LnBwdArgs {
   const float* w; const float* stats;
   void* dx; long lddx; RowMap dxmap; int accumulate;
   float* dw; float* db; h16* dx16; DropArgs drop16; int M;
+  // live table entry of the residual branch this LayerNorm closes, live_rows rows per pass (nullptr = every pass is live).
+  // ln_bwd_kernel: dy of a row outside the live passes counts as zero (its bytes are stale); ln_gelu_bwd_kernel walks the live rows only
+  const int* live; int live_rows;
 };
 
 // DET (deterministic mode, det_reduce.hip): a.dw is the partial workspace [gridDim.x][2][D]; workgroup blockIdx.x stores its dw | db
 // sums to slot blockIdx.x with plain stores
-template <int D, typename DyT, typename InT, typename DxT, bool GELU, bool PARAM, bool DET = false>
+// LIVE (a.live != nullptr; the launcher picks): without it the kernel is what it was before the live table existed -- a null check of
+// a.live at the top cost a serialized kernel-argument fetch per wave, 5 % of this two-rows-per-wave kernel inside the step.
+template <int D, typename DyT, typename InT, typename DxT, bool GELU, bool PARAM, bool DET = false, bool LIVE = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   constexpr int NC = D / 256;
   constexpr int NP = PARAM ? NC : 1;
@@ -160,6 +167,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
     const float mean = a.stats[2 * (long)m], rstd = a.stats[2 * (long)m + 1];
     f32x4 xh[NC], g[NC], raw[GELU ? NC : 1];
     float s1 = 0.f, s2 = 0.f;
+    // LIVE: dy of a row outside the live passes is masked to +0 bit by bit behind an UNCONDITIONAL load (a `dead ? 0 : load` select
+    // makes hipcc branch around every load and wait for each one separately: 7 - 25 % on this kernel inside the step).  The table is read
+    // in the loop, behind the row's first loads (the compiler barrier keeps it there): read in front of the loop, every wave would wait
+    // for it before it issues anything.
+    uint32_t keep = 0xFFFFFFFFu;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int col = c * 256 + lane * 4;
@@ -169,7 +181,16 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) xv[e] = gelu_erf(xv[e]);
       }
-      const f32x4 d = Vec4<DyT>::load(dy + col);
+      f32x4 d = Vec4<DyT>::load(dy + col);
+      if constexpr (LIVE) {
+        if (c == 0) {
+          asm volatile("" ::: "memory");
+          const RowRange lr = live_rows_of(a.live, a.live_rows, a.M);      // (clamped like every other reader of the table)
+          keep = (m >= lr.first && m < lr.end) ? 0xFFFFFFFFu : 0u;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = __uint_as_float(__float_as_uint(d[e]) & keep);
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         xh[c][e] = (xv[e] - mean) * rstd;
@@ -272,7 +293,7 @@ MT_DEVINL void ldf8(const float* p, f32x2 (&o)[4]) {
 
 // Two waves per row (a lane owns D / 128 columns in chunks of 8): ~100 VGPRs, 4-5 waves per SIMD of loads in flight.
 // Row statistics cross the wave pair through LDS.
-template <int D>
+template <int D, bool LIVE = false>
 __global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(LnFwdArgs a) {
   constexpr int NC = D / 1024;   // 8-element chunks per lane
   __shared__ float red[2][4];
@@ -281,10 +302,11 @@ __global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(LnFwdArgs a) {
   f32x2 wr[NC][4], br[NC][4];
 #pragma unroll
   for (int c = 0; c < NC; ++c) { ldf8(a.w + col0 + c * 512, wr[c]); ldf8(a.b + col0 + c * 512, br[c]); }
-  for (int base = blockIdx.x * 2; base < a.M; base += gridDim.x * 2) {
+  const RowRange lr = live_rows_of(LIVE ? a.live : nullptr, a.live_rows, a.M);      // (uniform over the workgroup: the barriers below stay aligned)
+  for (int base = lr.first + blockIdx.x * 2; base < lr.end; base += gridDim.x * 2) {
     const int m = base + rsel;
-    const bool valid = m < a.M;
-    const int mc = valid ? m : a.M - 1;
+    const bool valid = m < lr.end;
+    const int mc = valid ? m : lr.end - 1;
     const h16* x = reinterpret_cast<const h16*>(a.x) + a.xmap.map(mc) * a.ldx;
     h16x8 raw[NC];
 #pragma unroll
@@ -328,7 +350,7 @@ __global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(LnFwdArgs a) {
 }
 
 // backward: WPR waves per row (a lane owns D / (64 WPR) columns in chunks of 8), one row per workgroup iteration
-template <int D, int WPR>
+template <int D, int WPR, bool LIVE = false>
 __global__ __launch_bounds__(64 * WPR) void ln_gelu_bwd_kernel(LnBwdArgs a) {
   constexpr int NC = D / (512 * WPR);
   static_assert(NC * 512 * WPR == D, "row must split into 8-element chunks over the waves");
@@ -339,7 +361,8 @@ __global__ __launch_bounds__(64 * WPR) void ln_gelu_bwd_kernel(LnBwdArgs a) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) ldf8(a.w + col0 + c * 512, wr[c]);
   int it = 0;
-  for (int m = blockIdx.x; m < a.M; m += gridDim.x, it ^= 1) {
+  const RowRange lr = live_rows_of(LIVE ? a.live : nullptr, a.live_rows, a.M);      // (uniform over the workgroup: one barrier per row, as before)
+  for (int m = lr.first + blockIdx.x; m < lr.end; m += gridDim.x, it ^= 1) {
     const h16* dy = reinterpret_cast<const h16*>(a.dy) + a.dymap.map(m) * a.lddy;
     const h16* x = reinterpret_cast<const h16*>(a.x) + a.xmap.map(m) * a.ldx;
     h16x8 rx[NC], rd[NC];
@@ -402,11 +425,13 @@ template <int D>
 int ln_fwd_types(const LnFwdArgs& a, int in_dt, int out_dt, int gelu, hipStream_t s) {
   if constexpr (D % 1024 == 0) {
     if (gelu && in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16 && !a.add_rows && !(a.ldx & 7) && !(a.ldy & 7)) {
-      hipLaunchKernelGGL((ln_gelu_fwd_kernel<D>), dim3(ln_gelu_grid(a.M)), dim3(256), 0, s, a);
+      if (a.live) hipLaunchKernelGGL((ln_gelu_fwd_kernel<D, true>), dim3(ln_gelu_grid(a.M)), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((ln_gelu_fwd_kernel<D>), dim3(ln_gelu_grid(a.M)), dim3(256), 0, s, a);
       MT_CHECK_LAUNCH();
       return MT_OK;
     }
   }
+  if (a.live) return MT_ERR_UNSUPPORTED;      // (only the form above walks a live range)
   if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, float, h16>(a, gelu, s);
   if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F32) return ln_fwd_dispatch<D, float, float>(a, gelu, s);
   if (in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, h16, h16>(a, gelu, s);
@@ -433,6 +458,8 @@ int ln_bwd_launch(const LnBwdArgs& a, hipStream_t s, bool det = false) {
     } else {
       return MT_ERR_UNSUPPORTED;
     }
+  } else if (a.live) {
+    hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, false, false, true>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
   } else {
     hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, false>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
   }
@@ -471,6 +498,22 @@ __global__ void droppath_rows_kernel(float* x, int M, int D, DropArgs d) {
     Vec4<float>::store(x + (long)m * D + c, v);
   }
 }
+// live table (include/modaltune_hip.h: mt_droppath_live): thread i evaluates the B draws of site i and stores their hull
+struct LiveSites { int n; unsigned site[MT_LIVE_SITES_MAX]; float p[MT_LIVE_SITES_MAX]; };
+__global__ void droppath_live_kernel(LiveSites ls, int B, const uint32_t* rng, int* table) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ls.n) return;
+  DropArgs d;
+  d.rng = rng; d.site = 0; d.p = 0.f; d.path_site = ls.site[i]; d.path_p = ls.p[i]; d.rows_per_pass = 1;
+  int b0 = 0, b1 = 0;
+  for (int b = 0; b < B; ++b)
+    if (drop_path_factor(d, b) != 0.f) {
+      if (b1 == 0) b0 = b;
+      b1 = b + 1;
+    }
+  table[2 * i] = b0; table[2 * i + 1] = b1;
+}
+
 __global__ void rng_advance_kernel(uint32_t* rng) { if (threadIdx.x == 0 && blockIdx.x == 0) rng[2] += 1u; }
 
 __global__ void cast_f32_f16_kernel(const float* x, h16* y, long n) {
@@ -641,12 +684,12 @@ int ew_grid(long n) { return (int)max(1L, min((n + 1023) / 1024, 4096L)); }
 
 }  // namespace
 
-extern "C" int mt_layernorm_fwd_eps(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
-                                    const float* w, const float* b, const float* add_rows, int add_period, void* y,
-                                    long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D, float eps,
-                                    mt_stream_t stream) {
-  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || !(eps > 0.f)) return MT_ERR_BAD_ARG;
-  LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M, eps};
+static int ln_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* b,
+                  const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
+                  float eps, const int* live, int live_rows, mt_stream_t stream) {
+  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || !(eps > 0.f) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
+  LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M, eps,
+              live, live_rows};
   hipStream_t s = (hipStream_t)stream;
   switch (D) {
     case 256: return ln_fwd_types<256>(a, in_dtype, out_dtype, gelu_in, s);
@@ -657,12 +700,26 @@ extern "C" int mt_layernorm_fwd_eps(const void* x, long ldx, const MtRowMap* xma
   }
 }
 
+extern "C" int mt_layernorm_fwd_eps(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
+                                    const float* w, const float* b, const float* add_rows, int add_period, void* y,
+                                    long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D, float eps,
+                                    mt_stream_t stream) {
+  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, eps, nullptr, 0, stream);
+}
+
 extern "C" int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
                                 const float* w, const float* b, const float* add_rows, int add_period, void* y,
                                 long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
                                 mt_stream_t stream) {
-  return mt_layernorm_fwd_eps(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, 1e-5f,
-                              stream);
+  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, 1e-5f, nullptr, 0, stream);
+}
+
+extern "C" int mt_layernorm_fwd_live(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
+                                     const float* w, const float* b, const float* add_rows, int add_period, void* y,
+                                     long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
+                                     const int* live, int live_rows, mt_stream_t stream) {
+  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, 1e-5f, live, live_rows,
+                stream);
 }
 
 extern "C" int mt_add_layernorm_fwd_eps(const float* x, const mt_half* branch, const MtDropout* drop, const float* w,
@@ -688,11 +745,13 @@ static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int
     if constexpr (D % 1024 == 0) {
       if (dyh && inh && dxh && !a.dw && !(a.lddy & 7) && !(a.ldx & 7) && !(a.lddx & 7)) {
         constexpr int WPR = (D % 1536 == 0) ? 3 : 2;        // 3072 -> three waves per row (16 columns per lane)
-        hipLaunchKernelGGL((ln_gelu_bwd_kernel<D, WPR>), dim3(min(a.M, 16384)), dim3(64 * WPR), 0, s, a);
+        if (a.live) hipLaunchKernelGGL((ln_gelu_bwd_kernel<D, WPR, true>), dim3(min(a.M, 16384)), dim3(64 * WPR), 0, s, a);
+        else hipLaunchKernelGGL((ln_gelu_bwd_kernel<D, WPR>), dim3(min(a.M, 16384)), dim3(64 * WPR), 0, s, a);
         MT_CHECK_LAUNCH();
         return MT_OK;
       }
     }
+    if (a.live) return MT_ERR_UNSUPPORTED;      // (a GELU input means a LayerNorm INSIDE a branch: only the form above walks a live range)
     if (dyh && inh && dxh) return ln_bwd_launch<D, h16, h16, h16, true>(a, s, det);
     return MT_ERR_UNSUPPORTED;
   }
@@ -702,15 +761,16 @@ static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int
   return MT_ERR_UNSUPPORTED;
 }
 
-extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
-                                long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
-                                const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
-                                int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
-                                int D, mt_stream_t stream) {
-  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db)) return MT_ERR_BAD_ARG;
+extern "C" int mt_layernorm_bwd_live(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
+                                     long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
+                                     const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
+                                     int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
+                                     int D, const int* live, int live_rows, mt_stream_t stream) {
+  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
   if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
+  if (live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
   LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate, dw, db,
-              (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M};
+              (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M, live, live_rows};
   hipStream_t s = (hipStream_t)stream;
   switch (D) {
     case 256: return ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
@@ -719,6 +779,15 @@ extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap
     case 3072: return ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
     default: return MT_ERR_UNSUPPORTED;
   }
+}
+
+extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
+                                long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
+                                const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
+                                int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
+                                int D, mt_stream_t stream) {
+  return mt_layernorm_bwd_live(dy, lddy, dymap, dy_dtype, x, ldx, xmap, in_dtype, gelu_in, w, stats, dx, lddx, dxmap, dx_dtype, accumulate,
+                               dw, db, dx_f16, dx_f16_drop, M, D, nullptr, 0, stream);
 }
 
 // ---- deterministic twins (det_reduce.hip): partials = [slots][2][D] for dw | db, slots = workgroups of the PARAM form
@@ -770,6 +839,16 @@ extern "C" int mt_cast_f32_to_f16(const float* x, mt_half* y, long n, const MtDr
 extern "C" int mt_rng_advance(unsigned* rng, mt_stream_t stream) {
   if (!rng) return MT_ERR_BAD_ARG;
   hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rng);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+extern "C" int mt_droppath_live(const unsigned* path_sites, const float* path_ps, int n, int B, const unsigned* rng, int* table,
+                                mt_stream_t stream) {
+  if (!path_sites || !path_ps || !rng || !table || n < 1 || n > MT_LIVE_SITES_MAX || B < 1) return MT_ERR_BAD_ARG;
+  LiveSites ls;
+  ls.n = n;
+  for (int i = 0; i < MT_LIVE_SITES_MAX; ++i) { ls.site[i] = i < n ? path_sites[i] : 0u; ls.p[i] = i < n ? path_ps[i] : 0.f; }
+  hipLaunchKernelGGL(droppath_live_kernel, dim3(1), dim3(MT_LIVE_SITES_MAX), 0, (hipStream_t)stream, ls, B, rng, table);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }

@@ -234,6 +234,8 @@ class Engine:
         dpr = np.linspace(0.0, float(cfg.drop_path_rate), cfg.depth) if cfg.depth > 1 else np.zeros(1)
         self._layer_path_p = [float(v) for v in dpr]          # ENC:37-41
         self.leaf_stream = os.environ.get("MT_LEAF_STREAM", "0") == "1"
+        # backbone kernels leave out the task passes DropPath dropped (_live_table); MT_DROPPATH_SKIP=0: every pass is computed
+        self.droppath_skip = os.environ.get("MT_DROPPATH_SKIP", "1") != "0"
         self._side, self._side_refs, self._side_busy = None, [], False
         if self.deterministic and self.leaf_stream:
             raise ValueError(self._LEAF_DET)
@@ -291,6 +293,21 @@ class Engine:
             return None, None
         p, pp = float(self.cfg.dropout), self._layer_path_p[l]
         return (self._drop(16 + 4 * l, p, 17 + 4 * l, pp, N), self._drop(18 + 4 * l, p, 19 + 4 * l, pp, N))
+
+    def _live_table(self, ws, B: int):
+        """The DropPath live table of this forward call (include/modaltune_hip.h: mt_droppath_live): row 2 l / 2 l + 1 = the live pass
+        range of layer l's attention / FFN branch (the path sites of _layer_drops), written by ONE launch on the call's stream -- behind
+        the step's rng_advance, inside a captured graph, never read by the host.  It lives in the call's workspace store: concurrent
+        pass groups each have their store and their site group.  None (every kernel computes every pass) without DropPath, with
+        droppath_skip off, or for an engine whose workspace has no table."""
+        depth = self.cfg.depth
+        if not (self._drop_now and self.droppath_skip) or "live" not in ws or 2 * depth > ops.LIVE_SITES_MAX \
+                or not any(p > 0.0 for p in self._layer_path_p):
+            return None
+        off = self._site_base
+        ops.droppath_live([s + 4 * l + off for l in range(depth) for s in (17, 19)],
+                          [self._layer_path_p[l] for l in range(depth) for _ in range(2)], B, self.rng, ws["live"])
+        return ws["live"]
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, state, strict=True):
@@ -450,6 +467,7 @@ class Engine:
             sp[nm] = (H16, (M, Fd))
         sp["dh"] = (F32, (M, D)); sp["delta"] = (F32, (nb, M, 16)); sp["dqkv16"] = (H16, (M, 3 * D))
         sp["scratch32"] = (F32, (Mp, D))
+        sp["live"] = (torch.int32, (2 * cfg.depth, 2))      # DropPath live table of the store's forward call (_live_table)
         plan = ops.make_plan(branch_table(N, self.seg_lengths, DILATED_RATIOS), N, B)
         sp["attn_ws"] = (H16, (ops.dilated_attn_bwd_workspace_bytes(plan) // 2,))
         if self.deterministic:
@@ -530,6 +548,7 @@ class Engine:
         self._site_base = 4096 * (self._fresh_calls & 0xFFFFF) if fresh else 1024 * int(site_group)
         self._ctx = dict(B=B, L=L, N=N, M=M, Mp=Mp, ws=ws)
         self._ctx["plan"] = self._attention_plan(N, B)
+        self._ctx["live"] = self._live_table(ws, B)
         P = self.store.param
         patch_map = rowmap(L, N, 1)     # patch rows of a [B, N, D] buffer
         self._ctx["patch_map"] = patch_map
@@ -1002,13 +1021,15 @@ class Engine:
         # from the layer above -- LN backward's second output)
         feeds_lower = all(l != a for a, _ in cfg.interaction_indexes)
         d_lower_ffn = self._layer_drops(l - 1, N_tok)[1] if feeds_lower else None
-        cb = ws.get(("_cb", l))
+        live = ctx.get("live")          # (this call's DropPath live table, or None: the pointers stay null = every pass)
+        cb = ws.get(("_cb", l, live is not None))
         if cb is None:
-            cb = ws[("_cb", l)] = ops.struct_of(
+            cb = ws[("_cb", l, live is not None)] = ops.struct_of(
                 ops.MtLongNetLayerBuffers, hin=ws[f"hin{l}"], hmid=ws[f"hmid{l}"], qkv=ws[f"qkv{l}"], o_br=ws[f"obr{l}"], lse_br=ws[f"lsebr{l}"],
                 lse_tot=ws[f"lsetot{l}"], a1=ws[f"a1_{l}"], st1=ws[f"st1_{l}"], stin=ws[f"stin_{l}"], st2=ws[f"st2_{l}"], stf=ws[f"stf_{l}"],
                 u16=ws["u16"], br16=ws["br16"], t16=ws["t16"], dh=ws["dh"], dy16=ws["dy16"], dh16=ws["dh16"], dt16=ws["dt16"],
-                da1=ws["da1"], dmixed=ws["dmixed"], dqkv16=ws["dqkv16"], delta=ws["delta"], attn_ws=ws["attn_ws"])
+                da1=ws["da1"], dmixed=ws["dmixed"], dqkv16=ws["dqkv16"], delta=ws["delta"], attn_ws=ws["attn_ws"],
+                live_attn=live[2 * l] if live is not None else None, live_ffn=live[2 * l + 1] if live is not None else None)
         lw = self._layer_w[l]
         # one C call per direction: csrc/layer.hip holds the launch list
         ops.longnet_layer_fwd(lw, cb, plan, M, D, Fd, out, pend=pend, defer=defer, drop_attn=d_attn, drop_ffn=d_ffn)

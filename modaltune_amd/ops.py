@@ -76,8 +76,9 @@ def _dr(d):
 
 
 def gemm_nt(A, W, out, M, N, K, *, lda=None, amap=None, ldc=None, cmap=None, epilogue=EPI_BIAS, bias=None, resid=None,
-            ldr=0, rmap=None, colscale=None, pos_table=None, pos_row=None, pos_col=None, drop=None):
-    """out = epilogue(A[M,K] @ W[N,K]^T) (include/modaltune_hip.h: mt_gemm_nt_f16)."""
+            ldr=0, rmap=None, colscale=None, pos_table=None, pos_row=None, pos_col=None, drop=None, live=None, live_rows=0):
+    """out = epilogue(A[M,K] @ W[N,K]^T) (include/modaltune_hip.h: mt_gemm_nt_f16; with `live`: mt_gemm_nt_f16_live, only the rows of
+    the live passes are computed and stored)."""
     epi = MtGemmEpilogue()
     if drop is not None:
         epi.drop = drop
@@ -89,6 +90,10 @@ def gemm_nt(A, W, out, M, N, K, *, lda=None, amap=None, ldc=None, cmap=None, epi
     epi.pos_table = pos_table.data_ptr() if pos_table is not None else None
     epi.pos_row = pos_row.data_ptr() if pos_row is not None else None
     epi.pos_col = pos_col.data_ptr() if pos_col is not None else None
+    if live is not None:
+        check(_lib.load().mt_gemm_nt_f16_live(_p(A), lda if lda is not None else K, _rm(amap), _p(W), M, N, K, epilogue, C.byref(epi), _p(out),
+                                              ldc if ldc is not None else N, _rm(cmap), _dt(out), _p(live), int(live_rows), _s()), "gemm_nt_live")
+        return
     check(_lib.load().mt_gemm_nt_f16(_p(A), lda if lda is not None else K, _rm(amap), _p(W), M, N, K, epilogue,
                                      C.byref(epi), _p(out), ldc if ldc is not None else N, _rm(cmap), _dt(out), _s()),
           "gemm_nt")
@@ -164,7 +169,14 @@ def sgemm(A, a_str, B, b_str, Cm, c_str, M, N, K, **k):
 
 
 def layernorm_fwd(x, w, b, y, stats, M, D, *, ldx=None, xmap=None, ldy=None, ymap=None, gelu_in=False, add_rows=None,
-                  add_period=0, eps=1e-5):
+                  add_period=0, eps=1e-5, live=None, live_rows=0):
+    if live is not None:      # (the reference's epsilon only: the FFN sub-LayerNorm of the LongNet layers)
+        if eps != 1e-5:
+            raise ValueError("layernorm_fwd: a live table goes with the default eps")
+        check(_lib.load().mt_layernorm_fwd_live(_p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(b),
+                                                _p(add_rows), add_period, _p(y), ldy if ldy is not None else D, _rm(ymap), _dt(y),
+                                                _p(stats), M, D, _p(live), int(live_rows), _s()), "layernorm_fwd_live")
+        return
     check(_lib.load().mt_layernorm_fwd_eps(_p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(b),
                                            _p(add_rows), add_period, _p(y), ldy if ldy is not None else D, _rm(ymap), _dt(y),
                                            _p(stats), M, D, float(eps), _s()), "layernorm_fwd")
@@ -177,31 +189,57 @@ def add_layernorm_fwd(x, branch, w, b, h, y, stats, M, D, drop=None, eps=1e-5):
 
 
 def layernorm_bwd(dy, x, w, stats, dx, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None, dxmap=None,
-                  gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None, det=None):
+                  gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None, det=None, live=None, live_rows=0):
+    if live is not None and dw is not None:
+        raise ValueError("layernorm_bwd: a live table goes with a frozen norm (dw / db of a trainable one sum over every row)")
     if det is not None and dw is not None:      # (a frozen norm reduces nothing over workgroups: the default launcher is deterministic)
         check(_lib.load().mt_layernorm_bwd_det(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x),
                                                ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats),
                                                _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate),
                                                _p(dw), _p(db), _p(dx16), _dr(dx16_drop), M, D, *_det(det), _s()), "layernorm_bwd_det")
         return
-    check(_lib.load().mt_layernorm_bwd(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x),
-                                       ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats),
-                                       _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate),
-                                       _p(dw), _p(db), _p(dx16), _dr(dx16_drop), M, D, _s()), "layernorm_bwd")
+    args = (_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in),
+            _p(w), _p(stats), _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate), _p(dw), _p(db), _p(dx16),
+            _dr(dx16_drop), M, D)
+    if live is None:
+        check(_lib.load().mt_layernorm_bwd(*args, _s()), "layernorm_bwd")
+    else:
+        check(_lib.load().mt_layernorm_bwd_live(*args, _p(live), int(live_rows), _s()), "layernorm_bwd_live")
 
 
-def dilated_attn_fwd(qkv, plan, o_br, lse_br):
-    check(_lib.load().mt_dilated_attn_fwd(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _s()), "dilated_attn_fwd")
+LIVE_SITES_MAX = 64      # MT_LIVE_SITES_MAX
 
 
-def dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot):
-    check(_lib.load().mt_dilated_mix_ln_fwd(_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats),
-                                            _p(lse_tot), _s()), "dilated_mix_ln_fwd")
+# `live` (here and below): one site's {b0, b1} of a DropPath live table (droppath_live; int32 tensor of 2), None = every pass
+def droppath_live(path_sites, path_ps, B, rng, table):
+    """table[i] = {b0, b1}: hull of the task passes whose DropPath draw at site path_sites[i] (rate path_ps[i]) is live; evaluated on
+    the device from `rng` (include/modaltune_hip.h: mt_droppath_live).  table: int32 [len(path_sites), 2]."""
+    n = len(path_sites)
+    check(_lib.load().mt_droppath_live((C.c_uint * n)(*path_sites), (C.c_float * n)(*path_ps), n, B, _p(rng), _p(table), _s()),
+          "droppath_live")
 
 
-def dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br):
-    check(_lib.load().mt_dilated_mix_ln_bwd(_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats),
-                                            _p(dmixed), _p(delta_br), _s()), "dilated_mix_ln_bwd")
+def dilated_attn_fwd(qkv, plan, o_br, lse_br, live=None):
+    if live is None:
+        check(_lib.load().mt_dilated_attn_fwd(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _s()), "dilated_attn_fwd")
+    else:
+        check(_lib.load().mt_dilated_attn_fwd_live(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _p(live), _s()), "dilated_attn_fwd_live")
+
+
+def dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, live=None):
+    args = (_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats), _p(lse_tot))
+    if live is None:
+        check(_lib.load().mt_dilated_mix_ln_fwd(*args, _s()), "dilated_mix_ln_fwd")
+    else:
+        check(_lib.load().mt_dilated_mix_ln_fwd_live(*args, _p(live), _s()), "dilated_mix_ln_fwd_live")
+
+
+def dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, live=None):
+    args = (_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats), _p(dmixed), _p(delta_br))
+    if live is None:
+        check(_lib.load().mt_dilated_mix_ln_bwd(*args, _s()), "dilated_mix_ln_bwd")
+    else:
+        check(_lib.load().mt_dilated_mix_ln_bwd_live(*args, _p(live), _s()), "dilated_mix_ln_bwd_live")
 
 
 def dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs=0):
@@ -236,11 +274,14 @@ def dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqk
     _dilated_attn_bwd_phase(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases)
 
 
-def dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases=ATTN_BWD_ALL):
+def dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases=ATTN_BWD_ALL, live=None):
     """The form the layer launcher uses: the dense (ratio 1) branch is written straight into dqkv16 by the KV and Q phases, the
     COMBINE phase (once, after both) adds the sparse branches in place.  Equal inputs give the dqkv16 of dilated_attn_bwd."""
-    check(_lib.load().mt_dilated_attn_bwd_inplace(_p(qkv), _p(dmixed), _p(lse_tot), _p(delta_br), C.byref(plan), _p(workspace),
-                                                  _p(dqkv16), phases, _s()), "dilated_attn_bwd_inplace")
+    args = (_p(qkv), _p(dmixed), _p(lse_tot), _p(delta_br), C.byref(plan), _p(workspace), _p(dqkv16), phases)
+    if live is None:
+        check(_lib.load().mt_dilated_attn_bwd_inplace(*args, _s()), "dilated_attn_bwd_inplace")
+    else:
+        check(_lib.load().mt_dilated_attn_bwd_inplace_live(*args, _p(live), _s()), "dilated_attn_bwd_inplace_live")
 
 
 def dilated_attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16):
