@@ -37,6 +37,21 @@ typedef enum {
  * copies of AM:492,501-510, and broadcast one slide to the 3 task passes (seg_stride = 0). */
 typedef struct { int seg_rows, seg_stride, row0; } MtRowMap;
 
+/* The optional inputs of a launcher, passed as `const MtLaunchOpts* opt` directly in front of `stream`.  opt == NULL or a zeroed struct: the
+ * default form.  Each launcher that takes one says which fields it honours; a set field it does not honour -- or a combination it does
+ * not serve -- returns MT_ERR_UNSUPPORTED, it is never ignored.  The options are checked before anything else. */
+typedef struct {
+  float eps;             /* LayerNorm forward epsilon; 0 = the reference's 1e-5 (negative / NaN: MT_ERR_BAD_ARG) */
+  const int* live;       /* one entry {b0, b1} of a DropPath live table (device; mt_droppath_live), or NULL: every pass */
+  int live_rows;         /* rows per pass, for launchers without a plan (GEMM, LayerNorm); the dilated-attention
+                            launchers take it from the plan and ignore it */
+  float* partials;       /* deterministic form: the caller's partial workspace (sized by mt_<name>_det_elems), or NULL: default form */
+  long partials_elems;
+  int grid_wgs;          /* mix kernels, tests and tools only: number of workgroups, 0 = default */
+} MtLaunchOpts;
+
+/* major * 100 + minor * 10.  3.0: the optional inputs of a launcher travel in MtLaunchOpts; the suffixed twin entries (_eps, _det, _grid,
+ * _live) of 2.x are gone, so a 2.x caller does not link against this library. */
 int mt_version(void);
 const char* mt_status_string(int status);
 /* Build provenance: sha256 (hex) over the kernel sources, this header and the compiler flags the library was built from
@@ -83,10 +98,10 @@ int mt_droppath_rows_f32(float* x, int M, int D, const MtDropout* drop, mt_strea
  * computed as if live and discarded by the DropPath factor, as without a table.  path_sites / path_ps: HOST arrays of n <=
  * MT_LIVE_SITES_MAX entries (MtDropout.path_site / .path_p of the branches); rng as in MtDropout; table: device int[2 n].  Launch it
  * after the step's mt_rng_advance and before the first consumer; forward and backward read the same table.
- * The `_live` launchers below take `const int* live` = one site's {b0, b1} (device): work of the passes outside [b0, b1) is not
+ * The launchers that honour MtLaunchOpts.live take one site's {b0, b1} (device): work of the passes outside [b0, b1) is not
  * done and its outputs keep whatever bytes they held -- the consumers of a branch select a dropped pass to 0 and never multiply it
- * (mt_add_layernorm_fwd, the BIAS_RESID epilogue), and mt_layernorm_bwd_live counts its dy as zero.  live == NULL: every pass is
- * live, the launcher without the suffix.  Correctness never depends on a pass having been left out. */
+ * (mt_add_layernorm_fwd, the BIAS_RESID epilogue), and mt_layernorm_bwd with a table counts its dy as zero.  live == NULL: every pass
+ * is live.  Correctness never depends on a pass having been left out. */
 #define MT_LIVE_SITES_MAX 64
 int mt_droppath_live(const unsigned* path_sites, const float* path_ps, int n, int B, const unsigned* rng, int* table,
                      mt_stream_t stream);
@@ -107,27 +122,26 @@ typedef struct {
  * Replaces every big-M nn.Linear on the path: PatchEmbed.proj (SE:52-56), q/k/v/out_proj (DA:169-171,260),
  * fc1/fc2 (FFN:134,140), adapter q_proj/output_proj/k|v projections (AM:154-164,221-231), and — with a
  * pre-transposed weight — the activation-gradient (dX) GEMMs of the frozen backbone. */
+/* opt: live.  With a table the product runs over the rows of the live passes only (live_rows rows per pass): M_eff = (b1 - b0) * live_rows
+ * rows starting at row b0 * live_rows are computed, in row tiles laid from that row on, and stored; every other row of C keeps its bytes.
+ * A row's result does not depend on where the tiles lie, and whatever in an epilogue depends on the row (the head-major row of
+ * MT_EPI_QKV_HM, row maps) takes the global row: kept rows keep their bits.  For MT_EPI_BIAS and MT_EPI_QKV_HM (the products inside a
+ * residual branch); the epilogues that carry the residual stream (BIAS_RESID, INJECT, POSEMB) run over every row: MT_ERR_UNSUPPORTED
+ * with a table. */
 int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
                    int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap, int out_dtype,
-                   mt_stream_t stream);
-/* The same over the rows of the live passes only (live: one entry of a DropPath live table -- mt_droppath_live above --, live_rows rows
- * per pass; NULL = every row): M_eff = (b1 - b0) * live_rows rows starting at row b0 * live_rows are computed, in row tiles laid from
- * that row on, and stored; every other row of C keeps its bytes.  A row's result does not depend on where the tiles lie, and whatever
- * in an epilogue depends on the row (the head-major row of MT_EPI_QKV_HM, row maps) takes the global row: kept rows keep their bits.
- * For MT_EPI_BIAS and MT_EPI_QKV_HM (the products inside a residual branch); the epilogues that carry the residual stream
- * (BIAS_RESID, INJECT, POSEMB) run over every row: MT_ERR_UNSUPPORTED with a table. */
-int mt_gemm_nt_f16_live(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
-                        int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap, int out_dtype,
-                        const int* live, int live_rows, mt_stream_t stream);
+                   const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* C[N1,N2] (fp32) += sum_m A[m,N1] * B[m,N2] over M rows (split over workgroups, fp32 atomics): the weight
  * gradient of a big-M nn.Linear (autograd of AM:154-164 etc.).  N1 % 64 == 0, N2 % 64 == 0.
- * colsum (fp32 [N1], or NULL): colsum[n] += sum_m A[m,n] on the same pass -- the bias gradient of that nn.Linear. */
+ * colsum (fp32 [N1], or NULL): colsum[n] += sum_m A[m,n] on the same pass -- the bias gradient of that nn.Linear.
+ * opt: partials (the deterministic forms at the end of this header; ldc >= N2 then). */
 int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb, const MtRowMap* bmap,
-                   int M, int N1, int N2, float* C, long ldc, float* colsum, mt_stream_t stream);
+                   int M, int N1, int N2, float* C, long ldc, float* colsum, const MtLaunchOpts* opt, mt_stream_t stream);
 
-/* out[n] (fp32) += sum_m A[m,n]: bias gradient of a big-M nn.Linear.  N % 8 == 0, lda % 8 == 0 (16-byte loads). */
-int mt_colsum_f16(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, mt_stream_t stream);
+/* out[n] (fp32) += sum_m A[m,n]: bias gradient of a big-M nn.Linear.  N % 8 == 0, lda % 8 == 0 (16-byte loads).  opt: partials. */
+int mt_colsum_f16(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, const MtLaunchOpts* opt,
+                  mt_stream_t stream);
 
 /* Generic small strided fp32 GEMM for the token-side ops (T <= 66 rows; gene encoder GE:194-223, prompt
  * self-attention projections AM:81-94, extractor FFN AM:284-287, fusion head LVA:343-347), forward and
@@ -171,54 +185,39 @@ typedef struct {
 int mt_sgemm_multi(const MtSgemm* probs, int n, mt_stream_t stream);
 
 /* ------------------------------------------------------------- LayerNorm --------------------------- */
-/* y = LN(f(x)) * w + b over the last dim D (eps 1e-5), one wave per row; stats (mean, rstd) saved per row.
+/* y = LN(f(x)) * w + b over the last dim D, one wave per row; stats (mean, rstd) saved per row.
  * f = identity or erf-GELU computed in fp32 (FFN:136 forces the activation to fp32, then FFN:138 ffn_layernorm).
  * in_dtype/out_dtype: MT_OUT_F16 / MT_OUT_F32.  D in {256, 768, 2304, 3072}.  `add_rows` (fp32 [add_period, D],
- * or NULL) is added AFTER the affine: LN(c) + pe as in AM:218,227 (with_pos_embed on normed memory). */
+ * or NULL) is added AFTER the affine: LN(c) + pe as in AM:218,227 (with_pos_embed on normed memory).
+ * opt: eps, live.  eps: the default is the reference's 1e-5 (ENC / AM / GE LayerNorms); the TITAN ViT's LayerNorms carry their own, e.g.
+ * timm's 1e-6 (the backward needs none: it reads the saved rstd).  live (live_rows rows per pass): only the rows of the live passes, for
+ * the fp16 GELU form (D = 3072: the FFN's sub-LayerNorm, a LayerNorm INSIDE a branch); every other form with a table:
+ * MT_ERR_UNSUPPORTED. */
 int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
                      const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
-                     int out_dtype, float* stats, int M, int D, mt_stream_t stream);
-/* mt_layernorm_fwd restricted to the rows of the live passes (live_rows rows per pass): the fp16 GELU form (D = 3072: the FFN's
- * sub-LayerNorm, a LayerNorm INSIDE a branch); every other form with a table: MT_ERR_UNSUPPORTED */
-int mt_layernorm_fwd_live(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
-                          const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
-                          int out_dtype, float* stats, int M, int D, const int* live, int live_rows, mt_stream_t stream);
+                     int out_dtype, float* stats, int M, int D, const MtLaunchOpts* opt, mt_stream_t stream);
 /* h = x + drop(branch) ; y = fp16(LN(h) * w + b): the residual add of a backbone sub-layer (ENC:95-97,121-123 --
  * x = residual stream fp32 [M, D], branch = fp16 output of the out_proj / fc2 GEMM, drop = that branch's Dropout +
  * DropPath, same counters as the BIAS_RESID GEMM epilogue) riding on the LayerNorm that consumes the sum.
- * h (fp32, != x) receives the new residual stream, stats the (mean, rstd) rows.  D = 768. */
+ * h (fp32, != x) receives the new residual stream, stats the (mean, rstd) rows.  D = 768.  opt: eps. */
 int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const MtDropout* drop, const float* w, const float* b,
-                         float* h, mt_half* y, float* stats, int M, int D, mt_stream_t stream);
-
-/* The same two launchers with an explicit epsilon (the entries above use the reference's 1e-5, ENC / AM / GE LayerNorms; the
- * TITAN ViT's LayerNorms carry their own `eps`, e.g. timm's 1e-6).  The backward needs no epsilon: it reads the saved rstd. */
-int mt_layernorm_fwd_eps(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
-                         const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
-                         int out_dtype, float* stats, int M, int D, float eps, mt_stream_t stream);
-int mt_add_layernorm_fwd_eps(const float* x, const mt_half* branch, const MtDropout* drop, const float* w, const float* b,
-                             float* h, mt_half* y, float* stats, int M, int D, float eps, mt_stream_t stream);
+                         float* h, mt_half* y, float* stats, int M, int D, const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* dx (+)= LN backward.  dy fp16 or fp32 [M,D]; x as in forward (gelu_in: also backprop through the GELU).
  * dx_dtype F32 with accumulate=1 adds into the fp32 residual-gradient stream (ENC:137-154 backward);
  * dw/db (fp32 [D], atomically accumulated) may be NULL for frozen norms (selective backward).
  * dx_f16 (dense fp16 [M,D], or NULL): a second, half-precision copy of the final dx -- the operand of the next dX GEMM
  * of the frozen layer below, written here instead of by a separate cast pass over the fp32 stream; dx_f16_drop (or
- * NULL): the dropout / DropPath mask of the residual branch that GEMM differentiates, applied to the copy only. */
+ * NULL): the dropout / DropPath mask of the residual branch that GEMM differentiates, applied to the copy only.
+ * opt: live, partials (not both: MT_ERR_UNSUPPORTED).  live = the table entry of the residual branch this LayerNorm closes (live_rows
+ * rows per pass): dy of a row outside the live passes counts as ZERO whatever its bytes are -- then an accumulating dx passes through
+ * unchanged and dx_f16 is still written, which is what exact-zero dy rows give.  The fp16 GELU form (the FFN's sub-LayerNorm) instead
+ * walks the live rows only and leaves the other rows of dx untouched; the other GELU forms and a trainable norm (dw / db) take no
+ * table: MT_ERR_UNSUPPORTED.  partials: the deterministic form (end of this header), dw and db required. */
 int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
                      const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
                      long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
-                     mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, mt_stream_t stream);
-
-/* mt_layernorm_bwd with the live table entry of the residual branch this LayerNorm closes (live_rows rows per pass): dy of a row
- * outside the live passes counts as ZERO whatever its bytes are -- then an accumulating dx passes through unchanged and dx_f16 is
- * still written, which is what exact-zero dy rows give.  The fp16 GELU form (the FFN's sub-LayerNorm) instead walks the live rows
- * only and leaves the other rows of dx untouched; the other GELU forms and a trainable norm (dw / db) take no table:
- * MT_ERR_UNSUPPORTED. */
-int mt_layernorm_bwd_live(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
-                          const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
-                          long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
-                          mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, const int* live, int live_rows,
-                          mt_stream_t stream);
+                     mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* ------------------------------------------------------- dilated attention ------------------------- */
 #define MT_MAX_BRANCHES 8
@@ -242,38 +241,24 @@ typedef struct {
  * frozen q_proj weight and bias before rounding them to fp16, so no kernel multiplies by it and q is rounded once.
  * For every branch, every (segment, head): O_b = softmax(Q K^T / sqrt(48)) V over the head's dilated positions, zero-padded rows acting as keys with
  * logit 0 / value 0 (DA:98-101,24-28).  o_br: fp16 [nbranch][B*N, 768]; lse_br: fp32 [nbranch][B*N, 16]
- * (natural log).  (position, head) pairs a branch does not visit are left untouched.  DA:212-253, MHA:109-119. */
-int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br,
+ * (natural log).  (position, head) pairs a branch does not visit are left untouched.  DA:212-253, MHA:109-119.
+ * opt: live -- workgroups of the passes outside [live[0], live[1]) exit before they touch anything. */
+int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const MtLaunchOpts* opt,
                         mt_stream_t stream);
-
-/* the same with a live table entry: workgroups of the passes outside [live[0], live[1]) exit before they touch anything */
-int mt_dilated_attn_fwd_live(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const int* live,
-                             mt_stream_t stream);
 
 /* Branch mix + inner_attn_ln: w_b = softmax_b(lse_b) per (position, head) (constant in backward, DA:132-137),
  * mixed = sum_b w_b O_b, y = LN(mixed) (DA:257-258).  Writes y fp16 [B*N,768], LN stats, and
- * lse_tot = logsumexp_b(lse_b) fp32 [B*N,16] for the backward. */
+ * lse_tot = logsumexp_b(lse_b) fp32 [B*N,16] for the backward.
+ * opt (both mix launchers): live -- the rows of the live passes only; grid_wgs (tests and tools only; the results do not depend on it)
+ * > 0 = that many workgroups, capped at what the rows need. */
 int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
-                          const float* ln_b, mt_half* y, float* stats, float* lse_tot, mt_stream_t stream);
+                          const float* ln_b, mt_half* y, float* stats, float* lse_tot, const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* Backward of mix + inner_attn_ln: given dy (fp16, gradient wrt the LN output) recomputes mixed, writes
  * dmixed fp16 HEAD-MAJOR [16][B*N][48] and delta_br[b][row][head] = sum_d dmixed * O_b (fp32). */
 int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
                           const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                          float* delta_br, mt_stream_t stream);
-/* mix forward / backward over the rows of the live passes only */
-int mt_dilated_mix_ln_fwd_live(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
-                               const float* ln_b, mt_half* y, float* stats, float* lse_tot, const int* live, mt_stream_t stream);
-int mt_dilated_mix_ln_bwd_live(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                               const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                               float* delta_br, const int* live, mt_stream_t stream);
-/* The two launchers above with the number of workgroups given (tests and tools only; the results do not depend on it):
- * grid_wgs > 0 = that many workgroups (capped at what the rows need), 0 = the default. */
-int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w,
-                               const float* ln_b, mt_half* y, float* stats, float* lse_tot, int grid_wgs, mt_stream_t stream);
-int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                               const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                               float* delta_br, int grid_wgs, mt_stream_t stream);
+                          float* delta_br, const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* Flash-style backward of all branches: dqkv fp16 [B*N, 2304] (overwritten) from qkv, dmixed, lse_tot, delta_br.  The q
  * columns of dqkv are the gradient with respect to the PRE-SCALED q' (what the dX GEMM through the scaled q_proj cache needs).
@@ -289,15 +274,12 @@ int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, const float* 
  * workspace slot and the dqkv row have the same address arithmetic; its workspace region is left untouched) and the combine
  * adds the sparse branches only where they cover a (position, head), in the same order and precision as the form above, so
  * equal inputs give equal dqkv.  KV and Q phases must both have run on dqkv before COMBINE, and COMBINE runs once.  The
- * workspace keeps its size.  What mt_longnet_layer_bwd uses; a plan without a ratio-1 branch takes the workspace form. */
+ * workspace keeps its size.  What mt_longnet_layer_bwd uses; a plan without a ratio-1 branch takes the workspace form.
+ * opt: live -- the live passes only (all three phases; a plan without a ratio-1 branch runs the workspace-form combine over every row:
+ * the dqkv rows of a dropped pass then hold undefined values, which no consumer reads). */
 int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
-                                const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, mt_stream_t stream);
-
-/* the in-place backward over the live passes only (all three phases; a plan without a ratio-1 branch runs the
- * workspace-form combine over every row: the dqkv rows of a dropped pass then hold undefined values, which no consumer reads) */
-int mt_dilated_attn_bwd_inplace_live(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot, const float* delta_br,
-                                     const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, const int* live,
-                                     mt_stream_t stream);
+                                const MtDilatedPlan* plan, void* workspace, mt_half* dqkv, int phases, const MtLaunchOpts* opt,
+                                mt_stream_t stream);
 
 /* ------------------------------------------------- dense attention with 2-D ALiBi (TITAN blocks) ---- */
 /* The attention of the TITAN slide encoder's ViT blocks (titan_adapter.py:253-293 `get_alibi`, :359-361,394
@@ -362,7 +344,7 @@ int mt_pool_attn_bwd(const float* q, const mt_half* kv, const float* scores, con
  * still outstanding (hin is then written here) or NULL; defer != 0: leave this layer's fc2 add to the layer above (br16 holds the
  * branch, `out` is not written).  backward: dh (fp32 [M, D]) in / out; dh16_valid: the layer above left fp16(dh) in dh16;
  * feeds_lower: leave fp16(dh) (masked with drop_lower_ffn) for the layer below.
- * live_attn / live_ffn (one pass = plan->N rows): the kernels inside a branch -- its GEMMs (mt_gemm_nt_f16_live), attention, mix, combine,
+ * live_attn / live_ffn (one pass = plan->N rows): the kernels inside a branch -- its GEMMs, attention, mix, combine,
  * the FFN's sub-LayerNorm -- leave the dropped passes of the branch out, forward and backward; the kernels that carry the residual
  * stream (the add + LayerNorm forward, the LayerNorm backward, the cast, the BIAS_RESID product) run over all rows. */
 typedef struct {
@@ -409,8 +391,8 @@ typedef struct {
   mt_half *u16, *br16, *t16;
   float* dh; mt_half *dy16, *dh16, *dt16, *da1, *dqkv16; float* delta;
 } MtVitBlockBuffers;
-/* forward, in launch order: norm1 (mt_layernorm_fwd_eps; with pend_x: mt_add_layernorm_fwd_eps, which also writes hin) -> QKV GEMM ->
- * mt_dense_attn_fwd -> proj GEMM -> norm2 (mt_add_layernorm_fwd_eps: hmid = hin + branch) -> fc1 GEMM -> mt_gelu_f16_fwd ->
+/* forward, in launch order: norm1 (mt_layernorm_fwd with n1_eps; with pend_x: mt_add_layernorm_fwd, which also writes hin) -> QKV GEMM ->
+ * mt_dense_attn_fwd -> proj GEMM -> norm2 (mt_add_layernorm_fwd with n2_eps: hmid = hin + branch) -> fc1 GEMM -> mt_gelu_f16_fwd ->
  * fc2 GEMM (+ hmid into `out`; with defer: the plain branch into br16). */
 enum { MT_VBF_LN1 = 1 << 0, MT_VBF_QKV = 1 << 1, MT_VBF_ATTN = 1 << 2, MT_VBF_PROJ = 1 << 3, MT_VBF_LN2 = 1 << 4, MT_VBF_FC1 = 1 << 5,
        MT_VBF_GELU = 1 << 6, MT_VBF_FC2 = 1 << 7 };
@@ -445,19 +427,20 @@ int mt_extract_attn_fwd(const float* q, const mt_half* kv, int B, int T, int L, 
 int mt_extract_attn_bwd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
                         int B, int T, int L, float* dq, mt_half* dkv, mt_stream_t stream);
 
-/* Width-aware twins of the four cores above: `heads` heads of dim `head_dim` (16, 32 or 64; anything else returns
+/* Width-aware forms of the four cores above: `heads` heads of dim `head_dim` (16, 32 or 64; anything else returns
  * MT_ERR_UNSUPPORTED), E = heads * head_dim wherever 192 stands above (kv [B*L, 2E]), lse [M,heads] / [B,T,heads], the
  * extractor partials part_acc [B*heads*nsplit*T*head_dim] and part_ml [B*heads*nsplit*T*2] floats.  The entry points above
- * are these with (12, 16). */
+ * are these with (12, 16) (and opt = NULL).  The two backward forms take opt: partials (the deterministic forms, end of this header). */
 int mt_inject_attn_fwd_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T, int heads,
                           int head_dim, mt_half* a, float* lse, mt_stream_t stream);
 int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
                           int rows_per_pass, const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq,
-                          float* dk, float* dv, mt_stream_t stream);
+                          float* dk, float* dv, const MtLaunchOpts* opt, mt_stream_t stream);
 int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
                            float* lse, float* part_acc, float* part_ml, int nsplit, mt_stream_t stream);
 int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
-                           int B, int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, mt_stream_t stream);
+                           int B, int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, const MtLaunchOpts* opt,
+                           mt_stream_t stream);
 
 /* Pathway networks of the gene encoder, all G pathways in one launch (gene_encoder.py:97-131,194-207: per pathway
  * SNN_Block(n_i -> latent), SNN_Block(latent -> latent), ELU, AlphaDropout off):
@@ -551,11 +534,11 @@ int mt_copy_rows_f32(const float* src, long lds, const MtRowMap* smap, float* ds
                      int M, int D, int accumulate, mt_stream_t stream);
 /* Injector residual-path backward (A.1): dres(m,:) += (1 + g) * dy(m,:) for the patch rows; also reduces
  * dgamma[n] += sum_m dy(m,n) * (x(m,n) + proj(m,n)) where proj = a @ Wo^T + bo is recomputed by the caller as
- * fp16 `proj`.  */
+ * fp16 `proj`.  opt: partials. */
 int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
                         const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
                         const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,
-                        mt_stream_t stream);
+                        const MtLaunchOpts* opt, mt_stream_t stream);
 
 /* ---------------------------------------------------------- head, loss, optimiser ------------------ */
 /* y[r,:] = x[r,:] / ||x[r,:]||_2 for R contiguous rows of O (projected text rows, TM:213) */
@@ -625,48 +608,28 @@ int mt_scatter_rows_f32(const float* src, const int* src_idx, const int* idx, fl
                         mt_stream_t stream);
 int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_stream_t stream);
 
-/* ------------------------------------------------------- deterministic twins ------------------------ */
+/* ------------------------------------------------------- deterministic forms ------------------------ */
 /* The six launchers above that accumulate a trainable-parameter gradient with fp32 atomics (in whatever order their workgroups
- * retire), in a bit-reproducible form: no atomic, global or LDS, executes.  Every workgroup stores its partial result with plain
- * stores to its own slot of `partials` (a pure function of its block index), then ONE reduce kernel (csrc/det_reduce.hip) adds the
- * slots in ascending order and adds the sum to the destination -- the `+=` of the default forms is kept, and every output that is not
- * reduced across workgroups (dx, dx_f16, dproj, the patch-side dq, dkv) has the default form's bits.  Arguments as in the default
- * form, plus the caller's fp32 workspace: `partials` (16-byte aligned) of `partials_elems` floats, at least what the `_det_elems`
- * query of the same shape returns (host arithmetic only; a negative MtStatus for a shape the twin rejects).  A NULL or short
- * workspace returns MT_ERR_BAD_ARG before any launch.  The workspace needs no initialisation: no slot is read that was not written
- * by the same call.  Like everything here: no allocation, no synchronisation; two calls in flight need two workspaces.
- *   mt_gemm_tn_f16_det        slots = the row ranges of the M-split that hold rows; [slots][N1][N2], then [slots][N1] with colsum
- *   mt_colsum_f16_det         [cdiv(M, 256)][N]
- *   mt_layernorm_bwd_det      dw and db required; [min(cdiv(M, 4), 512)][2][D]
- *   mt_inject_resid_bwd_det   [min(cdiv(M, 4), 512)][D]
- *   mt_inject_attn_bwd_hd_det [cdiv(rows_per_pass, 512)][B][T][E] for dk, then the same for dv
- *   mt_extract_attn_bwd_hd_det [cdiv(L, 512)][B][T][E] */
+ * retire) have a bit-reproducible form, selected by MtLaunchOpts.partials: no atomic, global or LDS, executes.  Every workgroup stores
+ * its partial result with plain stores to its own slot of `partials` (a pure function of its block index), then ONE reduce kernel
+ * (csrc/det_reduce.hip) adds the slots in ascending order and adds the sum to the destination -- the `+=` of the default forms is kept,
+ * and every output that is not reduced across workgroups (dx, dx_f16, dproj, the patch-side dq, dkv) has the default form's bits.
+ * `partials`: the caller's fp32 workspace (16-byte aligned) of `partials_elems` floats, at least what the `_det_elems` query of the same
+ * shape returns (host arithmetic only; a negative MtStatus for a shape the form rejects).  A short workspace returns MT_ERR_BAD_ARG
+ * before any launch.  The workspace needs no initialisation: no slot is read that was not written by the same call.  Like everything
+ * here: no allocation, no synchronisation; two calls in flight need two workspaces.
+ *   mt_gemm_tn_f16         slots = the row ranges of the M-split that hold rows; [slots][N1][N2], then [slots][N1] with colsum
+ *   mt_colsum_f16          [cdiv(M, 256)][N]
+ *   mt_layernorm_bwd       dw and db required; [min(cdiv(M, 4), 512)][2][D]
+ *   mt_inject_resid_bwd    [min(cdiv(M, 4), 512)][D]
+ *   mt_inject_attn_bwd_hd  [cdiv(rows_per_pass, 512)][B][T][E] for dk, then the same for dv
+ *   mt_extract_attn_bwd_hd [cdiv(L, 512)][B][T][E] */
 long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum);
-int mt_gemm_tn_f16_det(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb, const MtRowMap* bmap,
-                       int M, int N1, int N2, float* C, long ldc, float* colsum, float* partials, long partials_elems,
-                       mt_stream_t stream);
 long mt_colsum_f16_det_elems(int M, int N);
-int mt_colsum_f16_det(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, float* partials,
-                      long partials_elems, mt_stream_t stream);
 long mt_layernorm_bwd_det_elems(int M, int D);
-int mt_layernorm_bwd_det(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
-                         const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
-                         long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
-                         mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, float* partials, long partials_elems,
-                         mt_stream_t stream);
 long mt_inject_resid_bwd_det_elems(int M, int D);
-int mt_inject_resid_bwd_det(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
-                            const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
-                            const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,
-                            float* partials, long partials_elems, mt_stream_t stream);
 long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T, int heads, int head_dim);
-int mt_inject_attn_bwd_hd_det(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
-                              int rows_per_pass, const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq,
-                              float* dk, float* dv, float* partials, long partials_elems, mt_stream_t stream);
 long mt_extract_attn_bwd_hd_det_elems(int B, int T, int L, int heads, int head_dim);
-int mt_extract_attn_bwd_hd_det(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout,
-                               int B, int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, float* partials,
-                               long partials_elems, mt_stream_t stream);
 
 #ifdef __cplusplus
 }

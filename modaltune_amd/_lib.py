@@ -29,6 +29,11 @@ class MtGemmEpilogue(C.Structure):
                 ("pos_table", P), ("pos_row", P), ("pos_col", P), ("drop", MtDropout)]
 
 
+class MtLaunchOpts(C.Structure):
+    """The optional inputs of a launcher (include/modaltune_hip.h); NULL or all zero = the default form."""
+    _fields_ = [("eps", F), ("live", P), ("live_rows", I), ("partials", P), ("partials_elems", L), ("grid_wgs", I)]
+
+
 MT_SGEMM_MAX = 3
 
 
@@ -77,39 +82,29 @@ DR = C.POINTER(MtDropout)
 EP = C.POINTER(MtGemmEpilogue)
 PL = C.POINTER(MtDilatedPlan)
 DP = C.POINTER(MtDensePlan)
+OP = C.POINTER(MtLaunchOpts)
 
 # name -> argtypes (restype int unless listed in _RESTYPE)
 SIGNATURES = {
     "mt_version": [],
     "mt_status_string": [I],
     "mt_build_id": [],
-    "mt_gemm_nt_f16": [P, L, RM, P, I, I, I, I, EP, P, L, RM, I, P],
-    "mt_gemm_tn_f16": [P, L, RM, P, L, RM, I, I, I, P, L, P, P],
-    "mt_colsum_f16": [P, L, RM, I, I, P, P],
+    "mt_gemm_nt_f16": [P, L, RM, P, I, I, I, I, EP, P, L, RM, I, OP, P],
+    "mt_gemm_tn_f16": [P, L, RM, P, L, RM, I, I, I, P, L, P, OP, P],
+    "mt_colsum_f16": [P, L, RM, I, I, P, OP, P],
     "mt_sgemm_small": [P, L, L, L, P, L, L, L, P, I, P, L, L, L, I, I, I, I, I, I, P, P],
     "mt_sgemm_multi": [C.POINTER(MtSgemm), I, P],
-    "mt_layernorm_fwd": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, P],
-    "mt_add_layernorm_fwd": [P, P, DR, P, P, P, P, P, I, I, P],
-    "mt_layernorm_fwd_eps": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, F, P],
-    "mt_add_layernorm_fwd_eps": [P, P, DR, P, P, P, P, P, I, I, F, P],
-    "mt_layernorm_bwd": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P],
-    # DropPath live table and the `_live` twins: the plain form's arguments + (live[, live_rows]) in front of the stream
+    "mt_layernorm_fwd": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, OP, P],
+    "mt_add_layernorm_fwd": [P, P, DR, P, P, P, P, P, I, I, OP, P],
+    "mt_layernorm_bwd": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, OP, P],
+    # (OP = the options pointer, directly in front of the stream: include/modaltune_hip.h says which fields each launcher honours)
     "mt_droppath_live": [P, P, I, I, P, P, P],
-    "mt_gemm_nt_f16_live": [P, L, RM, P, I, I, I, I, EP, P, L, RM, I, P, I, P],
-    "mt_layernorm_fwd_live": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, P, I, P],
-    "mt_layernorm_bwd_live": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P, I, P],
-    "mt_dilated_attn_fwd_live": [P, PL, P, P, P, P],
-    "mt_dilated_mix_ln_fwd_live": [P, P, PL, P, P, P, P, P, P, P],
-    "mt_dilated_mix_ln_bwd_live": [P, P, P, P, PL, P, P, P, P, P, P],
-    "mt_dilated_attn_bwd_inplace_live": [P, P, P, P, PL, P, P, I, P, P],
-    "mt_dilated_attn_fwd": [P, PL, P, P, P],
-    "mt_dilated_mix_ln_fwd": [P, P, PL, P, P, P, P, P, P],
-    "mt_dilated_mix_ln_bwd": [P, P, P, P, PL, P, P, P, P, P],
-    "mt_dilated_mix_ln_fwd_grid": [P, P, PL, P, P, P, P, P, I, P],
-    "mt_dilated_mix_ln_bwd_grid": [P, P, P, P, PL, P, P, P, P, I, P],
+    "mt_dilated_attn_fwd": [P, PL, P, P, OP, P],
+    "mt_dilated_mix_ln_fwd": [P, P, PL, P, P, P, P, P, OP, P],
+    "mt_dilated_mix_ln_bwd": [P, P, P, P, PL, P, P, P, P, OP, P],
     "mt_dilated_attn_bwd_workspace_bytes": [PL],
     "mt_dilated_attn_bwd": [P, P, P, P, PL, P, P, I, P],
-    "mt_dilated_attn_bwd_inplace": [P, P, P, P, PL, P, P, I, P],
+    "mt_dilated_attn_bwd_inplace": [P, P, P, P, PL, P, P, I, OP, P],
     "mt_gene_snn_fwd": [P, P, P, P, P, I, I, I, P, P, P, DR, P],
     "mt_gene_snn_bwd": [P, P, P, P, P, P, I, I, I, P, P, P, DR, P],
     "mt_gene_snn_fwd_points": [P, P, P, P, P, P, P, I, I, I, P, P, P, P],
@@ -120,9 +115,9 @@ SIGNATURES = {
     "mt_extract_attn_fwd": [P, P, I, I, I, P, P, P, P, I, P],
     "mt_extract_attn_bwd": [P, P, P, P, P, I, I, I, P, P, P],
     "mt_inject_attn_fwd_hd": [P, I, I, P, P, I, I, I, P, P, P],
-    "mt_inject_attn_bwd_hd": [P, P, P, P, I, I, P, P, I, I, I, P, P, P, P],
+    "mt_inject_attn_bwd_hd": [P, P, P, P, I, I, P, P, I, I, I, P, P, P, OP, P],
     "mt_extract_attn_fwd_hd": [P, P, I, I, I, I, I, P, P, P, P, I, P],
-    "mt_extract_attn_bwd_hd": [P, P, P, P, P, I, I, I, I, I, P, P, P],
+    "mt_extract_attn_bwd_hd": [P, P, P, P, P, I, I, I, I, I, P, P, OP, P],
     "mt_token_mha_fwd": [P, P, P, I, I, I, I, P, P, P],
     "mt_token_mha_bwd": [P, P, P, P, P, I, I, I, I, P, P, P, P],
     "mt_extract_attn_probs": [P, P, P, I, I, I, P, P],
@@ -143,7 +138,7 @@ SIGNATURES = {
     "mt_axpy_bcast": [P, P, F, P, L, L, P],
     "mt_fold_rows": [P, I, L, P, P],
     "mt_copy_rows_f32": [P, L, RM, P, L, RM, I, I, I, P],
-    "mt_inject_resid_bwd": [P, L, RM, P, L, RM, P, P, P, L, RM, I, P, P, I, I, P],
+    "mt_inject_resid_bwd": [P, L, RM, P, L, RM, P, P, P, L, RM, I, P, P, I, I, OP, P],
     "mt_l2norm_rows": [P, P, I, I, P],
     "mt_distill_loss": [P, P, I, I, F, P, P, P, P],
     "mt_adamw_step": [P, P, P, P, L, D, D, D, D, D, I, P, F, P, P, P, P],
@@ -172,19 +167,13 @@ SIGNATURES = {
     "mt_titan_gather_tokens": [P, P, I, I, P, P],
     "mt_scatter_rows_f32": [P, P, P, P, I, I, I, P],
     "mt_row_absmax_f32": [P, P, I, I, P],
-    # deterministic twins: the default form's arguments + (partials, partials_elems); `_det_elems`: host-only size queries
+    # `_det_elems`: host-only size queries of the deterministic forms' workspace (MtLaunchOpts.partials)
     "mt_gemm_tn_f16_det_elems": [I, I, I, I],
-    "mt_gemm_tn_f16_det": [P, L, RM, P, L, RM, I, I, I, P, L, P, P, L, P],
     "mt_colsum_f16_det_elems": [I, I],
-    "mt_colsum_f16_det": [P, L, RM, I, I, P, P, L, P],
     "mt_layernorm_bwd_det_elems": [I, I],
-    "mt_layernorm_bwd_det": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, P, L, P],
     "mt_inject_resid_bwd_det_elems": [I, I],
-    "mt_inject_resid_bwd_det": [P, L, RM, P, L, RM, P, P, P, L, RM, I, P, P, I, I, P, L, P],
     "mt_inject_attn_bwd_hd_det_elems": [I, I, I, I, I],
-    "mt_inject_attn_bwd_hd_det": [P, P, P, P, I, I, P, P, I, I, I, P, P, P, P, L, P],
     "mt_extract_attn_bwd_hd_det_elems": [I, I, I, I, I],
-    "mt_extract_attn_bwd_hd_det": [P, P, P, P, P, I, I, I, I, I, P, P, P, L, P],
 }
 _RESTYPE = {"mt_status_string": C.c_char_p, "mt_build_id": C.c_char_p, "mt_dilated_attn_bwd_workspace_bytes": C.c_long, "mt_pool_attn_workspace_floats": C.c_long,
              "mt_alibi_dist_halves": C.c_long,

@@ -1012,15 +1012,24 @@ __global__ void token_probs_mean_kernel(const float* __restrict__ probs, int B, 
 }
 
 // ---------------------------------------------------------------- launchers ----------------------
-// One launcher per kernel, templated like it; AD_DISPATCH picks the instantiation: <16, 12> for the shipped 12 x 16 (the head count a
+// One launcher per kernel, templated like it; AD_DISPATCH (AD_SELECT: without the return) picks the instantiation: <16, 12> for the shipped 12 x 16 (the head count a
 // compile-time constant, as before the template), <HD, 0> otherwise.
+#define AD_SELECT(rc, heads, hd, CALL)                      \
+  do {                                                      \
+    if ((hd) == 16 && (heads) == 12) rc = CALL(16, 12);     \
+    else if ((hd) == 16) rc = CALL(16, 0);                  \
+    else if ((hd) == 32) rc = CALL(32, 0);                  \
+    else if ((hd) == 64) rc = CALL(64, 0);                  \
+    else rc = MT_ERR_UNSUPPORTED;                           \
+  } while (0)
+// (a launcher with a deterministic form defines AD_CALL(HD, HC, DET) and selects through these two)
+#define AD_BASE(HD, HC) AD_CALL(HD, HC, false)
+#define AD_DET(HD, HC) AD_CALL(HD, HC, true)
 #define AD_DISPATCH(heads, hd, CALL)                        \
   do {                                                      \
-    if ((hd) == 16 && (heads) == 12) return CALL(16, 12);   \
-    if ((hd) == 16) return CALL(16, 0);                     \
-    if ((hd) == 32) return CALL(32, 0);                     \
-    if ((hd) == 64) return CALL(64, 0);                     \
-    return MT_ERR_UNSUPPORTED;                              \
+    int rc__;                                               \
+    AD_SELECT(rc__, heads, hd, CALL);                       \
+    return rc__;                                            \
   } while (0)
 
 constexpr int LDS_MAX = 160 * 1024;
@@ -1191,27 +1200,8 @@ extern "C" int mt_inject_attn_fwd(const mt_half* q, int M, int rows_per_pass, co
   return mt_inject_attn_fwd_hd(q, M, rows_per_pass, k, v, T, 12, 16, a, lse, stream);
 }
 
-extern "C" int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M, int rows_per_pass,
-                                     const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq, float* dk, float* dv,
-                                     mt_stream_t stream) {
-  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 ||
-      T > TMAX || !ad_heads_ok(heads, head_dim))
-    return MT_ERR_BAD_ARG;
-#define AD_CALL(HD, HC)                                                                                                              \
-  launch_inject_bwd<HD, HC>((const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, M / rows_per_pass, k, v, T, heads, (h16*)dq, \
-                            dk, dv, (hipStream_t)stream)
-  AD_DISPATCH(heads, head_dim, AD_CALL);
-#undef AD_CALL
-}
-
-extern "C" int mt_inject_attn_bwd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
-                                  int rows_per_pass, const float* k, const float* v, int T, mt_half* dq, float* dk,
-                                  float* dv, mt_stream_t stream) {
-  return mt_inject_attn_bwd_hd(q, a, lse, da, M, rows_per_pass, k, v, T, 12, 16, dq, dk, dv, stream);
-}
-
-// deterministic twin (det_reduce.hip): partials = dk slots [row blocks][B][T][E], then dv slots likewise; row blocks =
-// cdiv(rows_per_pass, 512), E = heads * head_dim.  Rows t >= T of a slot do not exist.
+// partials = dk slots [row blocks][B][T][E], then dv slots likewise; row blocks = cdiv(rows_per_pass, 512), E = heads * head_dim.
+// Rows t >= T of a slot do not exist.
 extern "C" long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T, int heads, int head_dim) {
   if (M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim) ||
       (head_dim != 16 && head_dim != 32 && head_dim != 64))
@@ -1219,29 +1209,40 @@ extern "C" long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T,
   return 2L * cdiv(rows_per_pass, IBR * ITILES) * (M / rows_per_pass) * T * heads * head_dim;
 }
 
-extern "C" int mt_inject_attn_bwd_hd_det(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M, int rows_per_pass,
-                                         const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq, float* dk,
-                                         float* dv, float* partials, long partials_elems, mt_stream_t stream) {
-  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || !partials) return MT_ERR_BAD_ARG;
-  const long need = mt_inject_attn_bwd_hd_det_elems(M, rows_per_pass, T, heads, head_dim);
-  if (need < 0 || partials_elems < need) return MT_ERR_BAD_ARG;
-  const int slots = cdiv(rows_per_pass, IBR * ITILES), E = heads * head_dim;
-  const long slot = (long)(M / rows_per_pass) * T * E;
-  float* pk = partials;
-  float* pv = partials + slots * slot;
-  int rc = MT_ERR_UNSUPPORTED;
-#define AD_CALL(HD, HC)                                                                                                              \
-  launch_inject_bwd<HD, HC, true>((const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, M / rows_per_pass, k, v, T, heads, \
-                                  (h16*)dq, pk, pv, (hipStream_t)stream)
-  if (head_dim == 16 && heads == 12) rc = AD_CALL(16, 12);
-  else if (head_dim == 16) rc = AD_CALL(16, 0);
-  else if (head_dim == 32) rc = AD_CALL(32, 0);
-  else if (head_dim == 64) rc = AD_CALL(64, 0);
+// opt->partials: the deterministic form (det_reduce.hip) -- the kernel's dk / dv targets are the partial slots, two reduces follow
+extern "C" int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M, int rows_per_pass,
+                                     const float* k, const float* v, int T, int heads, int head_dim, mt_half* dq, float* dk, float* dv,
+                                     const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
+  float* partials = mt_opt_partials(opt);
+  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 ||
+      T > TMAX || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+  const int B = M / rows_per_pass, slots = cdiv(rows_per_pass, IBR * ITILES), E = heads * head_dim;
+  const long slot = (long)B * T * E;
+  if (partials) {
+    const long need = mt_inject_attn_bwd_hd_det_elems(M, rows_per_pass, T, heads, head_dim);
+    if (need < 0 || opt->partials_elems < need) return MT_ERR_BAD_ARG;
+  }
+  float* pk = partials ? partials : dk;
+  float* pv = partials ? partials + slots * slot : dv;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+#define AD_CALL(HD, HC, DET)                                                                                                            \
+  launch_inject_bwd<HD, HC, DET>((const h16*)q, (const h16*)a, lse, (const h16*)da, rows_per_pass, B, k, v, T, heads, (h16*)dq, pk, pv, s)
+  if (!partials) AD_SELECT(rc, heads, head_dim, AD_BASE);
+  else AD_SELECT(rc, heads, head_dim, AD_DET);
 #undef AD_CALL
+  if (rc != MT_OK || !partials) return rc;
+  rc = mt_det_reduce_launch(pk, slots, B * T, E, slot, dk, E, s);
   if (rc != MT_OK) return rc;
-  rc = mt_det_reduce_launch(pk, slots, (M / rows_per_pass) * T, E, slot, dk, E, (hipStream_t)stream);
-  if (rc != MT_OK) return rc;
-  return mt_det_reduce_launch(pv, slots, (M / rows_per_pass) * T, E, slot, dv, E, (hipStream_t)stream);
+  return mt_det_reduce_launch(pv, slots, B * T, E, slot, dv, E, s);
+}
+
+extern "C" int mt_inject_attn_bwd(const mt_half* q, const mt_half* a, const float* lse, const mt_half* da, int M,
+                                  int rows_per_pass, const float* k, const float* v, int T, mt_half* dq, float* dk,
+                                  float* dv, mt_stream_t stream) {
+  return mt_inject_attn_bwd_hd(q, a, lse, da, M, rows_per_pass, k, v, T, 12, 16, dq, dk, dv, nullptr, stream);
 }
 
 extern "C" int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
@@ -1262,45 +1263,40 @@ extern "C" int mt_extract_attn_fwd(const float* q, const mt_half* kv, int B, int
   return mt_extract_attn_fwd_hd(q, kv, B, T, L, 12, 16, out, lse, part_acc, part_ml, nsplit, stream);
 }
 
-extern "C" int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout, int B,
-                                      int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, mt_stream_t stream) {
-  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim))
-    return MT_ERR_BAD_ARG;
-#define AD_CALL(HD, HC) launch_extract_bwd<HD, HC>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, dq, (h16*)dkv, (hipStream_t)stream)
-  AD_DISPATCH(heads, head_dim, AD_CALL);
-#undef AD_CALL
-}
-
-// deterministic twin: partials = dq slots [key blocks][B][T][E], key blocks = cdiv(L, 512)
+// partials = dq slots [key blocks][B][T][E], key blocks = cdiv(L, 512)
 extern "C" long mt_extract_attn_bwd_hd_det_elems(int B, int T, int L, int heads, int head_dim) {
   if (B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim) || (head_dim != 16 && head_dim != 32 && head_dim != 64))
     return MT_ERR_BAD_ARG;
   return (long)cdiv(L, EBK * ETILES) * B * T * heads * head_dim;
 }
 
-extern "C" int mt_extract_attn_bwd_hd_det(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout, int B,
-                                          int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, float* partials,
-                                          long partials_elems, mt_stream_t stream) {
-  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || !partials) return MT_ERR_BAD_ARG;
-  const long need = mt_extract_attn_bwd_hd_det_elems(B, T, L, heads, head_dim);
-  if (need < 0 || partials_elems < need) return MT_ERR_BAD_ARG;
-  const int slots = cdiv(L, EBK * ETILES);
-  const long slot = (long)B * T * heads * head_dim;
-  int rc = MT_ERR_UNSUPPORTED;
-#define AD_CALL(HD, HC) \
-  launch_extract_bwd<HD, HC, true>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, partials, (h16*)dkv, (hipStream_t)stream)
-  if (head_dim == 16 && heads == 12) rc = AD_CALL(16, 12);
-  else if (head_dim == 16) rc = AD_CALL(16, 0);
-  else if (head_dim == 32) rc = AD_CALL(32, 0);
-  else if (head_dim == 64) rc = AD_CALL(64, 0);
+// opt->partials: the deterministic form -- the kernel's dq target is the partial slots, one reduce follows
+extern "C" int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const float* out, const float* lse, const float* dout, int B,
+                                      int T, int L, int heads, int head_dim, float* dq, mt_half* dkv, const MtLaunchOpts* opt,
+                                      mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
+  float* partials = mt_opt_partials(opt);
+  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim))
+    return MT_ERR_BAD_ARG;
+  if (partials) {
+    const long need = mt_extract_attn_bwd_hd_det_elems(B, T, L, heads, head_dim);
+    if (need < 0 || opt->partials_elems < need) return MT_ERR_BAD_ARG;
+  }
+  float* pq = partials ? partials : dq;
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+#define AD_CALL(HD, HC, DET) launch_extract_bwd<HD, HC, DET>(q, (const h16*)kv, out, lse, dout, B, T, L, heads, pq, (h16*)dkv, s)
+  if (!partials) AD_SELECT(rc, heads, head_dim, AD_BASE);
+  else AD_SELECT(rc, heads, head_dim, AD_DET);
 #undef AD_CALL
-  if (rc != MT_OK) return rc;
-  return mt_det_reduce_launch(partials, slots, B * T, heads * head_dim, slot, dq, heads * head_dim, (hipStream_t)stream);
+  if (rc != MT_OK || !partials) return rc;
+  const int E = heads * head_dim;
+  return mt_det_reduce_launch(partials, cdiv(L, EBK * ETILES), B * T, E, (long)B * T * E, dq, E, s);
 }
 
 extern "C" int mt_extract_attn_bwd(const float* q, const mt_half* kv, const float* out, const float* lse,
                                    const float* dout, int B, int T, int L, float* dq, mt_half* dkv, mt_stream_t stream) {
-  return mt_extract_attn_bwd_hd(q, kv, out, lse, dout, B, T, L, 12, 16, dq, dkv, stream);
+  return mt_extract_attn_bwd_hd(q, kv, out, lse, dout, B, T, L, 12, 16, dq, dkv, nullptr, stream);
 }
 
 static bool mha_ptrs_ok(const float* const* ps, int n, int E) {

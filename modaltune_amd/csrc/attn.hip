@@ -414,10 +414,11 @@ __global__ __launch_bounds__(256) void mix_ln_bwd_kernel(const h16* __restrict__
 
 }  // namespace
 
-extern "C" int mt_dilated_attn_fwd_live(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const int* live,
-                                        mt_stream_t stream) {
+extern "C" int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br, const MtLaunchOpts* opt,
+                                   mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE)) return rc;
   if (!qkv || !o_br || !lse_br || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128, live);
+  const Plan p = make_plan(plan, 128, mt_opt_live(opt));
   const int nblk = p.blk_off[p.nbranch];
   if (p.live) hipLaunchKernelGGL(dilated_attn_fwd_kernel<true>, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const h16*)qkv, p,
                      (h16*)o_br, lse_br);
@@ -425,11 +426,6 @@ extern "C" int mt_dilated_attn_fwd_live(const mt_half* qkv, const MtDilatedPlan*
                      (h16*)o_br, lse_br);
   MT_CHECK_LAUNCH();
   return MT_OK;
-}
-
-extern "C" int mt_dilated_attn_fwd(const mt_half* qkv, const MtDilatedPlan* plan, mt_half* o_br, float* lse_br,
-                                   mt_stream_t stream) {
-  return mt_dilated_attn_fwd_live(qkv, plan, o_br, lse_br, nullptr, stream);
 }
 
 // Grid of the mix kernels: as many workgroups (four waves, a wave = two rows at a time) per CU as a CU holds at once, never more than
@@ -443,13 +439,14 @@ static dim3 mix_grid(long M, int grid_wgs, int wg_per_cu) {
   return dim3((int)min((M + 7) / 8, (long)(grid_wgs > 0 ? grid_wgs : wg_per_cu * MIX_CUS)));
 }
 
-namespace {
-int mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan, const float* ln_w, const float* ln_b, mt_half* y,
-               float* stats, float* lse_tot, int grid_wgs, const int* live, mt_stream_t stream) {
+extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
+                                     const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
+                                     const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE | MT_OPT_GRID)) return rc;
   if (!o_br || !lse_br || !ln_w || !ln_b || !y || !stats || !lse_tot || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128, live);
+  const Plan p = make_plan(plan, 128, mt_opt_live(opt));
   const long M = (long)p.B * p.N;
-  const dim3 grid = mix_grid(M, grid_wgs, MIX_FWD_WG_PER_CU);
+  const dim3 grid = mix_grid(M, opt ? opt->grid_wgs : 0, MIX_FWD_WG_PER_CU);
   if (p.nbranch <= 5)
     hipLaunchKernelGGL(mix_ln_fwd_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, (const h16*)o_br, lse_br, p, ln_w, ln_b,
                        (h16*)y, stats, lse_tot);
@@ -459,33 +456,15 @@ int mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* pl
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
-}  // namespace
 
-extern "C" int mt_dilated_mix_ln_fwd_grid(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
-                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
-                                          int grid_wgs, mt_stream_t stream) {
-  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs, nullptr, stream);
-}
-
-extern "C" int mt_dilated_mix_ln_fwd(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
-                                     const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
-                                     mt_stream_t stream) {
-  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, nullptr, stream);
-}
-
-extern "C" int mt_dilated_mix_ln_fwd_live(const mt_half* o_br, const float* lse_br, const MtDilatedPlan* plan,
-                                          const float* ln_w, const float* ln_b, mt_half* y, float* stats, float* lse_tot,
-                                          const int* live, mt_stream_t stream) {
-  return mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, 0, live, stream);
-}
-
-namespace {
-int mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot, const MtDilatedPlan* plan,
-               const float* ln_w, const float* stats, mt_half* dmixed, float* delta_br, int grid_wgs, const int* live, mt_stream_t stream) {
+extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
+                                     const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
+                                     float* delta_br, const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE | MT_OPT_GRID)) return rc;
   if (!dy || !o_br || !lse_br || !lse_tot || !ln_w || !stats || !dmixed || !delta_br || !plan_ok(plan)) return MT_ERR_BAD_ARG;
-  const Plan p = make_plan(plan, 128, live);
+  const Plan p = make_plan(plan, 128, mt_opt_live(opt));
   const long M = (long)p.B * p.N;
-  const dim3 grid = mix_grid(M, grid_wgs, MIX_BWD_WG_PER_CU);
+  const dim3 grid = mix_grid(M, opt ? opt->grid_wgs : 0, MIX_BWD_WG_PER_CU);
   if (p.nbranch <= 5)
     hipLaunchKernelGGL(mix_ln_bwd_kernel<5>, grid, dim3(256), 0, (hipStream_t)stream, (const h16*)dy, (const h16*)o_br, lse_br,
                        lse_tot, p, ln_w, stats, (h16*)dmixed, delta_br);
@@ -494,25 +473,6 @@ int mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, cons
                        (const h16*)o_br, lse_br, lse_tot, p, ln_w, stats, (h16*)dmixed, delta_br);
   MT_CHECK_LAUNCH();
   return MT_OK;
-}
-}  // namespace
-
-extern "C" int mt_dilated_mix_ln_bwd_grid(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                                          float* delta_br, int grid_wgs, mt_stream_t stream) {
-  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, grid_wgs, nullptr, stream);
-}
-
-extern "C" int mt_dilated_mix_ln_bwd(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                                     const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                                     float* delta_br, mt_stream_t stream) {
-  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, nullptr, stream);
-}
-
-extern "C" int mt_dilated_mix_ln_bwd_live(const mt_half* dy, const mt_half* o_br, const float* lse_br, const float* lse_tot,
-                                          const MtDilatedPlan* plan, const float* ln_w, const float* stats, mt_half* dmixed,
-                                          float* delta_br, const int* live, mt_stream_t stream) {
-  return mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, 0, live, stream);
 }
 
 extern "C" long mt_dilated_attn_bwd_workspace_bytes(const MtDilatedPlan* plan) {
@@ -548,16 +508,11 @@ extern "C" int mt_dilated_attn_bwd(const mt_half* qkv, const mt_half* dmixed, co
   return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, false, nullptr, stream);
 }
 
+// (with a live table, a plan without a ratio-1 branch runs the workspace-form combine, which walks every row: the dqkv rows of a dropped
+// pass are then formed from stale workspace bytes -- like every buffer of the branch they are never read for such a pass)
 extern "C" int mt_dilated_attn_bwd_inplace(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
                                            const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
-                                           int phases, mt_stream_t stream) {
-  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, nullptr, stream);
-}
-
-extern "C" int mt_dilated_attn_bwd_inplace_live(const mt_half* qkv, const mt_half* dmixed, const float* lse_tot,
-                                                const float* delta_br, const MtDilatedPlan* plan, void* workspace, mt_half* dqkv,
-                                                int phases, const int* live, mt_stream_t stream) {
-  // (a plan without a ratio-1 branch runs the workspace-form combine, which walks every row: the dqkv rows of a dropped pass are then
-  // formed from stale workspace bytes -- like every buffer of the branch they are never read for such a pass)
-  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, live, stream);
+                                           int phases, const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE)) return rc;
+  return attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv, phases, true, mt_opt_live(opt), stream);
 }

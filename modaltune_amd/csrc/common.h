@@ -182,5 +182,21 @@ MT_DEVINL void stg8(h16* p, h16x8 v) { *reinterpret_cast<h16x8*>(p) = v; }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// MtLaunchOpts (include/modaltune_hip.h): the first check of every launcher that takes one.  `allowed`: the MT_OPT_* fields the launcher
+// honours; a set field outside them is MT_ERR_UNSUPPORTED -- never ignored --, a malformed value of an honoured one MT_ERR_BAD_ARG.
+enum { MT_OPT_EPS = 1, MT_OPT_LIVE = 2, MT_OPT_PARTIALS = 4, MT_OPT_GRID = 8 };
+static inline int mt_opts_check(const MtLaunchOpts* o, int allowed) {
+  if (!o) return MT_OK;
+  const int set = (o->eps != 0.f ? MT_OPT_EPS : 0) | (o->live || o->live_rows ? MT_OPT_LIVE : 0) |
+                  (o->partials || o->partials_elems ? MT_OPT_PARTIALS : 0) | (o->grid_wgs ? MT_OPT_GRID : 0);
+  if (set & ~allowed) return MT_ERR_UNSUPPORTED;
+  if (!(o->eps >= 0.f) || o->live_rows < 0 || o->partials_elems < 0 || o->grid_wgs < 0) return MT_ERR_BAD_ARG;
+  if (o->partials_elems && !o->partials) return MT_ERR_BAD_ARG;
+  return MT_OK;
+}
+static inline float mt_opt_eps(const MtLaunchOpts* o) { return o && o->eps != 0.f ? o->eps : 1e-5f; }
+static inline const int* mt_opt_live(const MtLaunchOpts* o) { return o ? o->live : nullptr; }
+static inline float* mt_opt_partials(const MtLaunchOpts* o) { return o ? o->partials : nullptr; }
+
 // det_reduce.hip: dst[r * ldd + c] += sum over slots i = 0 .. nparts - 1, ascending, of partials[i * part_stride + r * cols + c]
 int mt_det_reduce_launch(const float* partials, int nparts, int rows, int cols, long part_stride, float* dst, long ldd, hipStream_t s);

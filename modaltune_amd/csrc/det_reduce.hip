@@ -1,5 +1,5 @@
-// Deterministic mode: the ONE reduce kernel behind every `_det` launcher (include/modaltune_hip.h, "Deterministic twins").
-// A `_det` kernel stores its workgroups' partial results with plain stores, each to a slot that is a pure function of blockIdx;
+// Deterministic mode: the ONE reduce kernel behind every launcher's deterministic form (include/modaltune_hip.h, "deterministic forms":
+// MtLaunchOpts.partials).  A DET kernel stores its workgroups' partial results with plain stores, each to a slot that is a pure function of blockIdx;
 // this kernel then adds them up in ASCENDING slot order -- a fixed association, whatever order the workgroups retired in -- and
 // adds the sum to the destination (the `+=` of the atomic forms):
 //   dst[r * ldd + c] += ((p[0] + p[1]) + p[2]) + ...     p[i] = partials[i * part_stride + r * cols + c]

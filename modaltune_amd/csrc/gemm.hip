@@ -486,7 +486,7 @@ __global__ __launch_bounds__(512) void gemm_nt_pp_kernel(GemmNtArgs g) {
 
 template <int BN, int EPI, typename OutT, bool LIVE = false>
 int launch_nt(const GemmNtArgs& a, hipStream_t s) {
-  if constexpr (!LIVE && (EPI == MT_EPI_BIAS || EPI == MT_EPI_QKV_HM)) {      // (the epilogues a table goes with: mt_gemm_nt_f16_live)
+  if constexpr (!LIVE && (EPI == MT_EPI_BIAS || EPI == MT_EPI_QKV_HM)) {      // (the epilogues a table goes with: mt_gemm_nt_f16)
     if (a.live) return launch_nt<BN, EPI, OutT, true>(a, s);
   }
   if constexpr (BN == 256) {
@@ -967,9 +967,12 @@ __global__ __launch_bounds__(256) void sgemm_multi_kernel(SgemmMulti mm) {
 
 }  // namespace
 
-extern "C" int mt_gemm_nt_f16_live(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
-                                   int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
-                                   int out_dtype, const int* live, int live_rows, mt_stream_t stream) {
+extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
+                              int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
+                              int out_dtype, const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE)) return rc;
+  const int* live = mt_opt_live(opt);
+  const int live_rows = opt ? opt->live_rows : 0;
   if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0 || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
   // (a table goes with the products INSIDE a branch; the epilogues that carry the residual stream run over every row)
   if (live && epilogue != MT_EPI_BIAS && epilogue != MT_EPI_QKV_HM) return MT_ERR_UNSUPPORTED;
@@ -1020,22 +1023,30 @@ extern "C" int mt_gemm_nt_f16_live(const mt_half* A, long lda, const MtRowMap* a
   }
 }
 
-extern "C" int mt_gemm_nt_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* W, int M, int N, int K,
-                              int epilogue, const MtGemmEpilogue* epi, void* C, long ldc, const MtRowMap* cmap,
-                              int out_dtype, mt_stream_t stream) {
-  return mt_gemm_nt_f16_live(A, lda, amap, W, M, N, K, epilogue, epi, C, ldc, cmap, out_dtype, nullptr, 0, stream);
-}
-
 // 64 x 64 tiles and ~1024 workgroups (512 for the small products), a multiple of the 8 XCDs: see mt_gemm_tn_f16
 static int gemm_tn_split(int M, int tiles) {
   const int split = max(1, min(cdiv(M, 256), cdiv(tiles >= 16 ? 1024 : 512, tiles)));
   return cdiv(split, 8) * 8;
 }
 
+// The deterministic form (det_reduce.hip) launches as many splits as the default form (same tiles, same XCD rule);
+// slots = min(32-row steps, launched splits): the splits that hold rows (gemm_tn_kernel, DET).
+// partials = [slots][N1][N2], then (with_colsum) [slots][N1].
+static int gemm_tn_det_slots(int M, int N1, int N2) { return min(cdiv(M, 32), gemm_tn_split(M, (N1 / 64) * (N2 / 64))); }
+
+extern "C" long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum) {
+  if (M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64) return MT_ERR_BAD_ARG;
+  return (long)gemm_tn_det_slots(M, N1, N2) * N1 * ((long)N2 + (with_colsum ? 1 : 0));
+}
+
 extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb,
                               const MtRowMap* bmap, int M, int N1, int N2, float* C, long ldc, float* colsum,
-                              mt_stream_t stream) {
+                              const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
+  float* partials = mt_opt_partials(opt);
   if (!A || !B || !C || M <= 0 || N1 % 64 || N2 % 64 || lda % 8 || ldb % 8) return MT_ERR_BAD_ARG;
+  if (partials && (N1 <= 0 || N2 <= 0 || ldc < N2 || opt->partials_elems < mt_gemm_tn_f16_det_elems(M, N1, N2, colsum != nullptr)))
+    return MT_ERR_BAD_ARG;
   GemmTnArgs g;
   g.A = (const h16*)A; g.lda = lda; g.amap = make_rowmap(amap);
   g.B = (const h16*)B; g.ldb = ldb; g.bmap = make_rowmap(bmap);
@@ -1045,42 +1056,16 @@ extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   // tiles the kernel template allows re-read less but need more splits -- more atomics -- for the same number of workgroups)
   const int tiles = (N1 / 64) * (N2 / 64);
   const int split = gemm_tn_split(M, tiles);
-  g.rows_per_split = cdiv(cdiv(M, split), 32) * 32;
-  hipLaunchKernelGGL((gemm_tn_kernel<64, 64>), dim3(tiles * split), dim3(256), 0, (hipStream_t)stream, g);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-
-// ---- deterministic twins (det_reduce.hip).  As many splits are launched as the default form launches (same tiles, same XCD rule);
-// slots = min(32-row steps, launched splits): the splits that hold rows (gemm_tn_kernel, DET).
-// partials = [slots][N1][N2], then (with_colsum) [slots][N1].
-static int gemm_tn_det_slots(int M, int N1, int N2, int* split_out) {
-  const int split = gemm_tn_split(M, (N1 / 64) * (N2 / 64));
-  if (split_out) *split_out = split;
-  return min(cdiv(M, 32), split);
-}
-
-extern "C" long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum) {
-  if (M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64) return MT_ERR_BAD_ARG;
-  return (long)gemm_tn_det_slots(M, N1, N2, nullptr) * N1 * ((long)N2 + (with_colsum ? 1 : 0));
-}
-
-extern "C" int mt_gemm_tn_f16_det(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb,
-                                  const MtRowMap* bmap, int M, int N1, int N2, float* C, long ldc, float* colsum, float* partials,
-                                  long partials_elems, mt_stream_t stream) {
-  if (!A || !B || !C || M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64 || lda % 8 || ldb % 8 || ldc < N2 || !partials ||
-      partials_elems < mt_gemm_tn_f16_det_elems(M, N1, N2, colsum != nullptr))
-    return MT_ERR_BAD_ARG;
-  int split;
-  GemmTnArgs g;
-  g.A = (const h16*)A; g.lda = lda; g.amap = make_rowmap(amap);
-  g.B = (const h16*)B; g.ldb = ldb; g.bmap = make_rowmap(bmap);
-  g.M = M; g.N1 = N1; g.N2 = N2; g.rows_per_split = 0;
-  const int slots = gemm_tn_det_slots(M, N1, N2, &split);
-  float* pcs = partials + (long)slots * N1 * N2;
-  g.C = partials; g.ldc = N2; g.colsum = colsum ? pcs : nullptr;
-  const int tiles = (N1 / 64) * (N2 / 64);
   hipStream_t s = (hipStream_t)stream;
+  if (!partials) {
+    g.rows_per_split = cdiv(cdiv(M, split), 32) * 32;
+    hipLaunchKernelGGL((gemm_tn_kernel<64, 64>), dim3(tiles * split), dim3(256), 0, s, g);
+    MT_CHECK_LAUNCH();
+    return MT_OK;
+  }
+  const int slots = gemm_tn_det_slots(M, N1, N2);
+  float* pcs = partials + (long)slots * N1 * N2;
+  g.rows_per_split = 0; g.C = partials; g.ldc = N2; g.colsum = colsum ? pcs : nullptr;
   hipLaunchKernelGGL((gemm_tn_kernel<64, 64, true>), dim3(tiles * split), dim3(256), 0, s, g);
   MT_CHECK_LAUNCH();
   int rc = mt_det_reduce_launch(partials, slots, N1, N2, (long)N1 * N2, C, ldc, s);
@@ -1088,31 +1073,26 @@ extern "C" int mt_gemm_tn_f16_det(const mt_half* A, long lda, const MtRowMap* am
   return rc;
 }
 
-extern "C" int mt_colsum_f16(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out,
-                             mt_stream_t stream) {
-  if (!A || !out || M <= 0 || N <= 0 || (N & 7) || (lda & 7)) return MT_ERR_BAD_ARG;
-  const int rows_per_block = 256;
-  hipLaunchKernelGGL(colsum_kernel<false>, dim3(cdiv(N, 256), cdiv(M, rows_per_block)), dim3(256), 0, (hipStream_t)stream,
-                     (const h16*)A, lda, make_rowmap(amap), M, N, rows_per_block, out);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-
-// deterministic twin: partials = [cdiv(M, 256)][N], one row per blockIdx.y
 extern "C" long mt_colsum_f16_det_elems(int M, int N) {
   if (M <= 0 || N <= 0 || (N & 7)) return MT_ERR_BAD_ARG;
   return (long)cdiv(M, 256) * N;
 }
 
-extern "C" int mt_colsum_f16_det(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, float* partials,
-                                 long partials_elems, mt_stream_t stream) {
-  if (!A || !out || M <= 0 || N <= 0 || (N & 7) || (lda & 7) || !partials || partials_elems < mt_colsum_f16_det_elems(M, N))
+// opt->partials: the deterministic form, partials = [cdiv(M, 256)][N], one row per blockIdx.y
+extern "C" int mt_colsum_f16(const mt_half* A, long lda, const MtRowMap* amap, int M, int N, float* out, const MtLaunchOpts* opt,
+                             mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
+  float* partials = mt_opt_partials(opt);
+  if (!A || !out || M <= 0 || N <= 0 || (N & 7) || (lda & 7) || (partials && opt->partials_elems < mt_colsum_f16_det_elems(M, N)))
     return MT_ERR_BAD_ARG;
   const int rows_per_block = 256, slots = cdiv(M, rows_per_block);
-  hipLaunchKernelGGL(colsum_kernel<true>, dim3(cdiv(N, 256), slots), dim3(256), 0, (hipStream_t)stream, (const h16*)A, lda,
-                     make_rowmap(amap), M, N, rows_per_block, partials);
+  hipStream_t s = (hipStream_t)stream;
+  if (!partials) hipLaunchKernelGGL(colsum_kernel<false>, dim3(cdiv(N, 256), slots), dim3(256), 0, s, (const h16*)A, lda,
+                                    make_rowmap(amap), M, N, rows_per_block, out);
+  else hipLaunchKernelGGL(colsum_kernel<true>, dim3(cdiv(N, 256), slots), dim3(256), 0, s, (const h16*)A, lda, make_rowmap(amap), M, N,
+                          rows_per_block, partials);
   MT_CHECK_LAUNCH();
-  return mt_det_reduce_launch(partials, slots, 1, N, N, out, N, (hipStream_t)stream);
+  return partials ? mt_det_reduce_launch(partials, slots, 1, N, N, out, N, s) : MT_OK;
 }
 
 static int sgemm_fill(const MtSgemm& q, SgemmArgs& g) {

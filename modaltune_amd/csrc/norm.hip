@@ -684,12 +684,16 @@ int ew_grid(long n) { return (int)max(1L, min((n + 1023) / 1024, 4096L)); }
 
 }  // namespace
 
-static int ln_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* b,
-                  const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
-                  float eps, const int* live, int live_rows, mt_stream_t stream) {
-  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || !(eps > 0.f) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
-  LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M, eps,
-              live, live_rows};
+extern "C" int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
+                                const float* w, const float* b, const float* add_rows, int add_period, void* y,
+                                long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
+                                const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_EPS | MT_OPT_LIVE)) return rc;
+  const int* live = mt_opt_live(opt);
+  const int live_rows = opt ? opt->live_rows : 0;
+  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
+  LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M,
+              mt_opt_eps(opt), live, live_rows};
   hipStream_t s = (hipStream_t)stream;
   switch (D) {
     case 256: return ln_fwd_types<256>(a, in_dtype, out_dtype, gelu_in, s);
@@ -700,42 +704,16 @@ static int ln_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, i
   }
 }
 
-extern "C" int mt_layernorm_fwd_eps(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
-                                    const float* w, const float* b, const float* add_rows, int add_period, void* y,
-                                    long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D, float eps,
+extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const MtDropout* drop, const float* w,
+                                    const float* b, float* h, mt_half* y, float* stats, int M, int D, const MtLaunchOpts* opt,
                                     mt_stream_t stream) {
-  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, eps, nullptr, 0, stream);
-}
-
-extern "C" int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
-                                const float* w, const float* b, const float* add_rows, int add_period, void* y,
-                                long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
-                                mt_stream_t stream) {
-  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, 1e-5f, nullptr, 0, stream);
-}
-
-extern "C" int mt_layernorm_fwd_live(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
-                                     const float* w, const float* b, const float* add_rows, int add_period, void* y,
-                                     long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
-                                     const int* live, int live_rows, mt_stream_t stream) {
-  return ln_fwd(x, ldx, xmap, in_dtype, gelu_in, w, b, add_rows, add_period, y, ldy, ymap, out_dtype, stats, M, D, 1e-5f, live, live_rows,
-                stream);
-}
-
-extern "C" int mt_add_layernorm_fwd_eps(const float* x, const mt_half* branch, const MtDropout* drop, const float* w,
-                                        const float* b, float* h, mt_half* y, float* stats, int M, int D, float eps,
-                                        mt_stream_t stream) {
-  if (!x || !branch || !w || !b || !h || !y || !stats || M <= 0 || h == x || !(eps > 0.f)) return MT_ERR_BAD_ARG;
+  if (int rc = mt_opts_check(opt, MT_OPT_EPS)) return rc;
+  if (!x || !branch || !w || !b || !h || !y || !stats || M <= 0 || h == x) return MT_ERR_BAD_ARG;
   if (D != 768) return MT_ERR_UNSUPPORTED;
-  AddLnArgs a{x, (const h16*)branch, make_drop(drop), w, b, h, (h16*)y, stats, M, eps};
+  AddLnArgs a{x, (const h16*)branch, make_drop(drop), w, b, h, (h16*)y, stats, M, mt_opt_eps(opt)};
   hipLaunchKernelGGL((add_ln_fwd_kernel<768>), dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
-}
-
-extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const MtDropout* drop, const float* w,
-                                    const float* b, float* h, mt_half* y, float* stats, int M, int D, mt_stream_t stream) {
-  return mt_add_layernorm_fwd_eps(x, branch, drop, w, b, h, y, stats, M, D, 1e-5f, stream);
 }
 
 template <int D>
@@ -761,63 +739,45 @@ static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int
   return MT_ERR_UNSUPPORTED;
 }
 
-extern "C" int mt_layernorm_bwd_live(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
-                                     long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
-                                     const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
-                                     int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
-                                     int D, const int* live, int live_rows, mt_stream_t stream) {
-  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
-  if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
-  if (live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
-  LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate, dw, db,
-              (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M, live, live_rows};
-  hipStream_t s = (hipStream_t)stream;
-  switch (D) {
-    case 256: return ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
-    case 768: return ln_bwd_types<768>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
-    case 2304: return ln_bwd_types<2304>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
-    case 3072: return ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s);
-    default: return MT_ERR_UNSUPPORTED;
-  }
-}
-
-extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
-                                long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
-                                const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
-                                int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
-                                int D, mt_stream_t stream) {
-  return mt_layernorm_bwd_live(dy, lddy, dymap, dy_dtype, x, ldx, xmap, in_dtype, gelu_in, w, stats, dx, lddx, dxmap, dx_dtype, accumulate,
-                               dw, db, dx_f16, dx_f16_drop, M, D, nullptr, 0, stream);
-}
-
-// ---- deterministic twins (det_reduce.hip): partials = [slots][2][D] for dw | db, slots = workgroups of the PARAM form
 extern "C" long mt_layernorm_bwd_det_elems(int M, int D) {
   if (M <= 0 || (D != 256 && D != 768 && D != 2304 && D != 3072)) return MT_ERR_BAD_ARG;
   return (long)ln_param_grid(M) * 2 * D;
 }
 
-extern "C" int mt_layernorm_bwd_det(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
-                                    const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
-                                    long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
-                                    mt_half* dx_f16, const MtDropout* dx_f16_drop, int M, int D, float* partials, long partials_elems,
-                                    mt_stream_t stream) {
-  if (!dy || !x || !w || !stats || !dx || M <= 0 || !dw || !db || !partials) return MT_ERR_BAD_ARG;
+// opt->partials: the deterministic form (det_reduce.hip), partials = [slots][2][D] for dw | db, slots = workgroups of the PARAM form
+extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x,
+                                long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
+                                const float* stats, void* dx, long lddx, const MtRowMap* dxmap, int dx_dtype,
+                                int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
+                                int D, const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_LIVE | MT_OPT_PARTIALS)) return rc;
+  const int* live = mt_opt_live(opt);
+  const int live_rows = opt ? opt->live_rows : 0;
+  float* partials = mt_opt_partials(opt);
+  if (live && partials) return MT_ERR_UNSUPPORTED;
+  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (partials && !dw) || (live && live_rows < 1))
+    return MT_ERR_BAD_ARG;
   if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
-  const long need = mt_layernorm_bwd_det_elems(M, D);
-  if (need < 0) return MT_ERR_UNSUPPORTED;
-  if (partials_elems < need) return MT_ERR_BAD_ARG;
-  LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate, partials,
-              partials + D, (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M};
+  if (live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
+  if (partials) {
+    const long need = mt_layernorm_bwd_det_elems(M, D);
+    if (need < 0) return MT_ERR_UNSUPPORTED;
+    if (opt->partials_elems < need) return MT_ERR_BAD_ARG;
+  }
+  LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate,
+              partials ? partials : dw, partials ? partials + D : db, (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M, live,
+              live_rows};
   hipStream_t s = (hipStream_t)stream;
+  const bool det = partials != nullptr;
   int rc;
   switch (D) {
-    case 256: rc = ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
-    case 768: rc = ln_bwd_types<768>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
-    case 2304: rc = ln_bwd_types<2304>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
-    case 3072: rc = ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, true); break;
+    case 256: rc = ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
+    case 768: rc = ln_bwd_types<768>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
+    case 2304: rc = ln_bwd_types<2304>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
+    case 3072: rc = ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
     default: return MT_ERR_UNSUPPORTED;
   }
-  if (rc != MT_OK) return rc;
+  if (rc != MT_OK || !det) return rc;
   const int slots = ln_param_grid(M);
   rc = mt_det_reduce_launch(partials, slots, 1, D, 2L * D, dw, D, s);
   if (rc != MT_OK) return rc;
@@ -924,35 +884,26 @@ extern "C" int mt_copy_rows_f32(const float* src, long lds, const MtRowMap* smap
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
-extern "C" int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
-                                   const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
-                                   const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M,
-                                   int D, mt_stream_t stream) {
-  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768) return MT_ERR_BAD_ARG;
-  InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
-               make_rowmap(dxmap), dx_accumulate, (h16*)dproj, dgamma, M};
-  hipLaunchKernelGGL(inject_resid_bwd_kernel<768>, dim3(min(cdiv(M, 4), 512)), dim3(256), 0, (hipStream_t)stream, a);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-
-// deterministic twin: partials = [slots][D], slots = workgroups
 extern "C" long mt_inject_resid_bwd_det_elems(int M, int D) {
   if (M <= 0 || D != 768) return MT_ERR_BAD_ARG;
   return (long)min(cdiv(M, 4), 512) * D;
 }
 
-extern "C" int mt_inject_resid_bwd_det(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
-                                       const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
-                                       const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,
-                                       float* partials, long partials_elems, mt_stream_t stream) {
-  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 || !partials ||
-      partials_elems < mt_inject_resid_bwd_det_elems(M, D))
+// opt->partials: the deterministic form, partials = [slots][D], slots = workgroups
+extern "C" int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
+                                   const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
+                                   const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M,
+                                   int D, const MtLaunchOpts* opt, mt_stream_t stream) {
+  if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
+  float* partials = mt_opt_partials(opt);
+  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 ||
+      (partials && opt->partials_elems < mt_inject_resid_bwd_det_elems(M, D)))
     return MT_ERR_BAD_ARG;
   InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
-               make_rowmap(dxmap), dx_accumulate, (h16*)dproj, partials, M};
+               make_rowmap(dxmap), dx_accumulate, (h16*)dproj, partials ? partials : dgamma, M};
   const int slots = min(cdiv(M, 4), 512);
-  hipLaunchKernelGGL((inject_resid_bwd_kernel<768, true>), dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
+  if (!partials) hipLaunchKernelGGL(inject_resid_bwd_kernel<768>, dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((inject_resid_bwd_kernel<768, true>), dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
   MT_CHECK_LAUNCH();
-  return mt_det_reduce_launch(partials, slots, 1, D, D, dgamma, D, (hipStream_t)stream);
+  return partials ? mt_det_reduce_launch(partials, slots, 1, D, D, dgamma, D, (hipStream_t)stream) : MT_OK;
 }

@@ -177,8 +177,8 @@ class Engine:
     DETERMINISTIC_REFUSAL = None      # (a subclass that cannot run the deterministic mode says why: TitanEngine)
 
     def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device="cuda", deterministic: Optional[bool] = None):
-        """deterministic (None: deterministic_default()): the train step runs the `_det` launchers (include/modaltune_hip.h) wherever
-        the default ones sum a parameter gradient over workgroups with fp32 atomics -- the same seed, inputs and pass schedule then
+        """deterministic (None: deterministic_default()): the train step runs the launchers' deterministic forms (include/modaltune_hip.h:
+        MtLaunchOpts.partials) wherever the default ones sum a parameter gradient over workgroups with fp32 atomics -- the same seed, inputs and pass schedule then
         give the same bits in every gradient, run after run, eager or replayed.  Fixed at construction."""
         self.deterministic = deterministic_default() if deterministic is None else bool(deterministic)
         if self.deterministic and self.DETERMINISTIC_REFUSAL:
@@ -475,7 +475,7 @@ class Engine:
         return sp
 
     def _det_elems(self, B: int, Lx: int) -> int:
-        """Deterministic mode: floats of the partial workspace of one (B, Lx) geometry -- the largest need of the patch-side `_det`
+        """Deterministic mode: floats of the partial workspace of one (B, Lx) geometry -- the largest need of the patch-side deterministic
         launches of a step (they run one after the other on the geometry's stream and share it).  The store holds it like every other
         buffer: sized for the largest bag seen, moved (generation bumped) when the store grows."""
         cfg = self.cfg

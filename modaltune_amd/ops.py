@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import MtLongNetLayerBuffers, MtLongNetLayerWeights, MtVitBlockBuffers, MtVitBlockWeights
-from ._lib import MT_SGEMM_MAX, MtDensePlan, MtDilatedPlan, MtDropout, MtGemmEpilogue, MtRowMap, MtSgemm, check, rowmap
+from ._lib import MT_SGEMM_MAX, MtDensePlan, MtDilatedPlan, MtDropout, MtGemmEpilogue, MtLaunchOpts, MtRowMap, MtSgemm, check, rowmap
 
 F16, F32 = 0, 1
 EPI_BIAS, EPI_BIAS_RESID, EPI_INJECT, EPI_POSEMB, EPI_QKV_HM = 0, 1, 2, 3, 4
@@ -75,10 +75,32 @@ def _dr(d):
     return C.byref(d) if d is not None else None
 
 
+def _opts(what="", *, eps=1e-5, live=None, live_rows=0, det=None, grid_wgs=0):
+    """The options pointer of a launcher (include/modaltune_hip.h: MtLaunchOpts): None while every option is at its default -- the
+    default path builds nothing --, else a struct by reference.  live: one site's {b0, b1} of a DropPath live table (int32 tensor of 2);
+    det: the caller's partial workspace of a deterministic form (contiguous fp32 cuda tensor, sized by det_elems)."""
+    if eps == 1e-5 and live is None and det is None and not grid_wgs:
+        return None
+    o = MtLaunchOpts()
+    if eps != 1e-5:
+        if not eps > 0:      # (0 would read as "the default" over there)
+            check(-1, what)
+        o.eps = float(eps)
+    if live is not None:
+        o.live, o.live_rows = live.data_ptr(), int(live_rows)
+    if det is not None:
+        _need(det, torch.float32, "det")
+        if det.numel() == 0:      # (a null workspace would read as "the default form")
+            check(-1, what)
+        o.partials, o.partials_elems = det.data_ptr(), det.numel()
+    o.grid_wgs = int(grid_wgs)
+    return C.byref(o)
+
+
 def gemm_nt(A, W, out, M, N, K, *, lda=None, amap=None, ldc=None, cmap=None, epilogue=EPI_BIAS, bias=None, resid=None,
             ldr=0, rmap=None, colscale=None, pos_table=None, pos_row=None, pos_col=None, drop=None, live=None, live_rows=0):
-    """out = epilogue(A[M,K] @ W[N,K]^T) (include/modaltune_hip.h: mt_gemm_nt_f16; with `live`: mt_gemm_nt_f16_live, only the rows of
-    the live passes are computed and stored)."""
+    """out = epilogue(A[M,K] @ W[N,K]^T) (include/modaltune_hip.h: mt_gemm_nt_f16; with `live` only the rows of the live passes are
+    computed and stored)."""
     epi = MtGemmEpilogue()
     if drop is not None:
         epi.drop = drop
@@ -90,20 +112,16 @@ def gemm_nt(A, W, out, M, N, K, *, lda=None, amap=None, ldc=None, cmap=None, epi
     epi.pos_table = pos_table.data_ptr() if pos_table is not None else None
     epi.pos_row = pos_row.data_ptr() if pos_row is not None else None
     epi.pos_col = pos_col.data_ptr() if pos_col is not None else None
-    if live is not None:
-        check(_lib.load().mt_gemm_nt_f16_live(_p(A), lda if lda is not None else K, _rm(amap), _p(W), M, N, K, epilogue, C.byref(epi), _p(out),
-                                              ldc if ldc is not None else N, _rm(cmap), _dt(out), _p(live), int(live_rows), _s()), "gemm_nt_live")
-        return
     check(_lib.load().mt_gemm_nt_f16(_p(A), lda if lda is not None else K, _rm(amap), _p(W), M, N, K, epilogue,
-                                     C.byref(epi), _p(out), ldc if ldc is not None else N, _rm(cmap), _dt(out), _s()),
-          "gemm_nt")
+                                     C.byref(epi), _p(out), ldc if ldc is not None else N, _rm(cmap), _dt(out),
+                                     _opts(live=live, live_rows=live_rows), _s()), "gemm_nt")
 
 
-# Deterministic twins (include/modaltune_hip.h): the six wrappers below that reduce a parameter gradient over workgroups take
-# det=None | a contiguous fp32 cuda tensor, the caller's partial workspace (sized by det_elems); given one, the `_det` launcher runs:
-# no atomics, bit-reproducible sums.
+# Deterministic forms (include/modaltune_hip.h): the six wrappers below that reduce a parameter gradient over workgroups take
+# det=None | a contiguous fp32 cuda tensor, the caller's partial workspace (sized by det_elems); given one, the launcher runs its
+# deterministic form: no atomics, bit-reproducible sums.
 def det_elems(name: str, *shape) -> int:
-    """Floats of partial workspace the deterministic twin of `name` ("gemm_tn_f16", "colsum_f16", "layernorm_bwd", "inject_resid_bwd",
+    """Floats of partial workspace the deterministic form of `name` ("gemm_tn_f16", "colsum_f16", "layernorm_bwd", "inject_resid_bwd",
     "inject_attn_bwd_hd", "extract_attn_bwd_hd") needs for these shape arguments (include/modaltune_hip.h: mt_<name>_det_elems)."""
     n = getattr(_lib.load(), f"mt_{name}_det_elems")(*shape)
     if n < 0:
@@ -111,27 +129,17 @@ def det_elems(name: str, *shape) -> int:
     return int(n)
 
 
-def _det(det):
-    _need(det, torch.float32, "det")
-    return det.data_ptr(), det.numel()
-
-
 def gemm_tn(A, B, out, M, N1, N2, *, lda=None, amap=None, ldb=None, bmap=None, ldc=None, colsum=None, det=None):
     """out[N1,N2] += A^T B over M rows (weight gradient); colsum[N1] += column sums of A (the bias gradient) on the same pass."""
-    if det is not None:
-        check(_lib.load().mt_gemm_tn_f16_det(_p(A), lda if lda is not None else N1, _rm(amap), _p(B), ldb if ldb is not None else N2,
-                                             _rm(bmap), M, N1, N2, _p(out), ldc if ldc is not None else N2, _p(colsum), *_det(det), _s()),
-              "gemm_tn_det")
-        return
+    what = "gemm_tn" if det is None else "gemm_tn_det"
     check(_lib.load().mt_gemm_tn_f16(_p(A), lda if lda is not None else N1, _rm(amap), _p(B), ldb if ldb is not None else N2,
-                                     _rm(bmap), M, N1, N2, _p(out), ldc if ldc is not None else N2, _p(colsum), _s()), "gemm_tn")
+                                     _rm(bmap), M, N1, N2, _p(out), ldc if ldc is not None else N2, _p(colsum), _opts(what, det=det), _s()),
+          what)
 
 
 def colsum(A, out, M, N, *, lda=None, amap=None, det=None):
-    if det is not None:
-        check(_lib.load().mt_colsum_f16_det(_p(A), lda if lda is not None else N, _rm(amap), M, N, _p(out), *_det(det), _s()), "colsum_det")
-        return
-    check(_lib.load().mt_colsum_f16(_p(A), lda if lda is not None else N, _rm(amap), M, N, _p(out), _s()), "colsum")
+    what = "colsum" if det is None else "colsum_det"
+    check(_lib.load().mt_colsum_f16(_p(A), lda if lda is not None else N, _rm(amap), M, N, _p(out), _opts(what, det=det), _s()), what)
 
 
 def sgemm_problem(A, a_str, B, b_str, Cm, c_str, M, N, K, *, bias=None, bias_on_m=False, act=ACT_NONE, accumulate=False,
@@ -170,41 +178,29 @@ def sgemm(A, a_str, B, b_str, Cm, c_str, M, N, K, **k):
 
 def layernorm_fwd(x, w, b, y, stats, M, D, *, ldx=None, xmap=None, ldy=None, ymap=None, gelu_in=False, add_rows=None,
                   add_period=0, eps=1e-5, live=None, live_rows=0):
-    if live is not None:      # (the reference's epsilon only: the FFN sub-LayerNorm of the LongNet layers)
-        if eps != 1e-5:
-            raise ValueError("layernorm_fwd: a live table goes with the default eps")
-        check(_lib.load().mt_layernorm_fwd_live(_p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(b),
-                                                _p(add_rows), add_period, _p(y), ldy if ldy is not None else D, _rm(ymap), _dt(y),
-                                                _p(stats), M, D, _p(live), int(live_rows), _s()), "layernorm_fwd_live")
-        return
-    check(_lib.load().mt_layernorm_fwd_eps(_p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(b),
-                                           _p(add_rows), add_period, _p(y), ldy if ldy is not None else D, _rm(ymap), _dt(y),
-                                           _p(stats), M, D, float(eps), _s()), "layernorm_fwd")
+    check(_lib.load().mt_layernorm_fwd(_p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(b),
+                                       _p(add_rows), add_period, _p(y), ldy if ldy is not None else D, _rm(ymap), _dt(y),
+                                       _p(stats), M, D, _opts("layernorm_fwd", eps=eps, live=live, live_rows=live_rows), _s()),
+          "layernorm_fwd")
 
 
 def add_layernorm_fwd(x, branch, w, b, h, y, stats, M, D, drop=None, eps=1e-5):
     """h = x + drop(branch); y = fp16(LN(h) * w + b) (include/modaltune_hip.h: mt_add_layernorm_fwd)."""
-    check(_lib.load().mt_add_layernorm_fwd_eps(_p(x), _p(branch), _dr(drop), _p(w), _p(b), _p(h), _p(y), _p(stats), M, D,
-                                               float(eps), _s()), "add_layernorm_fwd")
+    check(_lib.load().mt_add_layernorm_fwd(_p(x), _p(branch), _dr(drop), _p(w), _p(b), _p(h), _p(y), _p(stats), M, D,
+                                           _opts("add_layernorm_fwd", eps=eps), _s()), "add_layernorm_fwd")
 
 
 def layernorm_bwd(dy, x, w, stats, dx, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None, dxmap=None,
                   gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None, det=None, live=None, live_rows=0):
     if live is not None and dw is not None:
         raise ValueError("layernorm_bwd: a live table goes with a frozen norm (dw / db of a trainable one sum over every row)")
-    if det is not None and dw is not None:      # (a frozen norm reduces nothing over workgroups: the default launcher is deterministic)
-        check(_lib.load().mt_layernorm_bwd_det(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x),
-                                               ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats),
-                                               _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate),
-                                               _p(dw), _p(db), _p(dx16), _dr(dx16_drop), M, D, *_det(det), _s()), "layernorm_bwd_det")
-        return
-    args = (_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x), ldx if ldx is not None else D, _rm(xmap), _dt(x), int(gelu_in),
-            _p(w), _p(stats), _p(dx), lddx if lddx is not None else D, _rm(dxmap), _dt(dx), int(accumulate), _p(dw), _p(db), _p(dx16),
-            _dr(dx16_drop), M, D)
-    if live is None:
-        check(_lib.load().mt_layernorm_bwd(*args, _s()), "layernorm_bwd")
-    else:
-        check(_lib.load().mt_layernorm_bwd_live(*args, _p(live), int(live_rows), _s()), "layernorm_bwd_live")
+    if dw is None:      # (a frozen norm reduces nothing over workgroups: the default form is deterministic)
+        det = None
+    what = "layernorm_bwd" if det is None else "layernorm_bwd_det"
+    check(_lib.load().mt_layernorm_bwd(_p(dy), lddy if lddy is not None else D, _rm(dymap), _dt(dy), _p(x), ldx if ldx is not None else D,
+                                       _rm(xmap), _dt(x), int(gelu_in), _p(w), _p(stats), _p(dx), lddx if lddx is not None else D,
+                                       _rm(dxmap), _dt(dx), int(accumulate), _p(dw), _p(db), _p(dx16), _dr(dx16_drop), M, D,
+                                       _opts(what, live=live, live_rows=live_rows, det=det), _s()), what)
 
 
 LIVE_SITES_MAX = 64      # MT_LIVE_SITES_MAX
@@ -220,37 +216,27 @@ def droppath_live(path_sites, path_ps, B, rng, table):
 
 
 def dilated_attn_fwd(qkv, plan, o_br, lse_br, live=None):
-    if live is None:
-        check(_lib.load().mt_dilated_attn_fwd(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _s()), "dilated_attn_fwd")
-    else:
-        check(_lib.load().mt_dilated_attn_fwd_live(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _p(live), _s()), "dilated_attn_fwd_live")
+    check(_lib.load().mt_dilated_attn_fwd(_p(qkv), C.byref(plan), _p(o_br), _p(lse_br), _opts(live=live), _s()), "dilated_attn_fwd")
 
 
-def dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, live=None):
-    args = (_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats), _p(lse_tot))
-    if live is None:
-        check(_lib.load().mt_dilated_mix_ln_fwd(*args, _s()), "dilated_mix_ln_fwd")
-    else:
-        check(_lib.load().mt_dilated_mix_ln_fwd_live(*args, _p(live), _s()), "dilated_mix_ln_fwd_live")
+def dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, live=None, grid_wgs=0):
+    """grid_wgs > 0: that many workgroups (tests, tools/mix_microbench.py): the results do not depend on it."""
+    check(_lib.load().mt_dilated_mix_ln_fwd(_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats), _p(lse_tot),
+                                            _opts(live=live, grid_wgs=grid_wgs), _s()), "dilated_mix_ln_fwd")
 
 
-def dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, live=None):
-    args = (_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats), _p(dmixed), _p(delta_br))
-    if live is None:
-        check(_lib.load().mt_dilated_mix_ln_bwd(*args, _s()), "dilated_mix_ln_bwd")
-    else:
-        check(_lib.load().mt_dilated_mix_ln_bwd_live(*args, _p(live), _s()), "dilated_mix_ln_bwd_live")
+def dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, live=None, grid_wgs=0):
+    check(_lib.load().mt_dilated_mix_ln_bwd(_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats), _p(dmixed),
+                                            _p(delta_br), _opts(live=live, grid_wgs=grid_wgs), _s()), "dilated_mix_ln_bwd")
 
 
 def dilated_mix_ln_fwd_grid(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs=0):
-    """dilated_mix_ln_fwd with the number of workgroups given (tests, tools/mix_microbench.py): the results do not depend on it."""
-    check(_lib.load().mt_dilated_mix_ln_fwd_grid(_p(o_br), _p(lse_br), C.byref(plan), _p(ln_w), _p(ln_b), _p(y), _p(stats),
-                                                 _p(lse_tot), int(grid_wgs), _s()), "dilated_mix_ln_fwd_grid")
+    """dilated_mix_ln_fwd(..., grid_wgs=) under the name the kernel tests and tools/mix_microbench.py call."""
+    dilated_mix_ln_fwd(o_br, lse_br, plan, ln_w, ln_b, y, stats, lse_tot, grid_wgs=grid_wgs)
 
 
 def dilated_mix_ln_bwd_grid(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, grid_wgs=0):
-    check(_lib.load().mt_dilated_mix_ln_bwd_grid(_p(dy), _p(o_br), _p(lse_br), _p(lse_tot), C.byref(plan), _p(ln_w), _p(stats),
-                                                 _p(dmixed), _p(delta_br), int(grid_wgs), _s()), "dilated_mix_ln_bwd_grid")
+    dilated_mix_ln_bwd(dy, o_br, lse_br, lse_tot, plan, ln_w, stats, dmixed, delta_br, grid_wgs=grid_wgs)
 
 
 def dilated_attn_bwd_workspace_bytes(plan) -> int:
@@ -277,11 +263,8 @@ def dilated_attn_bwd_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqk
 def dilated_attn_bwd_inplace_phases(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16, phases=ATTN_BWD_ALL, live=None):
     """The form the layer launcher uses: the dense (ratio 1) branch is written straight into dqkv16 by the KV and Q phases, the
     COMBINE phase (once, after both) adds the sparse branches in place.  Equal inputs give the dqkv16 of dilated_attn_bwd."""
-    args = (_p(qkv), _p(dmixed), _p(lse_tot), _p(delta_br), C.byref(plan), _p(workspace), _p(dqkv16), phases)
-    if live is None:
-        check(_lib.load().mt_dilated_attn_bwd_inplace(*args, _s()), "dilated_attn_bwd_inplace")
-    else:
-        check(_lib.load().mt_dilated_attn_bwd_inplace_live(*args, _p(live), _s()), "dilated_attn_bwd_inplace_live")
+    check(_lib.load().mt_dilated_attn_bwd_inplace(_p(qkv), _p(dmixed), _p(lse_tot), _p(delta_br), C.byref(plan), _p(workspace), _p(dqkv16),
+                                                  phases, _opts(live=live), _s()), "dilated_attn_bwd_inplace")
 
 
 def dilated_attn_bwd(qkv, dmixed, lse_tot, delta_br, plan, workspace, dqkv16):
@@ -485,12 +468,9 @@ def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None, heads=12, head_di
 
 
 def inject_attn_bwd(q, a, lse, da, k, v, dq, dk, dv, M, rows_per_pass, T, heads=12, head_dim=16, det=None):
-    if det is not None:
-        check(_lib.load().mt_inject_attn_bwd_hd_det(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim,
-                                                    _p(dq), _p(dk), _p(dv), *_det(det), _s()), "inject_attn_bwd_det")
-        return
+    what = "inject_attn_bwd" if det is None else "inject_attn_bwd_det"
     check(_lib.load().mt_inject_attn_bwd_hd(_p(q), _p(a), _p(lse), _p(da), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(dq),
-                                            _p(dk), _p(dv), _s()), "inject_attn_bwd")
+                                            _p(dk), _p(dv), _opts(what, det=det), _s()), what)
 
 
 def extract_attn_fwd(q, kv, out, lse, part_acc, part_ml, B, T, L, nsplit, heads=12, head_dim=16):
@@ -500,12 +480,9 @@ def extract_attn_fwd(q, kv, out, lse, part_acc, part_ml, B, T, L, nsplit, heads=
 
 
 def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L, heads=12, head_dim=16, det=None):
-    if det is not None:
-        check(_lib.load().mt_extract_attn_bwd_hd_det(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, heads, head_dim, _p(dq),
-                                                     _p(dkv), *_det(det), _s()), "extract_attn_bwd_det")
-        return
+    what = "extract_attn_bwd" if det is None else "extract_attn_bwd_det"
     check(_lib.load().mt_extract_attn_bwd_hd(_p(q), _p(kv), _p(out), _p(lse), _p(dout), B, T, L, heads, head_dim, _p(dq), _p(dkv),
-                                             _s()), "extract_attn_bwd")
+                                             _opts(what, det=det), _s()), what)
 
 
 def token_mha_fwd(q, k, v, out, probs, B, T, E, heads):
@@ -589,16 +566,11 @@ def copy_rows(src, dst, M, D, *, lds=None, smap=None, ldd=None, dmap=None, accum
 
 def inject_resid_bwd(dy, x, proj, gamma, dx, dproj, dgamma, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None,
                      dxmap=None, dx_accumulate=False, det=None):
-    if det is not None:
-        check(_lib.load().mt_inject_resid_bwd_det(_p(dy), lddy if lddy is not None else D, _rm(dymap), _p(x),
-                                                  ldx if ldx is not None else D, _rm(xmap), _p(proj), _p(gamma), _p(dx),
-                                                  lddx if lddx is not None else D, _rm(dxmap), int(dx_accumulate), _p(dproj),
-                                                  _p(dgamma), M, D, *_det(det), _s()), "inject_resid_bwd_det")
-        return
+    what = "inject_resid_bwd" if det is None else "inject_resid_bwd_det"
     check(_lib.load().mt_inject_resid_bwd(_p(dy), lddy if lddy is not None else D, _rm(dymap), _p(x),
                                           ldx if ldx is not None else D, _rm(xmap), _p(proj), _p(gamma), _p(dx),
                                           lddx if lddx is not None else D, _rm(dxmap), int(dx_accumulate), _p(dproj),
-                                          _p(dgamma), M, D, _s()), "inject_resid_bwd")
+                                          _p(dgamma), M, D, _opts(what, det=det), _s()), what)
 
 
 def l2norm_row(x, y, O):

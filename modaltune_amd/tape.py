@@ -99,7 +99,7 @@ class Tape:
         self.on_realloc: Optional[Callable[[], None]] = None     # owner hook: captured graphs point into the arena
 
     def det_partials(self, op: str, *shape) -> Optional[torch.Tensor]:
-        """The partial workspace for the deterministic twin of `op` at `shape` (None outside the deterministic mode)."""
+        """The partial workspace for the deterministic form of `op` at `shape` (None outside the deterministic mode)."""
         if not self.deterministic:
             return None
         need = ops.det_elems(op, *shape)

@@ -12,7 +12,7 @@ or compose directly.  There is no CPU implementation (the product path has no fa
 Determinism: every op registered here is bit-reproducible as it stands, so torch.use_deterministic_algorithms(True) needs no switch
 in this file -- none of them forwards to a launcher that sums over workgroups with atomics (`layernorm_bwd` is the frozen form: no dw /
 db).  The six launchers that do (ops.gemm_tn, colsum, layernorm_bwd with dw / db, inject_resid_bwd, inject_attn_bwd, extract_attn_bwd)
-have `_det` twins (ops: det=); an op added here on top of one of them has to pass a partial workspace under torch's flag or raise
+have deterministic forms (ops: det=); an op added here on top of one of them has to pass a partial workspace under torch's flag or raise
 (tests/test_deterministic_cpu.py holds this file to that).
 
     import modaltune_amd.torch_ops        # registers the namespace

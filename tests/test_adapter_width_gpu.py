@@ -153,7 +153,7 @@ def test_width_aware_entry_points_equal_their_twins_at_12x16():
         w = torch.zeros(M, T, device=DEV)
         if hd:
             _lib.check(lib.mt_inject_attn_fwd_hd(p(q), M, L, p(k), p(v), T, H, D, p(a), p(lse), s()))
-            _lib.check(lib.mt_inject_attn_bwd_hd(p(q), p(a), p(lse), p(da), M, L, p(k), p(v), T, H, D, p(dq), p(dk), p(dv), s()))
+            _lib.check(lib.mt_inject_attn_bwd_hd(p(q), p(a), p(lse), p(da), M, L, p(k), p(v), T, H, D, p(dq), p(dk), p(dv), None, s()))
             _lib.check(lib.mt_inject_attn_probs_hd(p(q), M, L, p(k), p(lse), T, H, D, p(w), s()))
         else:
             _lib.check(lib.mt_inject_attn_fwd(p(q), M, L, p(k), p(v), T, p(a), p(lse), s()))
@@ -178,7 +178,7 @@ def test_width_aware_entry_points_equal_their_twins_at_12x16():
         w = torch.zeros(B, T, L, device=DEV)
         if hd:
             _lib.check(lib.mt_extract_attn_fwd_hd(p(q), p(kv), B, T, L, H, D, p(out), p(lse), p(pa), p(pm), nsplit, s()))
-            _lib.check(lib.mt_extract_attn_bwd_hd(p(q), p(kv), p(out), p(lse), p(dout), B, T, L, H, D, p(dq), p(dkv), s()))
+            _lib.check(lib.mt_extract_attn_bwd_hd(p(q), p(kv), p(out), p(lse), p(dout), B, T, L, H, D, p(dq), p(dkv), None, s()))
             _lib.check(lib.mt_extract_attn_probs_hd(p(q), p(kv), p(lse), B, T, L, H, D, p(w), s()))
         else:
             _lib.check(lib.mt_extract_attn_fwd(p(q), p(kv), B, T, L, p(out), p(lse), p(pa), p(pm), nsplit, s()))

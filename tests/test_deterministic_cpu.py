@@ -22,7 +22,7 @@ def cdiv(a, b):
 
 
 def _tn_slots(M, N1, N2):
-    """(splits of mt_gemm_tn_f16_det that hold rows, splits launched).  csrc/gemm.hip: 64 x 64 tiles, ~1024 workgroups (512 for fewer
+    """(splits of the deterministic mt_gemm_tn_f16 that hold rows, splits launched).  csrc/gemm.hip: 64 x 64 tiles, ~1024 workgroups (512 for fewer
     than 16 tiles), at least 256 rows per split, a multiple of the 8 XCDs -- the default form's launch; the 32-row steps are dealt out
     evenly over the first min(steps, launched) splits."""
     tiles = (N1 // 64) * (N2 // 64)
@@ -157,8 +157,13 @@ def test_torch_ops_forward_to_no_atomic_launcher():
 
 
 def test_abi_lists_a_twin_and_a_query_for_each_of_the_six():
+    """The deterministic form of each of the six is an option of the base entry (MtLaunchOpts.partials), not an entry of its own: the
+    options pointer stands directly in front of the stream, and the size query is there."""
     from modaltune_amd import _lib
+    assert [f for f, _ in _lib.MtLaunchOpts._fields_][3:5] == ["partials", "partials_elems"]
+    assert dict(_lib.MtLaunchOpts._fields_)["partials_elems"] is _lib.L
     for n in ("mt_gemm_tn_f16", "mt_colsum_f16", "mt_layernorm_bwd", "mt_inject_resid_bwd", "mt_inject_attn_bwd_hd", "mt_extract_attn_bwd_hd"):
-        assert _lib.SIGNATURES[n + "_det"][:-3] == _lib.SIGNATURES[n][:-1]                    # the default arguments ...
-        assert _lib.SIGNATURES[n + "_det"][-3:] == [_lib.P, _lib.L, _lib.P]                   # ... + partials, partials_elems, stream
+        assert n + "_det" not in _lib.SIGNATURES
+        assert _lib.SIGNATURES[n][-2:] == [_lib.C.POINTER(_lib.MtLaunchOpts), _lib.P]         # ... options, stream
+        assert _lib.SIGNATURES[n + "_det_elems"] and all(t is _lib.I for t in _lib.SIGNATURES[n + "_det_elems"])
         assert _lib._RESTYPE[n + "_det_elems"] is _lib.C.c_long

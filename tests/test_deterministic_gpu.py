@@ -1,4 +1,4 @@
-"""GPU: the deterministic twins (`mt_*_det`, include/modaltune_hip.h) of the six launchers that sum a parameter gradient over workgroups
+"""GPU: the deterministic forms (MtLaunchOpts.partials, include/modaltune_hip.h; ops: det=) of the six launchers that sum a parameter gradient over workgroups
 with fp32 atomics.  Every case checks
 
   (a) the reduced outputs against the float64 restatement tests/test_kernels_gpu.py uses for the default form, at the bar that test

@@ -228,7 +228,7 @@ SENT = 7.0
 
 @pytest.mark.parametrize("b0,b1", [(0, 3), (1, 3), (0, 2), (1, 2), (0, 0), (2, 3)])
 def test_attention_forward_live_rows(rigs, b0, b1):
-    """mt_dilated_attn_fwd_live: rows of the passes in [b0, b1) equal the full launch, every other row keeps the sentinel."""
+    """mt_dilated_attn_fwd with a live entry: rows of the passes in [b0, b1) equal the full launch, every other row keeps the sentinel."""
     rig = rigs(3)
     plan = rig.eng._attention_plan(N, 3)
     nb, M = plan.nbranch, 3 * N
@@ -275,9 +275,39 @@ def test_ffn_layernorm_live_rows(rigs, b0, b1):
         assert bool((got[:r0] == SENT).all()) and bool((got[r1:] == SENT).all())
 
 
+def test_ffn_layernorm_live_rows_with_an_explicit_eps():
+    """A live entry and an epsilon in one call (one MtLaunchOpts; the fp16 GELU form, D = 3072, 3 passes of 5 rows): the live rows have
+    the bits of the same call without a table, the other rows keep the sentinel, and the epsilon is the one given -- inputs of standard
+    deviation 1e-3 leave a row variance of about 2.5e-7 behind the GELU, so rstd at 1e-6 is about 3 times that at 1e-5."""
+    _gpu()
+    rows, F = 5, 3072
+    M = 3 * rows
+    g = torch.Generator(device="cuda").manual_seed(15)
+    x = (torch.randn(M, F, device="cuda", generator=g) * 1e-3).half()
+    w = torch.rand(F, device="cuda", generator=g) + 0.5
+    b = torch.randn(F, device="cuda", generator=g) * 0.1
+    y_full, st_full = torch.empty_like(x), torch.empty(M, 2, device="cuda")
+    ops.layernorm_fwd(x, w, b, y_full, st_full, M, F, gelu_in=True, eps=1e-6)
+    y_ref, st_ref = torch.empty_like(x), torch.empty(M, 2, device="cuda")
+    ops.layernorm_fwd(x, w, b, y_ref, st_ref, M, F, gelu_in=True)          # eps = 1e-5
+    torch.cuda.synchronize()
+    ratio = st_full[:, 1] / st_ref[:, 1]
+    assert float(ratio.min()) > 2.0 and not torch.equal(y_full, y_ref), ratio
+    for b0, b1 in ((1, 3), (0, 3), (0, 0)):
+        live = torch.tensor([b0, b1], dtype=torch.int32, device="cuda")
+        y, st = torch.full_like(x, SENT), torch.full((M, 2), SENT, device="cuda")
+        ops.layernorm_fwd(x, w, b, y, st, M, F, gelu_in=True, eps=1e-6, live=live, live_rows=rows)
+        torch.cuda.synchronize()
+        r0, r1 = b0 * rows, b1 * rows
+        for got, full, other in ((y, y_full, y_ref), (st, st_full, st_ref)):
+            assert torch.equal(got[r0:r1], full[r0:r1]), (b0, b1)
+            assert bool((got[:r0] == SENT).all()) and bool((got[r1:] == SENT).all()), (b0, b1)
+            assert r0 == r1 or not torch.equal(got[r0:r1], other[r0:r1]), (b0, b1)
+
+
 @pytest.mark.parametrize("b0,b1", [(0, 3), (1, 2), (0, 0), (0, 1)])
 def test_residual_layernorm_backward_counts_dead_dy_as_zero(rigs, b0, b1):
-    """mt_layernorm_bwd_live on the residual stream (D = 768, accumulating, with the fp16 copy): NaN dy rows outside the live passes give
+    """mt_layernorm_bwd with a live entry on the residual stream (D = 768, accumulating, with the fp16 copy): NaN dy rows outside the live passes give
     what exact-zero dy rows give -- dh unchanged there, dx_f16 written."""
     _gpu()
     M, D = 3 * N, 768
@@ -315,7 +345,7 @@ GEMM_CASES = [
 
 @pytest.mark.parametrize("rows,Nn,K,epi,with_bias", GEMM_CASES)
 def test_gemm_live_rows(rows, Nn, K, epi, with_bias):
-    """mt_gemm_nt_f16_live: rows of the passes in [b0, b1) are torch.equal to the full launch -- the row tiles are laid from row
+    """mt_gemm_nt_f16 with a live entry: rows of the passes in [b0, b1) are torch.equal to the full launch -- the row tiles are laid from row
     b0 * rows on, a row's bits do not depend on that, and the head-major epilogue places it by its global row -- and every other row of
     C keeps the sentinel."""
     _gpu()

@@ -1,6 +1,10 @@
 """Build the C-ABI library of another git revision next to the working-tree one, for same-box A/B timing:
     python tools/build_ref_lib.py HEAD build_variants/base/libmodaltune_hip.so
-The A/B itself: tools/ab_lib.sh <libA.so> <libB.so> <script> [args]  (MODALTUNE_HIP_LIB selects the library)."""
+The A/B itself: tools/ab_lib.sh <libA.so> <libB.so> <script> [args]  (MODALTUNE_HIP_LIB selects the library).
+This tree's Python (_lib.SIGNATURES, ops.py) drives both libraries, so the other revision must share this tree's C ABI: same entry
+points, same argument lists (mt_version() tells the major number).  Across a commit that changes the ABI -- the one that moved the optional
+inputs into MtLaunchOpts (mt_version 3.0) is one -- a library of the far side fails to bind or is called with the wrong arguments: A/B
+whole trees instead (a checkout of each revision, each with its own build and its own Python)."""
 import os
 import subprocess
 import sys
