@@ -564,6 +564,25 @@ int mt_adamw_step(float* p, const float* g, float* m, float* v, long n, double l
 int mt_scaler_update(float* scale, int* growth_tracker, int* found_inf, int* step_dev /* ++ on a clean step, or NULL */,
                      float growth, float backoff, int interval, mt_stream_t stream);
 int mt_check_finite(const float* g, long n, int* found_inf, mt_stream_t stream);
+/* Global-norm clipping (torch.nn.utils.clip_grad_norm_, norm_type 2) without a host read-back.
+ * mt_grad_sumsq: sumsq[0] = sum of g[i]^2 over n floats (g 4-byte aligned, any n >= 1), squared and summed in DOUBLE from the first
+ * element: finite inputs never overflow and the same input gives the same bits.  Two launches, no floating-point atomics: every
+ * stage-1 workgroup stores its sum into its own slot of `partials` (device doubles, at least mt_grad_sumsq_partials_elems(n) of them,
+ * no initialisation needed), one workgroup adds the slots in ascending order.  *found_inf (device int, or NULL) is ORed with 1 when an
+ * element is not finite -- mt_check_finite's rule (+-FLT_MAX and subnormals are finite; never cleared here) -- so at a step that
+ * clips this launch stands in for mt_check_finite. */
+int mt_grad_sumsq(const float* g, long n, double* partials, long partials_elems, double* sumsq, int* found_inf, mt_stream_t stream);
+/* host arithmetic: the slots mt_grad_sumsq needs for n elements (non-decreasing in n); negative for n <= 0 */
+long mt_grad_sumsq_partials_elems(long n);
+/* One thread, double arithmetic, each output rounded once to fp32: S = sumsq[0] + ... + sumsq[nsums - 1] (ascending);
+ *   out[0] = total_norm = sqrt(S) * grad_mult / *scale (scale NULL: 1): the norm of the unscaled, averaged gradient
+ *   out[1] = coef = min(1, max_norm / (total_norm + 1e-6))
+ *   out[2] = *scale / coef: hand `out + 2` to mt_adamw_step as its `scale` and it applies g * grad_mult * coef / *scale
+ * coef == 1 leaves out[2] = *scale bit for bit (an unclipped step is today's arithmetic); so do max_norm = +inf (report the norm
+ * only), a set *found_inf (device int or NULL; the step is skipped anyway) and a non-finite S.  A finite gradient whose norm
+ * overflows fp32: total_norm = +inf, coef = 0, out[2] = +inf (the update sees a zero gradient, as with torch). */
+int mt_grad_clip_coef(const double* sumsq, int nsums, double grad_mult, const float* scale, double max_norm, const int* found_inf,
+                      float* out, mt_stream_t stream);
 
 /* Measurement aid (bench.py, SURVEY §8d "the builder's own MFMA micro-benchmark peak"): `workgroups` x 4 waves each issue
  * iters x 4 independent v_mfma_f32_32x32x16_f16 on non-trivial register operands = workgroups * 4 * iters * 4 * 32768 FLOP. */
@@ -575,7 +594,7 @@ int mt_mfma_probe(float* sink, int workgroups, int iters, mt_stream_t stream);
  * stream, without a host read-back.  s[0] is clamped to [2^-126, 2^126] (a maximum below ~target / FLT_MAX would otherwise
  * give s[0] = inf, s[1] = 0): s[0] and s[1] are finite, positive normal numbers for every input. */
 int mt_absmax_scale(const float* x, long n, float target, float* s, mt_stream_t stream);
-/* y[i] = a[i] + (*alpha) * b[i] with alpha a DEVICE scalar (a may be NULL: y = (*alpha) * b) */
+/* y[i] = a[i] + (*alpha) * b[i] with alpha a DEVICE scalar (a may be NULL: y = (*alpha) * b); y may be a or b (in place) */
 int mt_axpy_dev(const float* a, const float* b, const float* alpha, float* y, long n, mt_stream_t stream);
 /* LongNetViT.coords_to_pos (SE:198-211) on the device: prow[i] = floor(coords[i][0] / tile), pcol[i] = floor(coords[i][1]
  * / tile) for fp32 coords [L, 2]; cells outside [0, ngrids) are clamped and *err (device int, or NULL) is OR-ed with 1 --

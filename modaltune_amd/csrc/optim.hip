@@ -89,6 +89,98 @@ __global__ void check_finite_kernel(const float* __restrict__ g, long n, int* __
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(found_inf, 1);
 }
 
+// Sum of squares of the flat gradient, stage 1: workgroup b stores the double sum of its grid-stride share into partials[b] (a plain
+// store into its own slot: the workspace needs no initialisation, nothing is added with atomics).  Squares and sums are double from
+// the first element: finite fp32 inputs cannot overflow (2^24 * FLT_MAX^2 < 2^281) and the result does not depend on fp32 association.
+// `g` is 4-byte aligned: workgroup 0 takes the `head` scalars in front of the first 16-byte boundary and the `tail` scalars behind the
+// last whole float4; everything between is read as float4, four loads in flight per thread.  The cross-wave step goes through LDS
+// as doubles only (one LDS banking class, common.h).
+constexpr int SUMSQ_THREADS = 256, SUMSQ_UNROLL = 4, SUMSQ_MAX_WGS = 2048;
+constexpr long SUMSQ_WG_ELEMS = (long)SUMSQ_THREADS * SUMSQ_UNROLL * 4;      // elements of one workgroup before the grid stride
+
+MT_DEVINL double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+MT_DEVINL double sq4(f32x4 x) {
+  const double a = (double)x[0], b = (double)x[1], c = (double)x[2], d = (double)x[3];
+  return fma(a, a, fma(b, b, fma(c, c, d * d)));
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_partials_kernel(const float* __restrict__ g, long n, int head, long nvec,
+                                                                            double* __restrict__ partials) {
+  __shared__ double red[SUMSQ_THREADS / MT_WAVE];
+  const int tid = threadIdx.x;
+  const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
+  const long stride = (long)gridDim.x * SUMSQ_THREADS;
+  double acc = 0.0;
+  long v = (long)blockIdx.x * SUMSQ_THREADS + tid;
+  for (; v + 3 * stride < nvec; v += 4 * stride) {
+    const f32x4 x0 = gv[v], x1 = gv[v + stride], x2 = gv[v + 2 * stride], x3 = gv[v + 3 * stride];
+    acc += (sq4(x0) + sq4(x1)) + (sq4(x2) + sq4(x3));
+  }
+  for (; v < nvec; v += stride) acc += sq4(gv[v]);
+  if (blockIdx.x == 0) {
+    const long tail0 = head + 4 * nvec;
+    if (tid < head) { const double x = (double)g[tid]; acc = fma(x, x, acc); }
+    if (tail0 + tid < n) { const double x = (double)g[tail0 + tid]; acc = fma(x, x, acc); }      // (n - tail0 <= 3)
+  }
+  acc = wave_sum_f64(acc);
+  if ((tid & (MT_WAVE - 1)) == 0) red[tid / MT_WAVE] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = red[0];
+#pragma unroll
+    for (int w = 1; w < SUMSQ_THREADS / MT_WAVE; ++w) s += red[w];
+    partials[blockIdx.x] = s;
+  }
+}
+
+// Stage 2, one workgroup: thread t adds the slots [t * per, (t + 1) * per) in ascending order, thread 0 adds the 256 thread sums in
+// ascending order.  A sum of squares is non-finite exactly when an element was (inf^2 = +inf, squares never cancel): that is the flag,
+// ORed like mt_check_finite's and never cleared.
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_final_kernel(const double* __restrict__ partials, int nparts,
+                                                                         double* __restrict__ sumsq, int* __restrict__ found_inf) {
+  __shared__ double red[SUMSQ_THREADS];
+  const int tid = threadIdx.x, per = (nparts + SUMSQ_THREADS - 1) / SUMSQ_THREADS;
+  double s = 0.0;
+  for (int i = tid * per; i < min(nparts, (tid + 1) * per); ++i) s += partials[i];
+  red[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double t = red[0];
+    for (int i = 1; i < SUMSQ_THREADS; ++i) t += red[i];
+    sumsq[0] = t;
+    if (found_inf && !isfinite(t)) atomicOr(found_inf, 1);
+  }
+}
+
+// torch.nn.utils.clip_grad_norm_'s coefficient on the device, one thread, double throughout, each output rounded once:
+//   out[0] = total_norm = sqrt(sum of the slots, ascending) * grad_mult / *scale
+//   out[1] = coef = min(1, max_norm / (total_norm + 1e-6));   out[2] = *scale / coef: the `scale` mt_adamw_step then divides by
+// coef == 1 (also: max_norm = +inf, a set found_inf, a non-finite sum) leaves out[2] = *scale bit for bit; a finite gradient whose norm
+// overflows fp32 gives total_norm = +inf and coef = 0 (out[2] = +inf: AdamW sees g * 0), as torch does.
+__global__ void grad_clip_coef_kernel(const double* __restrict__ sumsq, int nsums, double grad_mult, const float* __restrict__ scale,
+                                      double max_norm, const int* __restrict__ found_inf, float* __restrict__ out) {
+  if (threadIdx.x || blockIdx.x) return;
+  double S = sumsq[0];
+  for (int i = 1; i < nsums; ++i) S += sumsq[i];
+  const float sc = scale ? *scale : 1.0f;
+  const double norm = sqrt(S) * grad_mult / (double)sc;
+  const float normf = (float)norm;
+  float coef = 1.0f, eff = sc;
+  if (isfinite(S) && !(found_inf && *found_inf) && !isinf(max_norm)) {
+    if (isinf(normf)) { coef = 0.0f; eff = __builtin_inff(); }
+    else {
+      const double c = fmin(1.0, max_norm / (norm + 1e-6));
+      coef = (float)c;
+      if (coef != 1.0f) eff = (float)((double)sc / c);
+    }
+  }
+  out[0] = normf; out[1] = coef; out[2] = eff;
+}
+
 // y[r] = x[r] / ||x[r]||_2 : one workgroup per row (text / ||text||, TM:213)
 __global__ __launch_bounds__(256) void l2norm_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int O) {
   __shared__ float red[256];
@@ -137,9 +229,10 @@ __global__ __launch_bounds__(256) void absmax_scale_kernel(const float* __restri
   }
 }
 
-// y = a + (*alpha) * b (a may be null: y = (*alpha) * b)
-__global__ void axpy_dev_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ alpha,
-                                float* __restrict__ y, long n) {
+// y = a + (*alpha) * b (a may be null: y = (*alpha) * b).  In place, y == b (optim.clip_grad_norm_: g *= coef) or y == a, is
+// supported: a thread reads index i of its inputs before it writes index i and touches no other index -- so `a`, `b` and `y` carry no
+// __restrict__.
+__global__ void axpy_dev_kernel(const float* a, const float* b, const float* __restrict__ alpha, float* y, long n) {
   const float al = *alpha;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     y[i] = (a ? a[i] : 0.f) + al * b[i];
@@ -258,6 +351,39 @@ extern "C" int mt_check_finite(const float* g, long n, int* found_inf, mt_stream
   if (!g || !found_inf || n <= 0) return MT_ERR_BAD_ARG;
   const int grid = (int)((n + 1023) / 1024 > 2048 ? 2048 : (n + 1023) / 1024);
   hipLaunchKernelGGL(check_finite_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, n, found_inf);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+// stage-1 workgroups = slots of the workspace: a pure function of n
+extern "C" long mt_grad_sumsq_partials_elems(long n) {
+  if (n <= 0) return MT_ERR_BAD_ARG;
+  const long wgs = (n + SUMSQ_WG_ELEMS - 1) / SUMSQ_WG_ELEMS;
+  return wgs > SUMSQ_MAX_WGS ? SUMSQ_MAX_WGS : wgs;
+}
+
+extern "C" int mt_grad_sumsq(const float* g, long n, double* partials, long partials_elems, double* sumsq, int* found_inf,
+                             mt_stream_t stream) {
+  if (!g || !partials || !sumsq || n <= 0) return MT_ERR_BAD_ARG;
+  if (((uintptr_t)g & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)sumsq & 7)) return MT_ERR_BAD_ARG;
+  const int grid = (int)mt_grad_sumsq_partials_elems(n);
+  if (partials_elems < grid) return MT_ERR_BAD_ARG;
+  long head = (long)(((16 - ((uintptr_t)g & 15)) & 15) / 4);
+  if (head > n) head = n;
+  const long nvec = (n - head) / 4;
+  hipLaunchKernelGGL(grad_sumsq_partials_kernel, dim3(grid), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, g, n, (int)head, nvec, partials);
+  MT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_sumsq_final_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, (const double*)partials, grid, sumsq,
+                     found_inf);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_grad_clip_coef(const double* sumsq, int nsums, double grad_mult, const float* scale, double max_norm,
+                                 const int* found_inf, float* out, mt_stream_t stream) {
+  if (!sumsq || !out || nsums < 1 || !(max_norm >= 0.0) || !(grad_mult > 0.0)) return MT_ERR_BAD_ARG;
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sumsq, nsums, grad_mult, scale, max_norm,
+                     found_inf, out);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }

@@ -125,6 +125,7 @@ class GradReducer:
         self.views = [[flat_grad[o:o + n] for o, n in bk] for bk in buckets]
         self.pending: list = []
         self.started: set = set()
+        self.collectives = 0                  # collectives issued so far (a micro-step of an accumulation window issues none)
         self.param = flat_param
         self.sharded = bool(self.active and shard_last and flat_param is not None and len(buckets) > 0)
         self._param_pending: list = []
@@ -148,6 +149,7 @@ class GradReducer:
         if self.sharded and b == len(self.buckets) - 1:
             for o, s, out in self._rs:
                 src = self.flat[o:o + self.world * s]
+                self.collectives += 1
                 if self._host:
                     h = torch.empty(s, dtype=src.dtype)
                     dist.reduce_scatter_tensor(h, src.cpu(), op=dist.ReduceOp.SUM, group=self.group)
@@ -155,9 +157,11 @@ class GradReducer:
                 else:
                     self.pending.append(dist.reduce_scatter_tensor(out, src, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
             for o, n in self._tails:
+                self.collectives += 1
                 self.pending.append(dist.all_reduce(self.flat[o:o + n], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
             return
         for v in self.views[b]:
+            self.collectives += 1
             self.pending.append(dist.all_reduce(v, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def start_rest(self):
@@ -180,7 +184,24 @@ class GradReducer:
         """found_inf must be the same on every rank (GradScaler skips the WHOLE step): with a sharded bucket a rank only sees
         its own slice of the sums, so the flags are MAX-reduced (4 bytes)."""
         if self.sharded:
+            self.collectives += 1
             dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=self.group)
+
+    def sync_sumsq_(self, shard_sums: torch.Tensor):
+        """Global-norm clipping with a sharded bucket: a rank holds the reduced gradient of its own shards only, so the float64
+        sums of squares over them (the trailing slots of `norm_pieces`) are SUM-reduced; the slots of everything else were formed from
+        all-reduced gradients and are equal on every rank already.  Every rank then adds the same slots in the same order: one
+        coefficient, bit for bit.  A collective: beside sync_flag_, never inside a captured graph."""
+        if self.sharded and shard_sums.numel():
+            self.collectives += 1
+            dist.all_reduce(shard_sums, op=dist.ReduceOp.SUM, group=self.group)
+
+    def norm_pieces(self, n_flat: int):
+        """(`adam_pieces` reordered -- the ranges every rank holds reduced first, this rank's shards last --, number of the former)."""
+        pieces = self.adam_pieces(n_flat)
+        mine = {(o + self.rank * s, s) for o, s, _ in self._rs} if self.sharded else set()
+        shared = [p for p in pieces if p not in mine]
+        return shared + [p for p in pieces if p in mine], len(shared)
 
     def adam_pieces(self, n_flat: int) -> List[tuple]:
         """(offset, length) ranges of the flat buffers THIS rank's optimiser step updates: everything outside the sharded
@@ -205,6 +226,7 @@ class GradReducer:
             return
         W, r = self.world, self.rank
         for o, s, _ in self._rs:
+            self.collectives += 1
             full = self.param[o:o + W * s]
             mine = self.param[o + r * s:o + (r + 1) * s]
             if self._host:

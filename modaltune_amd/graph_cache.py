@@ -23,7 +23,10 @@ Real data has a new bag length almost every slide, so a geometry (the owner's ke
               capture_end() with its own exception swallowed.
 
 Users: trainer.TrainStep (the whole step, cut at the gradient-bucket joins when world > 1, and the optimiser graph as a second capture
-into the same pool), module_graph.ModuleReplay (forward and backward as a pair: one cut) and evaluate.EmbeddingExtractor (one graph
+into the same pool; with an accumulation window, accumulate > 1, the owner's key is (geometry, ROLE) -- role = (the call zeroes the
+gradient buffer, the call is the boundary that reduces and runs the optimiser) -- so visits, admission and the LRU all count
+(geometry, role) pairs: a hot geometry is admitted and captured once per role it is met in, at most three, and `size` bounds those
+captures, not the geometries), module_graph.ModuleReplay (forward and backward as a pair: one cut) and evaluate.EmbeddingExtractor (one graph
 under torch.cuda.graph: only the pool handle comes from here).  What is captured, the key and the entry stay with the owner.
 """
 import gc

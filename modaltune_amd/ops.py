@@ -645,6 +645,22 @@ def check_finite(g, n, found_inf):
     check(_lib.load().mt_check_finite(_p(g), n, _p(found_inf), _s()), "check_finite")
 
 
+def grad_sumsq_partials_elems(n: int) -> int:
+    return int(_lib.load().mt_grad_sumsq_partials_elems(n))
+
+
+def grad_sumsq(g, n, partials, sumsq, found_inf=None):
+    """sumsq[0] (float64) = sum of g[:n] ** 2; `partials`: float64 workspace of at least grad_sumsq_partials_elems(n) elements;
+    found_inf is ORed when an element is not finite (include/modaltune_hip.h: mt_grad_sumsq)."""
+    check(_lib.load().mt_grad_sumsq(_p(g), n, _p(partials), partials.numel(), _p(sumsq), _p(found_inf), _s()), "grad_sumsq")
+
+
+def grad_clip_coef(sumsq, nsums, grad_mult, scale, max_norm, found_inf, out):
+    """out[0:3] (fp32) = total norm, clip coefficient, *scale / coefficient (include/modaltune_hip.h: mt_grad_clip_coef)."""
+    check(_lib.load().mt_grad_clip_coef(_p(sumsq), nsums, float(grad_mult), _p(scale), float(max_norm), _p(found_inf), _p(out), _s()),
+          "grad_clip_coef")
+
+
 # ------------------------------------------------------------------------------------------------
 # Optional per-kernel timing with HIP events on the launch stream (bench.py --> roofline.achieved).
 # TIMER maps "<op>[shape]" -> list of (start_event, end_event); None = disabled (zero overhead path).

@@ -25,6 +25,91 @@ import torch
 from . import ops
 
 
+def _param_span(ps):
+    """(lowest address, fp32 elements up to the highest end) when `ps` are contiguous fp32 CUDA tensors of ONE storage that fill their
+    span (gaps allowed: ParamStore pads slots to 16 bytes), else None."""
+    if not ps or any(p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() for p in ps):
+        return None
+    base = ps[0].untyped_storage().data_ptr()
+    if any(p.untyped_storage().data_ptr() != base for p in ps):
+        return None
+    lo = min(p.data_ptr() for p in ps)
+    n = (max(p.data_ptr() + p.numel() * 4 for p in ps) - lo) // 4
+    # everything inside the span that is not a parameter must be padding an update may touch: true for ParamStore.flat (its gaps
+    # are zero-filled slot padding); refuse anything that is mostly holes (a few tensors of a much larger storage)
+    if (lo - base) % 16 or n <= 0 or sum(p.numel() for p in ps) < 0.95 * n:
+        return None
+    return lo, n
+
+
+def _flat_grad_view(ps, lo: int, n: int) -> Optional[torch.Tensor]:
+    """The gradients of `ps` as ONE flat tensor laid out like the parameters' span (lo, n) -- what the module bridge hands autograd --
+    else None.  The one test of "the gradients are one flat buffer": AdamW.step and clip_grad_norm_ share it."""
+    g0 = ps[0].grad
+    if g0 is None or g0.dtype != torch.float32 or not g0.is_cuda:
+        return None
+    gst = g0.untyped_storage()
+    gbase = gst.data_ptr()
+    delta = g0.data_ptr() - ps[0].data_ptr()
+    for p in ps:
+        g = p.grad
+        if g is None or g.dtype != torch.float32 or not g.is_contiguous() or g.data_ptr() - p.data_ptr() != delta \
+                or g.untyped_storage().data_ptr() != gbase:
+            return None
+    glo = lo + delta
+    if glo < gbase or glo + n * 4 > gbase + gst.nbytes() or (glo - gbase) % 4:
+        return None
+    return torch.empty(0, dtype=torch.float32, device=g0.device).set_(gst, (glo - gbase) // 4, (n,), (1,))
+
+
+def _fills_span(ps, lo: int, n: int) -> bool:
+    """`ps` ARE the span: sorted by address, every tensor starts less than 16 bytes behind the end of the one before it (ParamStore's
+    slot padding) and the last one ends the span.  A list that leaves out a tensor of the buffer -- whose gradient would then be counted
+    in the norm and scaled with the rest -- fails this (a slot is at least 16 bytes)."""
+    cur = lo
+    for p in sorted(ps, key=lambda t: t.data_ptr()):
+        if not 0 <= p.data_ptr() - cur < 16:
+            return False
+        cur = p.data_ptr() + p.numel() * 4
+    return cur == lo + n * 4
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:
+    """`torch.nn.utils.clip_grad_norm_` for the reference-style loop (scaler.unscale_(opt); clip; scaler.step(opt)).
+
+    When the gradients are one flat buffer laid out like the parameters (the drop-in modules; the test AdamW.step makes), `parameters`
+    are ALL the tensors of that buffer (a subset is torch's call: its norm is over the listed tensors only) and norm_type is 2, three launches replace torch's walk over 244 to 1 544 tensors: mt_grad_sumsq (sum of squares in double),
+    mt_grad_clip_coef (min(1, max_norm / (norm + 1e-6))) and one in-place mt_axpy_dev g *= coef.  The norm comes back as a 0-d device
+    tensor and nothing synchronises with the host unless error_if_nonfinite is set.  Anything else -- another norm_type, CPU tensors,
+    gradients in separate allocations -- is torch's own call, unchanged.
+
+    One difference from torch on the fast path: non-finite gradients are left as they are (coefficient 1) where torch multiplies them
+    by NaN; GradScaler skips the step either way."""
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    ps = list(parameters)
+    g = None
+    if float(norm_type) == 2.0 and ps and all(p.grad is not None for p in ps):
+        span = _param_span(ps)
+        g = _flat_grad_view(ps, *span) if span is not None and _fills_span(ps, *span) else None
+    if g is None:
+        return torch.nn.utils.clip_grad_norm_(ps, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    n = g.numel()
+    sumsq = torch.empty(1, dtype=torch.float64, device=g.device)
+    ws = torch.empty(ops.grad_sumsq_partials_elems(n), dtype=torch.float64, device=g.device)
+    out = torch.empty(3, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        ops.grad_sumsq(g, n, ws, sumsq)
+        ops.grad_clip_coef(sumsq, 1, 1.0, None, float(max_norm), None, out)
+        if error_if_nonfinite and not bool(torch.isfinite(out[0])):
+            raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be "
+                               "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                               "`error_if_nonfinite=False`")
+        ops.axpy_dev(None, g, out[1:2], g, n)
+    return out[0]
+
+
 class AdamW(torch.optim.AdamW):
     _step_supports_amp_scaling = True          # GradScaler.step: leave unscaling and the skip decision to step() (grad_scale / found_inf)
 
@@ -62,21 +147,12 @@ class AdamW(torch.optim.AdamW):
         AdamW leaves at zero)?  If so, build the flat moment buffers and make every parameter's optimiser state a VIEW of them, so
         `state_dict()` / `load_state_dict()` / a later torch step see ordinary per-parameter AdamW state."""
         ps = self._all_params()
-        if not ps or any(p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() for p in ps):
+        span = _param_span(ps)
+        if span is None:
             return None
+        lo, n = span
         st = ps[0].untyped_storage()
         base = st.data_ptr()
-        if any(p.untyped_storage().data_ptr() != base for p in ps):
-            return None
-        lo = min(p.data_ptr() for p in ps)
-        hi = max(p.data_ptr() + p.numel() * 4 for p in ps)
-        n = (hi - lo) // 4
-        if (lo - base) % 16 or n <= 0:
-            return None
-        # everything inside [lo, hi) that is not a parameter must be padding the update may touch: true for ParamStore.flat (its
-        # gaps are zero-filled slot padding); refuse anything that is mostly holes (a few tensors of a much larger storage)
-        if sum(p.numel() for p in ps) < 0.95 * n:
-            return None
         dev = ps[0].device
         m = torch.zeros(n, dtype=torch.float32, device=dev)
         v = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -112,22 +188,7 @@ class AdamW(torch.optim.AdamW):
 
     def _flat_grad(self, fl) -> Optional[torch.Tensor]:
         """The gradients as ONE flat tensor laid out like the parameters (what the module bridge hands autograd), else None."""
-        ps = self._all_params()
-        g0 = ps[0].grad
-        if g0 is None or g0.dtype != torch.float32 or not g0.is_cuda:
-            return None
-        gst = g0.untyped_storage()
-        gbase = gst.data_ptr()
-        delta = g0.data_ptr() - ps[0].data_ptr()
-        for p in ps:
-            g = p.grad
-            if g is None or g.dtype != torch.float32 or not g.is_contiguous() or g.data_ptr() - p.data_ptr() != delta \
-                    or g.untyped_storage().data_ptr() != gbase:
-                return None
-        glo = fl["lo"] + delta
-        if glo < gbase or glo + fl["n"] * 4 > gbase + gst.nbytes() or (glo - gbase) % 4:
-            return None
-        return torch.empty(0, dtype=torch.float32, device=g0.device).set_(gst, (glo - gbase) // 4, (fl["n"],), (1,))
+        return _flat_grad_view(self._all_params(), fl["lo"], fl["n"])
 
     def _sync_steps(self):
         if self._steps_dirty and self._flat is not None:

@@ -40,8 +40,26 @@ class TrainStep:
     def __init__(self, engine: Engine, lr: float = 1e-4 / 20, weight_decay: float = 0.01, betas=(0.9, 0.999),
                  eps: float = 1e-8, init_scale: float = 2.0 ** 15, growth_interval: int = 2000,
                  process_group=None, task_ids: Sequence[int] = (0, 1, 2), text_rows: Sequence[int] = (0, 1, 3),
-                 graph_cache_size: int = 8, capture_after: int = 2, split_passes="auto"):
+                 graph_cache_size: int = 8, capture_after: int = 2, split_passes="auto", accumulate: int = 1,
+                 max_grad_norm: Optional[float] = None):
         self.engine, self.dev = engine, engine.device
+        # Gradient accumulation and global-norm clipping.  A WINDOW is `accumulate` consecutive calls of step() / step_graphed(), mixed
+        # freely: calls 1 .. k-1 are micro-steps (dropout counter, forward, loss, backward ADDING into the flat gradient buffer; no
+        # collective, no optimiser, no scaler update), the k-th is the boundary (reduce, inf check, AdamW, scaler update) and applies
+        # the MEAN over the window: grad_mult = 1 / (world * k).  The loss scale therefore cannot move inside a window and one inf
+        # anywhere in it skips the whole window's update (torch's accumulate-then-scaler.step).  max_grad_norm: at the boundary
+        # mt_grad_sumsq stands in for mt_check_finite, mt_grad_clip_coef forms torch's clip_grad_norm_ coefficient on the device and
+        # AdamW divides by `scale / coef` -- nothing is read back; float("inf") only reports the norm.  `window_pos` (micro-steps the
+        # open window holds) is HOST state.  accumulate == 1 and max_grad_norm None: the step as it always was, launch for launch.
+        if int(accumulate) < 1 or (max_grad_norm is not None and not float(max_grad_norm) >= 0.0):
+            raise ValueError(f"accumulate must be >= 1 and max_grad_norm >= 0 (got {accumulate}, {max_grad_norm})")
+        self.accumulate = int(accumulate)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.window_pos = 0
+        self._clip_out = torch.zeros(3, dtype=F32, device=self.dev)      # mt_grad_clip_coef's {total norm, coefficient, scale / coefficient}
+        self.grad_norm, self.clip_coef = self._clip_out[0:1], self._clip_out[1:2]      # (written at a boundary, when max_grad_norm is set)
+        self._clip_scale = self._clip_out[2:3]
+        self._sumsq = self._sumsq_ws = None      # float64: one sum-of-squares slot per optimiser piece, mt_grad_sumsq's workspace
         self.wd, self.betas, self.eps = weight_decay, betas, eps
         n = engine.store.n_flat
         self.m = torch.zeros(n, dtype=F32, device=self.dev)
@@ -71,9 +89,13 @@ class TrainStep:
         # data-parallel reducer (buckets in the order the backward finalises them)
         nint = len(engine.cfg.interaction_indexes)
         self._nint = nint
+        # (MT_DP_SHARD_LAST=0: the last bucket is all-reduced like the others instead of reduce-scattered -- the reducer's other form)
         self.reducer = dp.GradReducer(engine.store.flat_grad, dp.grad_buckets(engine.store.slots, nint, n), process_group,
-                                      flat_param=engine.store.flat)
+                                      flat_param=engine.store.flat, shard_last=os.environ.get("MT_DP_SHARD_LAST", "1") != "0")
         engine.store.sync = self.reducer.wait_params      # state_dict() / a forward outside the step see complete parameters
+        if self.max_grad_norm is not None:      # (allocated here: never inside a capture)
+            self._sumsq = torch.zeros(len(self.reducer.norm_pieces(n)[0]), dtype=torch.float64, device=self.dev)
+            self._sumsq_ws = torch.empty(ops.grad_sumsq_partials_elems(n), dtype=torch.float64, device=self.dev)
         self._gcache = GraphCache(graph_cache_size, capture_after)      # the captured bag geometries: key -> _Captured
         self._opt_graph, self._opt_gen = None, -1      # world > 1: the optimiser's graph and the generation it was captured under
         self._cap, self._cap_buckets = None, []      # the graph_cache.Capture of a step in progress, the bucket behind each of its cuts
@@ -205,8 +227,10 @@ class TrainStep:
             return True
         return self.split_decisions[L] if L in self.split_decisions else L >= self.split_min_patches
 
-    def _fwd_bwd_split(self, x, coords, genes, text, clinical, staged_geometry=None, reduce: bool = True):
-        """_fwd_bwd with the task passes in two concurrent groups (see __init__)."""
+    def _fwd_bwd_split(self, x, coords, genes, text, clinical, staged_geometry=None, reduce: bool = True, zero: bool = True,
+                       micro: bool = False):
+        """_fwd_bwd with the task passes in two concurrent groups (see __init__).  zero False (a window's later micro-steps): the
+        store's own set keeps what the window holds -- the extra sets are zeroed as ever and sum_sets adds them into it."""
         eng, pg, ngroups = self.engine, self._pg, len(self._groups)
         if self._loss_parts is None:
             pg.ensure(ngroups)
@@ -248,13 +272,13 @@ class TrainStep:
         pg.fork(ngroups)
         # per-bucket joins: the groups' backwards advance stage by stage so that a bucket's all-reduce starts as soon as BOTH groups
         # have left its interaction block (see __init__: dp_schedule)
-        joined = (self._dp() and self.dp_schedule == "groups_joined" and reduce) or self.force_bucket_joins
+        joined = ((self._dp() and self.dp_schedule == "groups_joined" and reduce) or self.force_bucket_joins) and not micro
         eng.record_markers = bool(joined)
         calls, summed = [], set()
         self.buckets_started_early = 0
         try:
             for gi, (a, b) in enumerate(self._groups):
-                with pg.group(gi, zero="all"):
+                with pg.group(gi, zero="all" if zero else "extra"):
                     own = dict(need_grad=True, staged=True, clinical=clinical, share=share, tape=pg.tapes[gi], site_group=gi + 1,
                                ws_slot=self._group_slots[gi])
                     if titan:
@@ -310,17 +334,20 @@ class TrainStep:
             ops.axpy(self.loss, part, 1.0, self.loss)
         self.last_logits = logits_all
 
-    def _fwd_bwd(self, x, coords, genes, text, clinical, staged_geometry=None, reduce: bool = True):
+    def _fwd_bwd(self, x, coords, genes, text, clinical, staged_geometry=None, reduce: bool = True, zero: bool = True, micro: bool = False):
+        """Forward, loss and backward of one slide.  zero: the flat gradient buffer is cleared first (False: a window's later
+        micro-steps add to it); micro: a micro-step of an accumulation window -- like reduce False, and no bucket join either."""
         eng = self.engine
         Lnow = staged_geometry[1] if staged_geometry is not None else (x.reshape(-1, x.shape[-1]).shape[0] if torch.is_tensor(x) else None)
         if self._split_now(Lnow):
-            return self._fwd_bwd_split(x, coords, genes, text, clinical, staged_geometry, reduce=reduce)
+            return self._fwd_bwd_split(x, coords, genes, text, clinical, staged_geometry, reduce=reduce, zero=zero, micro=micro)
         self._wait_params()               # the all-gather of the last step's sharded parameter update (no-op otherwise)
         eng.grad_ready_hook = self._on_grad_ready if (reduce and self._dp()) else None
         if eng.stochastic:
             ops.rng_advance(eng.rng)          # a fresh set of dropout / DropPath masks per step
         target = self.project_text(text)
-        eng.store.flat_grad.zero_()
+        if zero:
+            eng.store.flat_grad.zero_()
         if hasattr(eng, "forward_slide"):      # TITAN configuration: gridding + backbone embed first (staged: gridding already done)
             logits = eng.forward_slide(x, coords, genes, self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=True,
                                        clinical=clinical, staged=staged_geometry is not None)
@@ -353,18 +380,43 @@ class TrainStep:
         """GradScaler's inf check over what this rank holds; with a sharded last bucket the flag is MAX-reduced so that every
         rank takes the same skip decision (a collective: never inside a captured graph)."""
         eng = self.engine
-        ops.check_finite(eng.store.flat_grad, eng.store.n_flat, self.found_inf)
+        if self.max_grad_norm is not None:
+            # clipping: the sums of squares of what this rank holds stand in for the check; the slots of its shards are SUM-reduced
+            # (as doubles) so that every rank forms the same coefficient -- both collectives outside any captured graph
+            self.reducer.sync_sumsq_(self._grad_sumsq())
+        else:
+            ops.check_finite(eng.store.flat_grad, eng.store.n_flat, self.found_inf)
         self.reducer.sync_flag_(self.found_inf)
 
-    def _adam_and_refresh(self, world: int, check: bool = True):
+    def _grad_sumsq(self) -> torch.Tensor:
+        """mt_grad_sumsq over every range this rank's optimiser step reads (reducer.norm_pieces: the shards' slots last), one slot
+        each; found_inf is ORed on the way.  Returns the slots of the shards (empty without a sharded bucket)."""
+        n = self.engine.store.n_flat
+        pieces, shared = self.reducer.norm_pieces(n)
+        g = self.engine.store.flat_grad
+        for i, (o, k) in enumerate(pieces):
+            ops.grad_sumsq(g[o:o + k], k, self._sumsq_ws, self._sumsq[i:i + 1], self.found_inf)
+        return self._sumsq[shared:]
+
+    def _adam_and_refresh(self, world: int, check: bool = True, micro_steps: Optional[int] = None):
+        """Inf check (unless the caller ran it), clip coefficient, AdamW over the MEAN of the `micro_steps` (default: `accumulate`)
+        slides of the window on every rank, scaler update, weight-cache refresh."""
         eng = self.engine
         n = eng.store.n_flat
-        if check:
+        grad_mult = 1.0 / (world * (self.accumulate if micro_steps is None else micro_steps))
+        clip = self.max_grad_norm is not None
+        if check and clip:
+            self._grad_sumsq()
+        elif check:
             ops.check_finite(eng.store.flat_grad, n, self.found_inf)
+        scale = self.scale
+        if clip:
+            ops.grad_clip_coef(self._sumsq, self._sumsq.numel(), grad_mult, self.scale, self.max_grad_norm, self.found_inf, self._clip_out)
+            scale = self._clip_scale      # = scale / coef (scale itself, bit for bit, when nothing is clipped)
         p, g = eng.store.flat, eng.store.flat_grad
         for o, k in self.reducer.adam_pieces(n):      # one launch, or: everything but the sharded bucket + this rank's shards
             ops.adamw_step(p[o:o + k], g[o:o + k], self.m[o:o + k], self.v[o:o + k], k, self._lr, self.betas[0], self.betas[1], self.eps,
-                           self.wd, 0, scale=self.scale, found_inf=self.found_inf, grad_mult=1.0 / world, step_dev=self.step_dev,
+                           self.wd, 0, scale=scale, found_inf=self.found_inf, grad_mult=grad_mult, step_dev=self.step_dev,
                            lr_dev=self.lr_dev)
         ops.scaler_update(self.scale, self.tracker, self.found_inf, self.step_dev, 2.0, 0.5, self.growth_interval)
         eng.refresh_trainable_caches()
@@ -382,7 +434,7 @@ class TrainStep:
         if e0 is not None:
             self.comm_events.append(("param", e0, self._mark()))
 
-    def optimizer_step(self):
+    def optimizer_step(self, micro_steps: Optional[int] = None):
         """Launch whatever buckets the backward has not started, wait for the collectives, AdamW + weight-cache refresh; with
         a sharded last bucket (world > 1) the updated shards are then all-gathered asynchronously (waited for at the top of the
         next step)."""
@@ -394,18 +446,39 @@ class TrainStep:
         if e0 is not None:
             self.comm_events.append(("grad", e0, self._mark()))
         if self.reducer.sharded:
-            self._adam_and_refresh(world, check=False)
+            self._adam_and_refresh(world, check=False, micro_steps=micro_steps)
             self.reducer.start_param_gather()
         else:
-            self._adam_and_refresh(world)
+            self._adam_and_refresh(world, micro_steps=micro_steps)
+
+    def _window_role(self):
+        """(first, boundary) of the call about to run: first -- the window is empty, the gradient buffer is zeroed; boundary -- the
+        call that completes the window and runs the optimiser.  accumulate == 1: (True, True) always."""
+        return self.window_pos == 0, self.window_pos + 1 >= self.accumulate
 
     def step(self, x, coords, genes, text, update: bool = True, clinical=None) -> torch.Tensor:
-        """One train step on one slide, eager launches.  Returns the (device) loss scalar; no host sync happens here."""
-        self._fwd_bwd(x, coords, genes, text, clinical, reduce=update)
+        """One train step on one slide, eager launches.  Returns the (device) loss scalar; no host sync happens here.  With
+        accumulate > 1 the call is a micro-step or the boundary of its window (see __init__); update=False (gradients only, nothing
+        else moves) has no meaning inside a window and raises there."""
+        if self.accumulate > 1 and not update:
+            raise ValueError("step(update=False) is not defined with accumulate > 1: micro-steps accumulate by themselves")
+        first, boundary = self._window_role()
+        self._fwd_bwd(x, coords, genes, text, clinical, reduce=update and boundary, zero=first, micro=not boundary)
         self.eager_steps += 1
-        if update:
+        if not boundary:
+            self.window_pos += 1
+        elif update:
             self.optimizer_step()
+            self.window_pos = 0
         return self.loss
+
+    def finish_window(self):
+        """Apply a partial window (an epoch ended inside it): the boundary's reduce, check, clip and AdamW over the MEAN of the
+        micro-steps seen, eagerly.  A no-op on an empty window.  Data parallel: every rank calls it at the same position."""
+        if self.window_pos == 0:
+            return
+        seen, self.window_pos = self.window_pos, 0
+        self.optimizer_step(micro_steps=seen)
 
     # ------------------------------------------------------------------ hipGraph replay of the whole step
     def step_graphed(self, x, coords, genes, text, clinical=None) -> torch.Tensor:
@@ -456,33 +529,44 @@ class TrainStep:
             self._opt_graph = None
         # (the data-parallel schedule is part of the key: bench.py --gpus N times the three schedules one after the other)
         key = (L, Lv, world, bool(eng.stochastic), self.dp_schedule if dp_on else None, self.force_bucket_joins)
+        first, boundary = self._window_role()
+        if self.accumulate > 1:
+            # the capture ROLE of the call is part of the key: a window's first call zeroes the gradient buffer, its later ones add to
+            # it, only the boundary carries the reducer cuts and the optimiser -- a recurring geometry is captured once per role it is
+            # met in (at most three: first, middle, boundary) and `graph_cache_size` counts (geometry, role) captures, not geometries.
+            # accumulate == 1 has the one role, with or without clipping: the keys are what they were.
+            key += ((first, boundary),)
         ent = cache.get(key)
-        if (self.auto_split and not dp_on and Lv not in self.split_decisions and B >= 3 and Lv >= 2048 and self._can_split()
+        if (self.auto_split and not dp_on and first and Lv not in self.split_decisions and B >= 3 and Lv >= 2048 and self._can_split()
                 and (ent is None or ent.segs is None) and cache.visits.get(key, 0) >= cache.capture_after
                 and not torch.cuda.is_current_stream_capturing()):
             self._trial_split(x, coords, genes, text, clinical, Lv, key)     # (sets split_decisions[Lv]; training state untouched)
             return self.step_graphed(x, coords, genes, text, clinical=clinical)
 
         def fwd_bwd():
-            self._fwd_bwd(None, None, self._sgenes, self._stext, self._sclin, staged_geometry=(B, Lv))
+            self._fwd_bwd(None, None, self._sgenes, self._stext, self._sclin, staged_geometry=(B, Lv), reduce=boundary, zero=first,
+                          micro=not boundary)
 
+        next_pos = 0 if boundary else self.window_pos + 1      # (window_pos moves behind the work, as in step(): a call that raises leaves it)
         if ent is None or ent.segs is None:
             if not cache.admit(key):              # eager visits (allocator, lazy kernel attributes, the tape's gradient arena
                 fwd_bwd()                         # sized from the last step)
                 self.eager_steps += 1
-                self.optimizer_step()
+                if boundary:
+                    self.optimizer_step()
+                self.window_pos = next_pos
                 return self.loss
             if ent is None:
                 ent = _Captured(gen)
                 cache.put(key, ent)               # (evicts BEFORE the capture: it may reuse the evicted graphs' blocks)
-            self._capture(ent, fwd_bwd, world)
+            self._capture(ent, fwd_bwd, world, boundary)
         for g, bucket in ent.segs:
             g.replay()
             if bucket is not None:
                 self.reducer.start(bucket)
         self.last_logits = ent.logits
         self.graph_replays += 1
-        if dp_on:
+        if dp_on and boundary:
             e0 = self._mark()
             self.reducer.start_rest()
             self.reducer.wait()
@@ -492,6 +576,7 @@ class TrainStep:
                 self.comm_events.append(("grad", e0, self._mark()))
             self._opt_graph.replay()
             self.reducer.start_param_gather()
+        self.window_pos = next_pos
         return self.loss
 
     def _trial_split(self, x, coords, genes, text, clinical, L: int, key: tuple, reps: int = 3):
@@ -499,11 +584,25 @@ class TrainStep:
         and each capture replayed `reps` times behind one untimed replay.  Eager timings do not rank the two (the groups' ~1 300 eager
         launches are partly host-bound: 18.8 / 19.0 ms eager against 18.4 / 17.7 replayed at L = 4 096).  The replays are real steps, so
         every piece of training state they touch -- weights, moments, step count, loss scale, dropout counter -- is saved in front and
-        restored behind them (lr is irrelevant then); the winner's capture is kept for the step that follows."""
+        restored behind them (lr is irrelevant then); the winner's capture is kept for the step that follows.
+        With accumulate > 1 the trial runs at a window's FIRST position only (the gradient buffer holds nothing the window needs) and
+        times whole steps: `accumulate` is 1 while it runs, so every replay is a complete first-and-boundary step under the key
+        without a role; window_pos is 0 before and after, and those captures are dropped (no window of k > 1 replays that role).  While
+        it runs the LRU holds one entry more, so the throw-away capture evicts no live (geometry, role) capture.  The decision is for
+        the geometry, but it reaches a role's capture only if that role is captured after the trial: a later position of the window
+        that was captured earlier, under the threshold rule, keeps its schedule until its capture is retired -- a window may mix
+        schedules as it may mix geometries, the gradients add up either way."""
         import time
         eng = self.engine
-        saved = [(t, t.clone()) for t in (eng.store.flat, self.m, self.v, self.step_dev, self.scale, self.tracker, self.found_inf, eng.rng)]
+        saved = [(t, t.clone()) for t in (eng.store.flat, self.m, self.v, self.step_dev, self.scale, self.tracker, self.found_inf, eng.rng,
+                                          self._clip_out)]
         was_auto, self.auto_split = self.auto_split, False
+        k_window = self.accumulate
+        if k_window > 1:
+            assert self.window_pos == 0
+            self.accumulate, key = 1, key[:-1]
+            self._gcache.size += 1
+            self._gcache.visits[key] = max(self._gcache.visits.get(key, 0), self._gcache.capture_after)
         counters = (self.graph_replays, self.eager_steps)
         res, caps = {}, {}
         try:
@@ -519,7 +618,10 @@ class TrainStep:
                 res["groups" if split else "batched"] = round(1e3 * (time.perf_counter() - t0) / reps, 3)
                 caps[split] = self._gcache.get(key)
         finally:
-            self.auto_split = was_auto
+            self.auto_split, self.accumulate, self.window_pos = was_auto, k_window, 0
+            if k_window > 1:
+                self._gcache.pop(key)
+                self._gcache.size -= 1
             self.graph_replays, self.eager_steps = counters
             for t, c in saved:
                 t.copy_(c)
@@ -527,7 +629,7 @@ class TrainStep:
         win = res["groups"] < res["batched"]
         self.split_decisions[L] = win
         self.split_trials[L] = res
-        if caps.get(win) is not None:
+        if k_window == 1 and caps.get(win) is not None:
             self._gcache.put(key, caps[win])      # (if the generation moved while it was held outside, get() never returns it and the next sync drops it)
 
     @property
@@ -536,18 +638,18 @@ class TrainStep:
         segs = [e.segs for e in self._gcache.entries.values() if e.segs is not None]
         return segs or None
 
-    def _capture(self, ent: _Captured, fwd_bwd, world: int):
+    def _capture(self, ent: _Captured, fwd_bwd, world: int, boundary: bool = True):
         torch.cuda.synchronize()
         with self._gcache.capture() as cap:
             self._cap, self._cap_buckets = cap, []
             try:
                 fwd_bwd()
-                if not self._dp():
+                if boundary and not self._dp():
                     self.optimizer_step()
             finally:
                 self._cap = None
         segs, logits = list(zip(cap.graphs, self._cap_buckets + [None])), self.last_logits
-        if self._dp() and self._opt_graph is None:
+        if boundary and self._dp() and self._opt_graph is None:
             with self._gcache.capture() as cap:
                 self._adam_and_refresh(world, check=not self.reducer.sharded)
             self._opt_graph, self._opt_gen = cap.graphs[0], ent.generation
@@ -567,7 +669,9 @@ class TrainStep:
 
     def unscaled_grads(self) -> Dict[str, torch.Tensor]:
         """The last step's gradients divided by the loss scale THEY carry (`grad_scale`) -- not by `scale`, which after an
-        update=True step that backed off or grew is already the next step's.  After a skipped step they are not finite."""
+        update=True step that backed off or grew is already the next step's.  After a skipped step they are not finite.
+        With accumulate > 1 this is the SUM over the micro-steps the window holds so far (after a boundary: the whole window's sum,
+        not its mean), and it is never clipped: max_grad_norm acts inside AdamW, the buffer keeps the raw gradient."""
         s = float(self.grad_scale)
         return {k: g / s for k, g in self.engine.store.grads.items()}
 
