@@ -51,7 +51,7 @@ typedef struct {
 } MtLaunchOpts;
 
 /* major * 100 + minor * 10.  3.0: the optional inputs of a launcher travel in MtLaunchOpts; the suffixed twin entries (_eps, _det, _grid,
- * _live) of 2.x are gone, so a 2.x caller does not link against this library. */
+ * _live) of 2.x are gone, so a 2.x caller does not link against this library.  3.1: + mt_token_mha_fwd_drop / _bwd_drop. */
 int mt_version(void);
 const char* mt_status_string(int status);
 /* Build provenance: sha256 (hex) over the kernel sources, this header and the compiler flags the library was built from
@@ -488,6 +488,17 @@ int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int 
                      float* probs, mt_stream_t stream);
 int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B,
                      int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream);
+/* The same with nn.MultiheadAttention(dropout = p) in train() (AM:42-52; the prompt_dropout key): the softmax probabilities are dropped
+ * before the value product, out = (P o m / (1 - p)) V.  m is the element-dropout keep mask of drop->site over the flat [B, heads, T, T]
+ * tensor -- element (b, h, i, j) has linear index ((b heads + h) T + i) T + j, so mt_dropout_f32 over one row of B heads T T ones
+ * (rounded up to a multiple of 4) with the same MtDropout returns exactly m / (1 - p).  probs keeps the PRE-dropout softmax (the
+ * attention maps and the backward read it); the backward regenerates m: dV = P~^T dO, dP = (dO V^T) o m / (1 - p), then delta and dS
+ * from P and that dP.  drop NULL, rng NULL or p == 0: the entries above, bit for bit.  p outside [0, 1) or path_p != 0 (there is no
+ * DropPath at this site): MT_ERR_BAD_ARG. */
+int mt_token_mha_fwd_drop(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,
+                          float* probs, const MtDropout* drop, mt_stream_t stream);
+int mt_token_mha_bwd_drop(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B,
+                          int T, int E, int heads, float* dq, float* dk, float* dv, const MtDropout* drop, mt_stream_t stream);
 
 /* Attention maps of the adapter attentions (forward only): the head-averaged softmax that nn.MultiheadAttention returns with
  * need_weights=True, recomputed from the operands and the LSE the forward kept -- the scores are rounded as the forward rounds

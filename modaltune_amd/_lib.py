@@ -120,6 +120,8 @@ SIGNATURES = {
     "mt_extract_attn_bwd_hd": [P, P, P, P, P, I, I, I, I, I, P, P, OP, P],
     "mt_token_mha_fwd": [P, P, P, I, I, I, I, P, P, P],
     "mt_token_mha_bwd": [P, P, P, P, P, I, I, I, I, P, P, P, P],
+    "mt_token_mha_fwd_drop": [P, P, P, I, I, I, I, P, P, DR, P],
+    "mt_token_mha_bwd_drop": [P, P, P, P, P, I, I, I, I, P, P, P, DR, P],
     "mt_extract_attn_probs": [P, P, P, I, I, I, P, P],
     "mt_inject_attn_probs": [P, I, I, P, P, I, P, P],
     "mt_extract_attn_probs_hd": [P, P, P, I, I, I, I, I, P, P],

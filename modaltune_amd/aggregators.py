@@ -248,7 +248,8 @@ class LongNetGeneAdapter(Aggregator):
         if getattr(self, "_ns_pending", None):
             self._drain_decodes(block=True)      # a mode switch ends a loop: every deferred task-token check has to have been seen
         if hasattr(self, "engine"):
-            self.engine.stochastic = bool(mode) and (self.cfg.dropout > 0 or self.cfg.drop_path_rate > 0)
+            self.engine.stochastic = bool(mode) and (self.cfg.dropout > 0 or self.cfg.drop_path_rate > 0 or
+                                                     (self.cfg.prompt_dropout > 0 and self.cfg.use_prompt_sa))
         return self
 
     # ---- parameter / state_dict surface under the reference's key names

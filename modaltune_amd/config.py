@@ -113,6 +113,10 @@ class ModelConfig:
         return int(self.interaction_indexes[0][0])
 
     def validate(self):
+        pd = float(self.prompt_dropout)
+        if not (0.0 <= pd < 1.0):      # (NaN fails both comparisons)
+            raise ValueError(f"prompt_dropout={self.prompt_dropout}: a dropout probability in [0, 1) (nn.Dropout refuses values outside "
+                             "[0, 1], and 1 leaves nothing to scale)")
         if self.embed_dim != 768 or self.head_dim != 48:
             raise ValueError("the HIP path is built for the Prov-GigaPath geometry (768-d, 16 heads x 48)")
         if self.prompt_agg not in ("avg", "cls") or self.token_agg not in ("sum", "cat"):

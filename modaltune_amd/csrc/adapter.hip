@@ -674,9 +674,29 @@ MT_DEVINL f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p);
 // that loop is in the 8 / 16-byte banking class (common.h: no counted lgkmcnt wait may span both classes).
 MT_DEVINL int mha_t4(int T) { return (T + 3) & ~3; }
 MT_DEVINL int mha_s1(int T) { const int t4 = mha_t4(T); return ((t4 >> 2) & 1) ? t4 : t4 + 4; }
-template <int HD>
+// DROP (nn.MultiheadAttention(dropout = p) in train(): dropout on the softmax, adapter_modules.py:42-52): P~ = P o m / (1 - p), m the
+// element-dropout keep mask of drop.site at linear index ((b heads + h) T + i) T + j -- the mask mt_dropout_f32 draws over the flat
+// [B heads T T] tensor.  The workgroup's T x T keep flags live in LDS as a BIT image, built once before the first barrier: byte x holds the
+// elements of linear index 8 (base / 8 + x) .. + 7 (base = the head's first element; two Philox calls, each yielding four consecutive
+// elements), so element (i, j) is bit (base & 7) + i T + j.  Writers store bytes, readers load 4-byte words: one banking class.
+// mha_keep_bytes(T): the image's LDS, a multiple of four that covers the word of the last bit (2052 bytes at T = 128).
+__host__ __device__ __forceinline__ int mha_keep_bytes(int T) { return (((T * T + 14) >> 3) + 3) & ~3; }
+MT_DEVINL uint32_t lds_u32(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
+MT_DEVINL void mha_keep_image(uint32_t* mb, int T, uint64_t base, const DropArgs& d, int tid) {
+  uint8_t* mb8 = reinterpret_cast<uint8_t*>(mb);
+  const uint64_t g0 = base >> 3;
+  const int nb = (int)(((base & 7) + (uint64_t)T * T + 7) >> 3);
+  const uint32_t thr = drop_threshold(d.p);
+  for (int x = tid; x < nb; x += 512) {
+    const uint64_t idx4 = (g0 + x) * 2;
+    mb8[x] = (uint8_t)(drop_keep4(d, idx4, thr) | (drop_keep4(d, idx4 + 1, thr) << 4));
+  }
+}
+MT_DEVINL bool mha_keep(const uint32_t* mb, int bit) { return (lds_u32(mb + (bit >> 5)) >> (bit & 31)) & 1u; }
+template <int HD, bool DROP = false>
 __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
-                                                            int T, int E, int heads, float* __restrict__ out, float* __restrict__ probs) {
+                                                            int T, int E, int heads, float* __restrict__ out, float* __restrict__ probs,
+                                                            DropArgs drop) {
   constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;      // C4: 16-byte chunks per row; DS: dims a thread owns in the value sweep
   constexpr float ASCALE = AdDim<HD>::SCALE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -685,6 +705,9 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
   float* vs = ks + T * AD;          // [T4][HD], rows T .. T4 - 1 zero
   float* ss = vs + T4 * AD;         // [T][S1], entries T .. T4 - 1 of a row zero
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3;
+  uint32_t* mb = reinterpret_cast<uint32_t*>(ss + T * S1);      // DROP: the keep-bit image, mha_keep_bytes(T)
+  const uint64_t mbase = ((uint64_t)b * heads + h) * T * T;
+  if constexpr (DROP) mha_keep_image(mb, T, mbase, drop, tid);
   for (int i = tid; i < T4 * C4; i += 512) {
     const int tt = i / C4, c = (i % C4) * 4;
     if (tt < T) {
@@ -727,7 +750,17 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
     l += __shfl_xor(l, 2, 64);
     const float inv = 1.0f / l;
     float* pr = probs + (((long)b * heads + h) * T + t) * T;
-    for (int j = sub; j < T; j += 4) { const float p = ss[t * S1 + j] * inv; ss[t * S1 + j] = p; pr[j] = p; }
+    if constexpr (DROP) {      // probs keeps P (the backward and the attention maps read it), the value sweep sees P~; a dropped entry is
+      const float keep = 1.f / (1.f - drop.p);      // selected to 0, never multiplied by it
+      const int bit0 = (int)(mbase & 7) + t * T;
+      for (int j = sub; j < T; j += 4) {
+        const float p = ss[t * S1 + j] * inv;
+        pr[j] = p;
+        ss[t * S1 + j] = mha_keep(mb, bit0 + j) ? p * keep : 0.f;
+      }
+    } else {
+      for (int j = sub; j < T; j += 4) { const float p = ss[t * S1 + j] * inv; ss[t * S1 + j] = p; pr[j] = p; }
+    }
   }
   __syncthreads();          // a row's four writers -> its four readers
   if (act) {
@@ -753,10 +786,16 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
 //   0  Q, K, V, dO, dS, P      T <= 127 at HD = 16, <= 114 at 32, <= 92 at 64
 //   1  Q, K, V, dO, dS         P read from global memory: every T <= 128 at 16 and 32, T <= 111 at 64
 //   2  V, dO, dS               P, Q and K read from global memory (L2-resident: T x HD floats per head): the rest, HD = 64 and T > 111
-template <int HD, int FORM>
+// DROP (the forward's P~ = P o m / (1 - p); probs holds P): dV = P~^T dO, dP = (dO V^T) o m / (1 - p), delta and dS from P and that dP -- a
+// dropped probability still receives -P delta.  The keep-bit image of the forward (mha_keep_image, regenerated from (rng, site, index))
+// sits behind the images above: + mha_keep_bytes(T), so the DROP instantiations change form one token earlier where the sum was
+// within 2 KiB of the limit:
+//   0  T <= 126 at HD = 16, <= 113 at 32, <= 92 at 64        1  every T <= 128 at 16 and 32, T <= 110 at 64        2  the rest
+template <int HD, int FORM, bool DROP = false>
 __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                             const float* __restrict__ probs, const float* __restrict__ dout, int T, int E,
-                                                            int heads, float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv) {
+                                                            int heads, float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
+                                                            DropArgs drop) {
   constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;
   constexpr float ASCALE = AdDim<HD>::SCALE;
   constexpr bool PL = FORM == 0, GQK = FORM == 2;
@@ -769,6 +808,10 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
   float* pls = dss + T * (T + 1);   // [T][T + 1]  P (FORM 0 only)
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3, S1 = T + 1;
   const float* pbase = probs + ((long)b * heads + h) * T * T;
+  uint32_t* mb = reinterpret_cast<uint32_t*>(PL ? pls + T * (T + 1) : pls);      // DROP: the keep-bit image, mha_keep_bytes(T)
+  const uint64_t mbase = ((uint64_t)b * heads + h) * T * T;
+  const float keep = DROP ? 1.f / (1.f - drop.p) : 1.f;
+  if constexpr (DROP) mha_keep_image(mb, T, mbase, drop, tid);
   for (int i = tid; i < T * C4; i += 512) {
     const int tt = i / C4, c = (i % C4) * 4;
     const long o = ((long)b * T + tt) * E + h * AD + c;
@@ -801,7 +844,16 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
       dss[t * S1 + j] = dp;
     }
     float delta = 0.f;
-    for (int j = sub; j < T; j += 4) delta = fmaf(lds_f32(&pr[j]), lds_f32(&dss[t * S1 + j]), delta);
+    if constexpr (DROP) {      // dP = dP~ o m / (1 - p), written back over the thread's own entries (4-byte class: mask words, P, dP)
+      const int bit0 = (int)(mbase & 7) + t * T;
+      for (int j = sub; j < T; j += 4) {
+        const float dp = mha_keep(mb, bit0 + j) ? lds_f32(&dss[t * S1 + j]) * keep : 0.f;
+        dss[t * S1 + j] = dp;
+        delta = fmaf(lds_f32(&pr[j]), dp, delta);
+      }
+    } else {
+      for (int j = sub; j < T; j += 4) delta = fmaf(lds_f32(&pr[j]), lds_f32(&dss[t * S1 + j]), delta);
+    }
     delta += __shfl_xor(delta, 1, 64);
     delta += __shfl_xor(delta, 2, 64);
     for (int j = sub; j < T; j += 4) dss[t * S1 + j] = lds_f32(&pr[j]) * (lds_f32(&dss[t * S1 + j]) - delta) * ASCALE;
@@ -821,7 +873,8 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
       const float dsk = lds_f32(&dss[j * S1 + t]);
 #pragma unroll
       for (int x = 0; x < DS / 4; ++x) ak[x] += dsk * lds_f32x4_by_dword(qr + j * rst + 4 * x);
-      const float pv = lds_f32(&pc[j * pst]);
+      float pv = lds_f32(&pc[j * pst]);
+      if constexpr (DROP) pv = mha_keep(mb, (int)(mbase & 7) + j * T + t) ? pv * keep : 0.f;      // P~[j][t]
 #pragma unroll
       for (int x = 0; x < DS / 4; ++x) av[x] += pv * lds_f32x4_by_dword(dos + j * AD + DS * sub + 4 * x);
     }
@@ -1139,46 +1192,61 @@ int launch_inject_probs(const h16* q, int rows_per_pass, int B, const float* k, 
   return MT_OK;
 }
 
+// d: the softmax dropout (make_drop of the entry's MtDropout); inactive = the DROP = false kernel, which never reads it
+template <int HD, bool DROP>
+int launch_token_fwd_drop(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out, float* probs,
+                          const DropArgs& d, hipStream_t stream) {
+  const int T4 = (T + 3) & ~3, S1 = ((T4 >> 2) & 1) ? T4 : T4 + 4;      // (mha_t4 / mha_s1 of the kernel)
+  const size_t shm = sizeof(float) * ((size_t)T * HD + (size_t)T4 * HD + (size_t)T * S1) + (DROP ? mha_keep_bytes(T) : 0);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)token_mha_fwd_kernel<HD, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((token_mha_fwd_kernel<HD, DROP>), dim3(heads, B), dim3(512), shm, stream, q, k, v, T, E, heads, out, probs, d);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
 template <int HD>
 int launch_token_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out, float* probs,
-                     hipStream_t stream) {
-  const int T4 = (T + 3) & ~3, S1 = ((T4 >> 2) & 1) ? T4 : T4 + 4;      // (mha_t4 / mha_s1 of the kernel)
-  const size_t shm = sizeof(float) * ((size_t)T * HD + (size_t)T4 * HD + (size_t)T * S1);
+                     const DropArgs& d, hipStream_t stream) {
+  return d.active() ? launch_token_fwd_drop<HD, true>(q, k, v, B, T, E, heads, out, probs, d, stream)
+                    : launch_token_fwd_drop<HD, false>(q, k, v, B, T, E, heads, out, probs, d, stream);
+}
+
+template <int HD, int FORM, bool DROP>
+void launch_token_bwd_form(size_t shm, const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
+                           int E, int heads, float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_fwd_kernel<HD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<HD, FORM, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
     attr_set = true;
   }
-  hipLaunchKernelGGL(token_mha_fwd_kernel<HD>, dim3(heads, B), dim3(512), shm, stream, q, k, v, T, E, heads, out, probs);
+  hipLaunchKernelGGL((token_mha_bwd_kernel<HD, FORM, DROP>), dim3(heads, B), dim3(512), shm, stream, q, k, v, probs, dout, T, E, heads, dq, dk,
+                     dv, d);
+}
+
+template <int HD, bool DROP>
+int launch_token_bwd_drop(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E,
+                          int heads, float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
+  // FORM 0 while the four operand images and both T x T images (dS, P) fit (T <= 127 / 114 / 92 at HD = 16 / 32 / 64), FORM 1 while the
+  // operands and dS do (every T at 16 and 32, T <= 111 at 64), FORM 2 (V, dO, dS) beyond.  DROP: plus the keep-bit image (T <= 126 / 113 /
+  // 92, then T <= 110 at 64: the kernel's comment)
+  const size_t op = sizeof(float) * (size_t)T * HD, tt = sizeof(float) * (size_t)T * (T + 1), mk = DROP ? mha_keep_bytes(T) : 0;
+  if (4 * op + 2 * tt + mk <= (size_t)LDS_MAX)
+    launch_token_bwd_form<HD, 0, DROP>(4 * op + 2 * tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  else if (4 * op + tt + mk <= (size_t)LDS_MAX)
+    launch_token_bwd_form<HD, 1, DROP>(4 * op + tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  else
+    launch_token_bwd_form<HD, 2, DROP>(2 * op + tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
-
-template <int HD, int FORM>
-void launch_token_bwd_form(size_t shm, const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
-                           int E, int heads, float* dq, float* dk, float* dv, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<HD, FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((token_mha_bwd_kernel<HD, FORM>), dim3(heads, B), dim3(512), shm, stream, q, k, v, probs, dout, T, E, heads, dq, dk, dv);
-}
-
 template <int HD>
 int launch_token_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E, int heads,
-                     float* dq, float* dk, float* dv, hipStream_t stream) {
-  // FORM 0 while the four operand images and both T x T images (dS, P) fit (T <= 127 / 114 / 92 at HD = 16 / 32 / 64), FORM 1 while the
-  // operands and dS do (every T at 16 and 32, T <= 111 at 64), FORM 2 (V, dO, dS) beyond
-  const size_t op = sizeof(float) * (size_t)T * HD, tt = sizeof(float) * (size_t)T * (T + 1);
-  if (4 * op + 2 * tt <= (size_t)LDS_MAX)
-    launch_token_bwd_form<HD, 0>(4 * op + 2 * tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
-  else if (4 * op + tt <= (size_t)LDS_MAX)
-    launch_token_bwd_form<HD, 1>(4 * op + tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
-  else
-    launch_token_bwd_form<HD, 2>(2 * op + tt, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, stream);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+                     float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
+  return d.active() ? launch_token_bwd_drop<HD, true>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream)
+                    : launch_token_bwd_drop<HD, false>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
 }
 
 inline bool ad_heads_ok(int heads, int head_dim) { return heads >= 1 && head_dim >= 1 && heads <= 1024; }
@@ -1309,28 +1377,42 @@ static int mha_head_dim(int E, int heads) {
   const int hd = E / heads;
   return (hd == 16 || hd == 32 || hd == 64) ? hd : 0;
 }
-extern "C" int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads,
-                                float* out, float* probs, mt_stream_t stream) {
+// the softmax dropout of the _drop entries: element dropout only (no DropPath at this site), p in [0, 1)
+static bool mha_drop_ok(const MtDropout* drop) { return !drop || (drop->p >= 0.f && drop->p < 1.f && drop->path_p == 0.f); }
+extern "C" int mt_token_mha_fwd_drop(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,
+                                     float* probs, const MtDropout* drop, mt_stream_t stream) {
   const float* ps[] = {q, k, v, out};
-  if (!mha_ptrs_ok(ps, 4, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads) return MT_ERR_BAD_ARG;
+  if (!mha_ptrs_ok(ps, 4, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads || !mha_drop_ok(drop))
+    return MT_ERR_BAD_ARG;
+  const DropArgs d = make_drop(drop);
   switch (mha_head_dim(E, heads)) {
-    case 16: return launch_token_fwd<16>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
-    case 32: return launch_token_fwd<32>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
-    case 64: return launch_token_fwd<64>(q, k, v, B, T, E, heads, out, probs, (hipStream_t)stream);
+    case 16: return launch_token_fwd<16>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
+    case 32: return launch_token_fwd<32>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
+    case 64: return launch_token_fwd<64>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
     default: return MT_ERR_UNSUPPORTED;
   }
 }
+extern "C" int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads,
+                                float* out, float* probs, mt_stream_t stream) {
+  return mt_token_mha_fwd_drop(q, k, v, B, T, E, heads, out, probs, nullptr, stream);
+}
 
-extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout,
-                                int B, int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream) {
+extern "C" int mt_token_mha_bwd_drop(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
+                                     int E, int heads, float* dq, float* dk, float* dv, const MtDropout* drop, mt_stream_t stream) {
   const float* ps[] = {q, k, v, dout, dq, dk, dv};
-  if (!mha_ptrs_ok(ps, 7, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads) return MT_ERR_BAD_ARG;
+  if (!mha_ptrs_ok(ps, 7, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads || !mha_drop_ok(drop))
+    return MT_ERR_BAD_ARG;
+  const DropArgs d = make_drop(drop);
   switch (mha_head_dim(E, heads)) {
-    case 16: return launch_token_bwd<16>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
-    case 32: return launch_token_bwd<32>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
-    case 64: return launch_token_bwd<64>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, (hipStream_t)stream);
+    case 16: return launch_token_bwd<16>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
+    case 32: return launch_token_bwd<32>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
+    case 64: return launch_token_bwd<64>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
     default: return MT_ERR_UNSUPPORTED;
   }
+}
+extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout,
+                                int B, int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream) {
+  return mt_token_mha_bwd_drop(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, nullptr, stream);
 }
 
 extern "C" int mt_extract_attn_probs_hd(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, int heads, int head_dim,

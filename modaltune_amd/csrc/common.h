@@ -170,6 +170,14 @@ MT_DEVINL bool drop_keep1(const DropArgs& d, uint32_t site, uint64_t idx) {
   return r[idx & 3] >= drop_threshold(d.p);
 }
 
+// keep flags of the FOUR elements whose linear index starts at 4 * idx4 (one Philox call: the words drop_elem4 / drop_keep1 see), bit e =
+// element 4 * idx4 + e
+MT_DEVINL uint32_t drop_keep4(const DropArgs& d, uint64_t idx4, uint32_t thr) {
+  uint32_t r[4];
+  philox4x32_7((uint32_t)idx4, (uint32_t)(idx4 >> 32), d.site, d.rng[2], d.rng[0], d.rng[1], r);
+  return (r[0] >= thr ? 1u : 0u) | (r[1] >= thr ? 2u : 0u) | (r[2] >= thr ? 4u : 0u) | (r[3] >= thr ? 8u : 0u);
+}
+
 // 16-byte global load/store helpers
 MT_DEVINL h16x8 ldg8(const h16* p) { return *reinterpret_cast<const h16x8*>(p); }
 MT_DEVINL void stg8(h16* p, h16x8 v) { *reinterpret_cast<h16x8*>(p) = v; }

@@ -597,7 +597,7 @@ class Engine:
             if need_grad and (self.grad_ready_hook is not None or self.record_markers):
                 tape.record_marker(i, lambda i=i: self.grad_ready_hook is not None and (self._leaf_join(), self.grad_ready_hook(i)))
             if i > 0 and cfg.use_prompt_sa:
-                c = self._prompt_self_attention(c, pe, f"prompt_selfattention.{i}.")
+                c = self._prompt_self_attention(c, pe, f"prompt_selfattention.{i}.", i)
             hin = ws[f"hin{la}"]
             # cls row of every pass: cls_token (+ pos_embed[0] = 0) for block 0, else carried from the previous block
             if i == 0 and a0 > 0:
@@ -926,17 +926,21 @@ class Engine:
         bq, bk, bv = (Param(b[i * E:(i + 1) * E], gb[i * E:(i + 1) * E]) for i in range(3))
         return P(pref + "q_proj_weight"), P(pref + "k_proj_weight"), P(pref + "v_proj_weight"), bq, bk, bv
 
-    def _prompt_self_attention(self, c: Var, pe: Param, pref: str) -> Var:
-        """SelfAttentionLayer.forward_pre (AM:81-94)."""
+    def _prompt_self_attention(self, c: Var, pe: Param, pref: str, i: int = 0) -> Var:
+        """SelfAttentionLayer.forward_pre (AM:81-94).  In train mode cfg.prompt_dropout acts twice (AM:42-52): on the softmax
+        probabilities (site 400 + 2 i, element index over [B, heads, T, T]) and on output_proj's result before the residual add (site
+        401 + 2 i, element index over [B T, D], on the GEMM's epilogue)."""
         tape, P = self.tape, self.store.param
+        pd = float(self.cfg.prompt_dropout)
+        d_probs, d_res = self._drop(400 + 2 * i, pd), self._drop(401 + 2 * i, pd)
         tn = tape.layernorm(c, P(pref + "norm.weight"), P(pref + "norm.bias"))
         kin = tape.add_rows_param(tn, pe)
         Wq, Wk, Wv, bq, bk, bv = self._mha_in(pref + "self_attn.")
         q1, k, v = tape.linear_group([(kin, P(pref + "q_proj.weight"), P(pref + "q_proj.bias")), (kin, Wk, bk), (tn, Wv, bv)])
         q = tape.linear(q1, Wq, bq)
-        a = tape.token_mha(q, k, v, self.cfg.num_heads, mean_probs=self._maps.get(pref + "self_attn"))
+        a = tape.token_mha(q, k, v, self.cfg.num_heads, mean_probs=self._maps.get(pref + "self_attn"), drop=d_probs)
         o = tape.linear(a, P(pref + "self_attn.out_proj.weight"), P(pref + "self_attn.out_proj.bias"))
-        return tape.linear(o, P(pref + "output_proj.weight"), P(pref + "output_proj.bias"), resid=c)
+        return tape.linear(o, P(pref + "output_proj.weight"), P(pref + "output_proj.bias"), drop=d_res, resid=c)
 
     # ------------------------------------------------------------------ injector (A.1)
     def _injector(self, i: int, c: Var, pe: Param, src: torch.Tensor, src_map, hin: torch.Tensor, first: bool):

@@ -485,13 +485,24 @@ def extract_attn_bwd(q, kv, out, lse, dout, dq, dkv, B, T, L, heads=12, head_dim
                                              _opts(what, det=det), _s()), what)
 
 
-def token_mha_fwd(q, k, v, out, probs, B, T, E, heads):
-    check(_lib.load().mt_token_mha_fwd(_p(q), _p(k), _p(v), B, T, E, heads, _p(out), _p(probs), _s()), "token_mha_fwd")
+def token_mha_fwd(q, k, v, out, probs, B, T, E, heads, *, drop=None):
+    """drop (dropout_spec, element dropout only): the softmax dropout of nn.MultiheadAttention in train() -- mask index
+    ((b heads + h) T + i) T + j at drop.site; probs keeps the pre-dropout softmax.  None: the plain entry."""
+    if drop is None:
+        check(_lib.load().mt_token_mha_fwd(_p(q), _p(k), _p(v), B, T, E, heads, _p(out), _p(probs), _s()), "token_mha_fwd")
+    else:
+        check(_lib.load().mt_token_mha_fwd_drop(_p(q), _p(k), _p(v), B, T, E, heads, _p(out), _p(probs), _dr(drop), _s()),
+              "token_mha_fwd_drop")
 
 
-def token_mha_bwd(q, k, v, probs, dout, dq, dk, dv, B, T, E, heads):
-    check(_lib.load().mt_token_mha_bwd(_p(q), _p(k), _p(v), _p(probs), _p(dout), B, T, E, heads, _p(dq), _p(dk), _p(dv),
-                                       _s()), "token_mha_bwd")
+def token_mha_bwd(q, k, v, probs, dout, dq, dk, dv, B, T, E, heads, *, drop=None):
+    """drop: the forward's spec (the mask is regenerated from it)."""
+    if drop is None:
+        check(_lib.load().mt_token_mha_bwd(_p(q), _p(k), _p(v), _p(probs), _p(dout), B, T, E, heads, _p(dq), _p(dk), _p(dv),
+                                           _s()), "token_mha_bwd")
+    else:
+        check(_lib.load().mt_token_mha_bwd_drop(_p(q), _p(k), _p(v), _p(probs), _p(dout), B, T, E, heads, _p(dq), _p(dk), _p(dv),
+                                                _dr(drop), _s()), "token_mha_bwd_drop")
 
 
 def extract_attn_probs(q, kv, lse, w, B, T, L, heads=12, head_dim=16):

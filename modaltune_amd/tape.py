@@ -355,12 +355,14 @@ class Tape:
         self.record(bwd)
         return y
 
-    def token_mha(self, q: Var, k: Var, v: Var, heads: int, mean_probs: Optional[torch.Tensor] = None) -> Var:
-        """mean_probs [B, T, T] (optional): receives the head-averaged attention weights (the engine's attention maps)."""
+    def token_mha(self, q: Var, k: Var, v: Var, heads: int, mean_probs: Optional[torch.Tensor] = None, drop=None) -> Var:
+        """mean_probs [B, T, T] (optional): receives the head-averaged attention weights (the engine's attention maps).
+        drop (ops.dropout_spec; None = off): dropout on the softmax probabilities, the same spec forward and backward -- probs (and so
+        mean_probs) stay the pre-dropout softmax."""
         Bb, T, E = q.data.shape
         out = Var(self.new(Bb, T, E))
         probs = self.new(Bb, heads, T, T)
-        ops.token_mha_fwd(q.data, k.data, v.data, out.data, probs, Bb, T, E, heads)
+        ops.token_mha_fwd(q.data, k.data, v.data, out.data, probs, Bb, T, E, heads, drop=drop)
         if mean_probs is not None:
             ops.token_probs_mean(probs, mean_probs, Bb, heads, T)
 
@@ -368,7 +370,7 @@ class Tape:
             if out.grad is None:
                 return
             dq, dk, dv = self.new(Bb, T, E), self.new(Bb, T, E), self.new(Bb, T, E)
-            ops.token_mha_bwd(q.data, k.data, v.data, probs, out.grad, dq, dk, dv, Bb, T, E, heads)
+            ops.token_mha_bwd(q.data, k.data, v.data, probs, out.grad, dq, dk, dv, Bb, T, E, heads, drop=drop)
             for var, d in ((q, dq), (k, dk), (v, dv)):
                 var.acc(d)
         self.record(bwd)

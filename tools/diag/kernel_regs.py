@@ -6,7 +6,8 @@ existing kernels as they were:
     python tools/diag/kernel_regs.py --diff old.txt new.txt         -> profiles/
 
 A kernel that gained a trailing defaulted `bool` template parameter (`template <..., bool DET = false>`) is matched with its old symbol:
-the `false` instantiation IS the old kernel."""
+the `false` instantiation IS the old kernel -- also when the new forms bring trailing kernel parameters along (`DropArgs drop` of the
+prompt self-attention's DROP forms), which the `false` instantiation never reads."""
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
@@ -47,6 +48,9 @@ def diff(old_path, new_path):
         f, n = key
         for c in new:         # `Lb0E` appended to the template argument list (a non-template kernel also gains `I...E` and its return type `v`)
             if c[0] == f and (c[1].replace("Lb0EE", "E", 1) == n or c[1].replace("ILb0EEEv", "E", 1) == n):
+                return c
+        for c in new:         # ... and with it trailing kernel parameters that only the `true` form reads (their mangled types follow the old list)
+            if c[0] == f and "Lb0EE" in c[1] and c[1].replace("Lb0EE", "E", 1).startswith(n):
                 return c
         return None
     pairs = {k: twin(k) for k in old}
