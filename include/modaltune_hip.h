@@ -482,6 +482,20 @@ int mt_gene_snn_bwd_input(const float* params, const long* offs, const int* size
 int mt_ig_finalize(const float* genes, const float* baseline, const float* dgenes, const int* sizes, const long* goff, int G,
                    float* attr, float* pathway, mt_stream_t stream);
 
+/* Integrated Gradients over the PATCH embeddings.  The patch embedding is affine in the input features, so the straight path between a
+ * baseline bag and the slide is the straight path between their embeddings ex, eb [L, D] (fp32, D % 4 == 0, 16-byte aligned):
+ *   x0p[b L + l, :] = eb[l, :] + alphas[b] (ex[l, :] - eb[l, :])        1 <= B <= 4 passes, alphas [B] read on the DEVICE, any L >= 1
+ * alphas[b] == 0 stores eb's bits and alphas[b] == 1 stores ex's (selected, not computed): those passes are the plain forward.
+ * ex and eb are read once for all B passes. */
+int mt_patch_points_fwd(const float* ex, const float* eb, const float* alphas, int B, int L, int D, float* x0p, mt_stream_t stream);
+/* The per-patch attribution from the activation gradient dh [B, N, D] (N >= L + 1: row 0 of every pass is the cls row, never read):
+ *   acc[l] += unscale * sum_b weights[b] <dh[b N + 1 + l, :], ex[l, :] - eb[l, :]>
+ * weights [B] on the device; a pass with weights[b] == 0 is SKIPPED (its rows may hold anything); unscale: device scalar or NULL (= 1).
+ * One wave per patch row, b ascending, the lane sums joined by a butterfly: one writer per acc[l] and one summation order, no
+ * atomics -- the same bits on every call. */
+int mt_patch_ig_accumulate(const float* dh, int N, const float* ex, const float* eb, const float* weights, const float* unscale, int B,
+                           int L, int D, float* acc, mt_stream_t stream);
+
 /* Small dense multi-head attention over tokens (prompt self-attention AM:87): q,k,v fp32 [B,T,E], heads h; the head dim
  * E / h must be 16, 32 or 64 (MT_ERR_UNSUPPORTED otherwise). */
 int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,

@@ -110,6 +110,8 @@ SIGNATURES = {
     "mt_gene_snn_fwd_points": [P, P, P, P, P, P, P, I, I, I, P, P, P, P],
     "mt_gene_snn_bwd_input": [P, P, P, P, I, I, I, P, P, P, P, P, P, I, P],
     "mt_ig_finalize": [P, P, P, P, P, I, P, P, P],
+    "mt_patch_points_fwd": [P, P, P, I, I, I, P, P],
+    "mt_patch_ig_accumulate": [P, I, P, P, P, P, I, I, I, P, P],
     "mt_inject_attn_fwd": [P, I, I, P, P, I, P, P, P],
     "mt_inject_attn_bwd": [P, P, P, P, I, I, P, P, I, P, P, P, P],
     "mt_extract_attn_fwd": [P, P, I, I, I, P, P, P, P, I, P],

@@ -498,28 +498,35 @@ class LongNetGeneAdapter(Aggregator):
             logits, maps = ex[1](x, coords, self._gene_list(genes), clinical if self.CLINICAL else None)
         return {"logits": logits, "tokens": token_legend(self.cfg), "maps": maps}
 
-    def integrated_gradients(self, x, coords, genes, target, task_ids=(0, 1, 2), steps: int = 64, baseline=None, clinical=None) -> Dict[str, Any]:
+    def integrated_gradients(self, x, coords, genes, target, task_ids=(0, 1, 2), steps: int = 64, baseline=None, clinical=None,
+                             inputs: str = "genes", patch_baseline=None) -> Dict[str, Any]:
         """Integrated Gradients of F_t = <target_t, logits_t> over the gene inputs of one slide (README Figure 3 of the reference:
         the pathways influencing risk) -- attribution.IntegratedGradients has the quadrature and the result's keys
         (`attributions` [tasks, total genes] in pathway order, `pathway` [tasks, G], `f_input`, `f_baseline`, `delta`,
         `convergence_delta`, ...); attribution.top_pathways turns a row into the figure's bars.  target [len(task_ids), output_dim]
         or [output_dim]; baseline None = zeros.
 
+        inputs="patches" attributes to the PATCHES of the slide instead (the genes stay at their values; patch_baseline [L, in_chans],
+        None = zeros, is the baseline bag): `patches` [tasks, L] -- evaluate.attention_to_grid(res["patches"][t], coords) draws the
+        heatmap -- and `patches_total` [tasks].  inputs="both" walks one straight path through both modalities and returns both sets of
+        keys: how much of F(x, genes) - F(baseline) the image carries and how much the genes.
+
         Like attention_maps, this runs the eval forward -- no Dropout / DropPath -- whatever `model.training` says, and leaves the
         parameters, their gradients and every captured graph as they were."""
         from .attribution import IntegratedGradients
         if hasattr(self.engine, "forward_slide"):
             raise NotImplementedError("Integrated Gradients over the gene inputs of the TITAN configuration are not supported")
-        key = (tuple(int(t) for t in task_ids) if self.is_multi else (0,), int(steps))
+        key = (tuple(int(t) for t in task_ids) if self.is_multi else (0,), int(steps), str(inputs))
         ig = getattr(self, "_ig", None)
         if ig is None or ig[0] != key:
-            ig = self._ig = (key, IntegratedGradients(self.engine, key[0], steps=key[1]))
+            ig = self._ig = (key, IntegratedGradients(self.engine, key[0], steps=key[1], inputs=key[2]))
         self._sync_weight_caches()
         genes = self._gene_list(genes)
         if baseline is not None:
             baseline = self._gene_list(baseline)
         with torch.no_grad():
-            return ig[1](x, coords, genes, target, baseline=baseline, clinical=clinical if self.CLINICAL else None)
+            return ig[1](x, coords, genes, target, baseline=baseline, clinical=clinical if self.CLINICAL else None,
+                         patch_baseline=patch_baseline)
 
 
 @Aggregator.register("longnetvit_gene_clinical_adapter")

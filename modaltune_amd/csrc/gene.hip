@@ -602,3 +602,102 @@ extern "C" int mt_ig_finalize(const float* genes, const float* baseline, const f
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
+
+// ---- Integrated Gradients over the PATCH embeddings (attribution.py, inputs = "patches" / "both").  The patch embedding is affine in
+// the input features, so the straight path x(alpha) = base + alpha (x - base) is the straight path between the two EMBEDDED bags, and
+// sum_c IG[l][c] = <e_x[l] - e_base[l], integral dF/dx0[l]>: one interpolation in the embedding space per pass and one weighted row dot
+// of the activation gradient -- no GEMM back to the input channels.  Both kernels are HBM-bound streams: 16-byte accesses, no LDS, no
+// atomics.
+namespace {
+
+struct PatchPointArgs {
+  const float* ex; const float* eb;      // [L][D]: the embedded input and the embedded baseline
+  const float* alphas;                   // [B] device (forward)
+  const float* weights;                  // [B] device (accumulate)
+  const float* unscale;                  // device scalar or null (= 1)
+  float* x0p;                            // [B][L][D]
+  const float* dh;                       // [B][N][D]: row 0 of every pass is the cls row
+  float* acc;                            // [L]
+  int B, L, D, N;
+};
+
+MT_DEVINL float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// x0p[b][l] = eb[l] + alpha_b (ex[l] - eb[l]): one thread per 16 bytes of a row, ex / eb read ONCE for all B passes.  alpha = 0 / 1
+// SELECT eb / ex (their bits: the endpoint passes are the plain forward at the baseline / at the input)
+__global__ __launch_bounds__(GL) void patch_points_fwd_kernel(PatchPointArgs a) {
+  const long e = ((long)blockIdx.x * GL + threadIdx.x) * 4;
+  const long n = (long)a.L * a.D;
+  if (e >= n) return;
+  const float4 x = ld4(a.ex + e), b = ld4(a.eb + e);
+  for (int p = 0; p < a.B; ++p) {
+    const float al = a.alphas[p];
+    float4 o;
+    if (al == 0.f) o = b;
+    else if (al == 1.f) o = x;
+    else o = make_float4(fmaf(al, x.x - b.x, b.x), fmaf(al, x.y - b.y, b.y), fmaf(al, x.z - b.z, b.z), fmaf(al, x.w - b.w, b.w));
+    *reinterpret_cast<float4*>(a.x0p + (long)p * n + e) = o;
+  }
+}
+
+// acc[l] += unscale * sum_b w_b <dh[b][1 + l], ex[l] - eb[l]>: one wave per patch row.  A lane forms its share of every live pass's
+// dot (columns ascending; the difference is formed once per column for all passes), sums the passes with their weights (b ascending),
+// and wave_sum joins the 64 lane sums: one writer per acc[l], one order.  A pass with w_b == 0 is NOT read (the endpoint and padding
+// slots of a quadrature); neither is any cls row.
+__global__ __launch_bounds__(GL) void patch_ig_accumulate_kernel(PatchPointArgs a) {
+  const int lane = threadIdx.x & (MT_WAVE - 1);
+  const long l = (long)blockIdx.x * (GL / MT_WAVE) + threadIdx.x / MT_WAVE;
+  if (l >= a.L) return;                  // (whole waves leave: wave_sum below sees full waves only)
+  float w[GP_MAX], part[GP_MAX];
+#pragma unroll
+  for (int p = 0; p < GP_MAX; ++p) {
+    w[p] = p < a.B ? a.weights[p] : 0.f;
+    part[p] = 0.f;
+  }
+  const float* ex = a.ex + l * a.D;
+  const float* eb = a.eb + l * a.D;
+  for (int c = lane * 4; c < a.D; c += MT_WAVE * 4) {
+    const float4 x = ld4(ex + c), b = ld4(eb + c);
+    const float4 d = make_float4(x.x - b.x, x.y - b.y, x.z - b.z, x.w - b.w);
+#pragma unroll
+    for (int p = 0; p < GP_MAX; ++p) {
+      if (w[p] == 0.f) continue;         // (wave-uniform)
+      const float4 g = ld4(a.dh + ((long)p * a.N + 1 + l) * a.D + c);
+      part[p] = fmaf(g.w, d.w, fmaf(g.z, d.z, fmaf(g.y, d.y, fmaf(g.x, d.x, part[p]))));
+    }
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int p = 0; p < GP_MAX; ++p)
+    if (w[p] != 0.f) s = fmaf(w[p], part[p], s);
+  s = wave_sum(s);
+  if (lane == 0) a.acc[l] += (a.unscale ? a.unscale[0] : 1.f) * s;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int mt_patch_points_fwd(const float* ex, const float* eb, const float* alphas, int B, int L, int D, float* x0p,
+                                   mt_stream_t stream) {
+  if (!ex || !eb || !alphas || !x0p || B < 1 || L < 1 || D < 4 || (D & 3)) return MT_ERR_BAD_ARG;
+  if (!aligned16(ex) || !aligned16(eb) || !aligned16(x0p)) return MT_ERR_BAD_ARG;
+  if (B > GP_MAX) return MT_ERR_UNSUPPORTED;
+  const long blocks = ((long)L * D / 4 + GL - 1) / GL;
+  if (blocks > 0x7fffffffL) return MT_ERR_UNSUPPORTED;
+  PatchPointArgs a{ex, eb, alphas, nullptr, nullptr, x0p, nullptr, nullptr, B, L, D, 0};
+  hipLaunchKernelGGL(patch_points_fwd_kernel, dim3((unsigned)blocks), dim3(GL), 0, (hipStream_t)stream, a);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_patch_ig_accumulate(const float* dh, int N, const float* ex, const float* eb, const float* weights,
+                                      const float* unscale, int B, int L, int D, float* acc, mt_stream_t stream) {
+  if (!dh || !ex || !eb || !weights || !acc || B < 1 || L < 1 || N < L + 1 || D < 4 || (D & 3)) return MT_ERR_BAD_ARG;
+  if (!aligned16(dh) || !aligned16(ex) || !aligned16(eb)) return MT_ERR_BAD_ARG;
+  if (B > GP_MAX) return MT_ERR_UNSUPPORTED;
+  PatchPointArgs a{ex, eb, nullptr, weights, unscale, nullptr, dh, acc, B, L, D, N};
+  hipLaunchKernelGGL(patch_ig_accumulate_kernel, dim3(cdiv(L, GL / MT_WAVE)), dim3(GL), 0, (hipStream_t)stream, a);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}

@@ -436,7 +436,7 @@ extern "C" int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_st
   return MT_OK;
 }
 
-extern "C" int mt_version(void) { return 310; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*; the binary itself is identified by mt_build_id(), not by this number)
+extern "C" int mt_version(void) { return 320; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate; the binary itself is identified by mt_build_id(), not by this number)
 
 extern "C" const char* mt_status_string(int status) {
   switch (status) {

@@ -168,6 +168,19 @@ class GenePoints:
         self.baseline, self.alphas, self.weights, self.dgenes, self.unscale = baseline, alphas, weights, dgenes, unscale
 
 
+class PatchPoints:
+    """The task passes of one forward as POINTS of the straight path baseline bag -> slide, taken in the embedding space (the patch
+    embedding is affine in the input features, so the straight path between two bags is the straight path between their embeddings):
+    pass p feeds the first Injector x0_base + alphas[p] (x0 - x0_base), and once the backward has reached the bottom it adds
+    unscale * sum_p weights[p] <dF_p/dx0[l], x0[l] - x0_base[l]> to dpatch[l] -- the per-patch sum of Integrated Gradients over the
+    input channels.  x0_base: the embedded baseline, fp32 [L, embed_dim] on the device (Engine.prepare_shared of the baseline bag at the
+    slide's coords); alphas, weights: fp32 [B] on the device; dpatch: the caller's fp32 [L] accumulator; unscale: device scalar or None."""
+    __slots__ = ("x0_base", "alphas", "weights", "dpatch", "unscale")
+
+    def __init__(self, x0_base, alphas, weights, dpatch, unscale=None):
+        self.x0_base, self.alphas, self.weights, self.dpatch, self.unscale = x0_base, alphas, weights, dpatch, unscale
+
+
 def deterministic_default() -> bool:
     """What `deterministic=None` means: MT_DETERMINISTIC=1 in the environment, or torch.use_deterministic_algorithms(True)."""
     return os.environ.get("MT_DETERMINISTIC", "0") == "1" or torch.are_deterministic_algorithms_enabled()
@@ -491,7 +504,8 @@ class Engine:
                 need_grad: bool = True, fresh: bool = False, staged: bool = False, geometry=None,
                 clinical: Optional[torch.Tensor] = None, share: Optional[dict] = None, tape: Optional[Tape] = None,
                 site_group: int = 0, ws_slot: int = 0, attn_maps: Optional[Dict[str, torch.Tensor]] = None,
-                points: Optional[GenePoints] = None, stochastic: Optional[bool] = None) -> torch.Tensor:
+                points: Optional[GenePoints] = None, stochastic: Optional[bool] = None,
+                patch_points: Optional[PatchPoints] = None) -> torch.Tensor:
         """x [L, in_chans] (or [1,L,in]); coords [L,2] (host or device); genes: list of [1, n_i]; task_onehots [B, num_tasks].
         Returns logits [B, output_dim] (fp32, device).  fresh=True gives this call its own tape and workspace so that
         several forwards can precede one backward (the reference calls the model 3x before loss.backward(), TM:175-177);
@@ -504,13 +518,22 @@ class Engine:
         its head-averaged softmax there right behind its attention core (shapes: attention_map_shapes).
         points: the B passes evaluate the gene encoder at B points between a baseline and `genes` and the backward writes the gene
         INPUT gradient (GenePoints).  stochastic=False runs this call -- a need_grad=True one too -- with every Dropout / DropPath
-        site off, without set_stochastic(): the engine's mode, dropout counters and generation stay (None / True: the engine's mode)."""
+        site off, without set_stochastic(): the engine's mode, dropout counters and generation stay (None / True: the engine's mode).
+        patch_points: the B passes feed the first Injector B points between an embedded baseline bag and the slide's patch embedding,
+        the backward keeps the gradient at block 0's input and turns it into per-patch attributions (PatchPoints).  need_grad=True and
+        stochastic=False; may be combined with `points` (one path through both modalities: the same alphas and weights)."""
         cfg, dev, t = self.cfg, self.device, self.store.tensors
         drop_now = bool(self.stochastic and need_grad and stochastic is not False)
         if points is not None:
             if drop_now:
                 raise ValueError("points: the path points are evaluated with the stochastic sites off (stochastic=False)")
             self._check_points(points, int(task_onehots.shape[0]))
+        if patch_points is not None:
+            if drop_now:
+                raise ValueError("patch_points: the path points are evaluated with the stochastic sites off (stochastic=False)")
+            if staged:
+                raise ValueError("patch_points: not available on the staged (graph replay) path")
+            self._check_patch_points(patch_points, int(task_onehots.shape[0]), int(x.reshape(-1, x.shape[-1]).shape[0]), need_grad)
         if self.store.sync is not None:
             self.store.sync()         # parameters complete on this rank before anything reads them (no-op when nothing is pending)
         if not self._caches_ready:
@@ -576,6 +599,14 @@ class Engine:
                 ws["x0d"] = torch.empty(B * L, D, dtype=F32, device=dev)
             ops.dropout_f32(ws["x0"], ws["x0d"], B * L, D, d_in, xmap=rowmap(L, 0, 0))
             src, src_map = ws["x0d"], rowmap(L, L, 0)
+        if patch_points is not None:                  # pass b reads its own point of the path between the two embedded bags
+            pp, ex = patch_points, ws["x0"]
+            x0p = torch.empty(B * L, D, dtype=F32, device=dev)
+            ops.patch_points_fwd(ex, pp.x0_base, pp.alphas, B, L, D, x0p)
+            src, src_map = x0p, rowmap(L, L, 0)
+            # (runs when the backward has reached the bottom: the first Injector's backward below leaves dF/dx0p in the patch rows of dh)
+            tape.record(lambda: ops.patch_ig_accumulate(ws["dh"], N, ex, pp.x0_base, pp.weights, B, L, D, pp.dpatch,
+                                                        unscale_dev=pp.unscale))
         a0 = cfg.first_interaction_layer
         if a0 > 0:
             # interaction_indexes[0][0] != 0 (LVA:269-281): the layers below the first interaction run on [cls; embedded slide] as plain
@@ -606,7 +637,7 @@ class Engine:
                 ops.copy_rows(self._cls_source().view(1, D), hin, B, D, smap=rowmap(1, 0, 0), dmap=rowmap(1, N, 0))
             else:
                 ops.copy_rows(ws[f"hout{i - 1}"], hin, B, D, smap=rowmap(1, N, 0), dmap=rowmap(1, N, 0))
-            self._injector(i, c, pe, src, src_map, hin, first=(i == 0))
+            self._injector(i, c, pe, src, src_map, hin, first=(i == 0 and patch_points is None))
             pend = None
             for l in range(la, lb + 1):
                 out = ws[f"hin{l + 1}"] if l < lb else ws[f"hout{i}"]
@@ -804,6 +835,24 @@ class Engine:
             if tns is None or tns.dtype != F32 or tns.device.type != self.device.type or not tns.is_contiguous() or tns.numel() != want:
                 raise ValueError(f"points.{nm}: expected a contiguous fp32 tensor of {want} element(s) on {self.device}")
 
+    def _check_patch_points(self, pp: "PatchPoints", B: int, L: int, need_grad: bool):
+        if hasattr(self, "forward_slide"):
+            raise NotImplementedError("input gradients of the TITAN configuration are not supported")
+        if self.cfg.first_interaction_layer != 0:
+            raise NotImplementedError("patch_points: first_interaction_layer > 0 is not supported (the layers in front of the first "
+                                      "interaction run forward-only)")
+        if not need_grad:
+            raise ValueError("patch_points: the attributions come out of the backward (need_grad=True)")
+        if B > ops.GENE_POINTS_MAX:
+            raise ValueError(f"patch_points: at most {ops.GENE_POINTS_MAX} points per engine pass, got {B}")
+        for nm, tns, want in (("x0_base", pp.x0_base, (L, self.cfg.embed_dim)), ("alphas", pp.alphas, (B,)), ("weights", pp.weights, (B,)),
+                              ("dpatch", pp.dpatch, (L,)), ("unscale", pp.unscale, (1,))):
+            if tns is None and nm == "unscale":
+                continue
+            if (not torch.is_tensor(tns) or tns.dtype != F32 or tns.device.type != self.device.type or not tns.is_contiguous()
+                    or tuple(tns.shape) != want):
+                raise ValueError(f"patch_points.{nm}: expected a contiguous fp32 tensor of shape {want} on {self.device}")
+
     def _gene_encoder(self, genes: Sequence[torch.Tensor], passes: int = 1, points: Optional[GenePoints] = None) -> Var:
         """GeneEncoder_Group.gene_encode (gene_encoder.py:194-215) of one slide for `passes` task passes: returns the gene tokens
         [1, G64, P, D] with P = passes in train mode with dropout (own masks per pass), else 1 (shared).
@@ -984,7 +1033,8 @@ class Engine:
             proj = torch.empty(Mp, D, dtype=H16, device=dev)
             ops.gemm_nt(o1, w16[ap + "output_proj"].w, proj, Mp, D, E, bias=t[ap + "output_proj.bias"])
             dproj = torch.empty(Mp, D, dtype=H16, device=dev)
-            # residual path: dh_patch <- (1+gamma) dh_patch (in place; block 0's input x0 needs no gradient)
+            # residual path: dh_patch <- (1+gamma) dh_patch (in place; first: block 0's input x0 needs no gradient -- unless the call
+            # carries patch points, which pass first=False: their row dot reads it)
             ops.inject_resid_bwd(dh, src, proj, t[pref + "gamma"], dh if not first else ws["scratch32"], dproj,
                                  g[pref + "gamma"], Mp, D, dymap=pm, xmap=src_map, dxmap=pm if not first else None, det=det)
             self._leaf(lambda: ops.gemm_tn(dproj, o1, g[ap + "output_proj.weight"], Mp, D, E, colsum=g[ap + "output_proj.bias"], det=det), dproj, o1)

@@ -462,6 +462,17 @@ def ig_finalize(genes, baseline, dgenes, sizes, goff, G, attr, pathway):
     check(_lib.load().mt_ig_finalize(_p(genes), _p(baseline), _p(dgenes), _p(sizes), _p(goff), G, _p(attr), _p(pathway), _s()), "ig_finalize")
 
 
+def patch_points_fwd(ex, eb, alphas_dev, B, L, D, x0p):
+    """x0p[b, l] = eb[l] + alphas_dev[b] (ex[l] - eb[l]); alpha 0 / 1 store eb's / ex's bits (mt_patch_points_fwd)."""
+    check(_lib.load().mt_patch_points_fwd(_p(ex), _p(eb), _p(alphas_dev), B, L, D, _p(x0p), _s()), "patch_points_fwd")
+
+
+def patch_ig_accumulate(dh, N, ex, eb, weights_dev, B, L, D, acc, unscale_dev=None):
+    """acc[l] += unscale * sum_b weights_dev[b] <dh[b, 1 + l], ex[l] - eb[l]>; weight-0 passes are not read (mt_patch_ig_accumulate)."""
+    check(_lib.load().mt_patch_ig_accumulate(_p(dh), N, _p(ex), _p(eb), _p(weights_dev), _p(unscale_dev), B, L, D, _p(acc), _s()),
+          "patch_ig_accumulate")
+
+
 def inject_attn_fwd(q, k, v, a, M, rows_per_pass, T, lse=None, heads=12, head_dim=16):
     check(_lib.load().mt_inject_attn_fwd_hd(_p(q), M, rows_per_pass, _p(k), _p(v), T, heads, head_dim, _p(a), _p(lse), _s()),
           "inject_attn_fwd")
