@@ -81,8 +81,20 @@ class ModelConfig:
 
     # ---- derived ----
     @property
-    def adapter_dim(self) -> int:          # E = int(768 * 0.25) (adapter_modules.py:153)
-        return int(self.embed_dim * self.cffn_ratio)
+    def adapter_dim(self) -> int:          # E = int(768 * 0.25) (adapter_modules.py:153); with_cffn False: cffn_ratio is ignored, E = 768
+        return int(self.embed_dim * self.cffn_ratio) if self.with_cffn else int(self.embed_dim)
+
+    @property
+    def packed_in_proj(self) -> bool:
+        """E == kdim == vdim: nn.MultiheadAttention keeps ONE in_proj_weight [3E, E] instead of q / k / v_proj_weight
+        (adapter_modules.py:42-49,157-164).  The parameter layout follows this property and nothing else."""
+        return self.adapter_dim == int(self.embed_dim)
+
+    @property
+    def extractor_ffn(self) -> bool:
+        """with_cffn: the attention layers have q_proj / output_proj and the Extractor has its FFN + DropPath
+        (adapter_modules.py:37-40,152-155,317-319).  The launch lists branch on this property and on packed_in_proj only."""
+        return bool(self.with_cffn)
 
     @property
     def adapter_head_dim(self) -> int:     # nn.MultiheadAttention(E, num_heads): E // num_heads (adapter_modules.py:164)
@@ -124,18 +136,20 @@ class ModelConfig:
         if not self.add_prompt_feature:
             raise ValueError("add_prompt_feature=False: the reference's own forward fails on this configuration (`outcome` is only bound "
                              "inside `if self.add_prompt_feature`, longvit_adapter.py:315-346): there is no behaviour to reproduce")
-        if not self.with_cffn:
-            raise NotImplementedError("with_cffn=False widens the adapter attention to 768 (12 heads x 64) and drops the Extractor FFN: at "
-                                      "E == embed_dim nn.MultiheadAttention packs its projections into one in_proj_weight, another "
-                                      "parameter layout than the one built here (adapter widths below 768: see cffn_ratio / num_heads)")
+        nh = int(self.num_heads)
+        if not self.with_cffn and (nh < 1 or self.embed_dim % nh or self.embed_dim // nh not in (16, 32, 64)):
+            raise NotImplementedError(f"with_cffn=False runs the adapter attention at the full width E = {self.embed_dim} (cffn_ratio is "
+                                      f"ignored): num_heads={self.num_heads} must give a head dim of 16, 32 or 64 there (48, 24 or 12 heads)")
         if not self.freeze_vit:
             raise NotImplementedError("freeze_vit=False: the backbone's weight gradients are not computed (selective backward)")
-        # adapter width (adapter_modules.py:153-164): E = int(768 * cffn_ratio), nn.MultiheadAttention(E, num_heads, kdim=vdim=768)
-        E, nh = self.adapter_dim, int(self.num_heads)
-        if E >= self.embed_dim:
+        # adapter width (adapter_modules.py:153-164): E = int(768 * cffn_ratio), nn.MultiheadAttention(E, num_heads, kdim=vdim=768);
+        # E == 768 (with_cffn False) is the packed in_proj_weight layout (packed_in_proj)
+        E = self.adapter_dim
+        if self.with_cffn and E >= self.embed_dim:
             raise NotImplementedError(f"cffn_ratio={self.cffn_ratio} gives the adapter width E = {E} >= embed_dim {self.embed_dim}: with "
                                       "E == kdim nn.MultiheadAttention packs q / k / v into one in_proj_weight (another state-dict "
-                                      "layout); the adapter is built for E < 768")
+                                      "layout); with the q_proj / output_proj wrap the adapter is built for E < 768 (with_cffn=False runs "
+                                      "the full width E = 768; E > 768 is refused)")
         if E < 64 or E % 64:
             raise ValueError(f"cffn_ratio={self.cffn_ratio} gives the adapter width E = int(768 * cffn_ratio) = {E}: E must be a positive "
                              "multiple of 64 (the projection GEMMs run on K % 64 == 0)")
@@ -256,8 +270,10 @@ def sincos_1d_table(ngrids: int, dim: int) -> np.ndarray:
     return np.concatenate([np.sin(out), np.cos(out)], axis=1).astype(np.float32)
 
 
-def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int = 3, E: int = 192) -> Dict[str, float]:
-    """Algorithmic FLOPs: 2mnk GEMMs, 4*nq*nk*d attention, no recompute counted.  E: adapter width (cfg.adapter_dim)."""
+def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int = 3, E: int = 192, cffn: bool = True) -> Dict[str, float]:
+    """Algorithmic FLOPs (SURVEY.md §8d): 2mnk GEMMs, 4*nq*nk*d attention, no recompute counted.  E: adapter width (cfg.adapter_dim);
+    cffn (cfg.extractor_ffn): False drops the q_proj / output_proj products of every adapter attention (with_cffn=False has neither;
+    the Extractor FFN's token-side products were never counted)."""
     seg = seg or segment_lengths()
     N, D, F, H, d = L + 1, 768, 3072, 16, 48
     patch = 2.0 * L * 1536 * D
@@ -272,8 +288,9 @@ def flops_per_slide_step(L: int, T: int, depth: int = 12, seg=None, tasks: int =
             for r in range(b.ratio):
                 nv = min(b.n, max(0, -(-(lim - r) // b.ratio)))
                 attn_exec += (H // b.ratio) * nv * nv * d * 4.0
-    inj = 2.0 * L * (D * E + E * E + E * E + E * D) + 4.0 * L * T * E + 2.0 * T * 2 * D * E
-    ext = 2.0 * T * (D * E + E * E + E * E + E * D) + 4.0 * L * T * E + 2.0 * L * 2 * D * E + 2.0 * T * 2 * D * E
+    wrap = (D * E + E * D) if cffn else 0
+    inj = 2.0 * L * (wrap + E * E + E * E) + 4.0 * L * T * E + 2.0 * T * 2 * D * E
+    ext = 2.0 * T * (wrap + E * E + E * E) + 4.0 * L * T * E + 2.0 * L * 2 * D * E + 2.0 * T * 2 * D * E
     adapter = 3 * inj + 5 * ext
     fwd = patch + depth * (gemm_layer + attn_layer) + adapter
     bwd = depth * (gemm_layer + 2.5 * attn_layer) + 2 * adapter

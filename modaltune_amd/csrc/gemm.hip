@@ -1029,14 +1029,55 @@ static int gemm_tn_split(int M, int tiles) {
   return cdiv(split, 8) * 8;
 }
 
+// Output tile of a product: 64 x 64 everywhere, except for the products of the full-width adapters, N1 * N2 >= 768 * 768 (q / out:
+// 768 x 768, k | v: 1536 x 768), whose 144 / 288 64 x 64 tiles re-read each operand 12 / 24 times.  Measured on one MI355X, three
+// alternating runs, us per launch min..max ("Full-width adapters"; profiles/full_width_tn_tiles.txt):
+//                         M = 30 003: 64x64       128x64      128x128       M = 12 291: 64x64     128x64     128x128
+//   768 x 768   atomic    108.0..108.6  114.3..115.3  112.1..112.8          54.4..55.2  61.1..62.0  76.4..77.8
+//   768 x 768   DET       112.0..116.2  113.0..113.2   91.6..92.9           54.2..55.3  55.9..56.7  53.7..54.5
+//   1536 x 768  atomic    197.2..198.1  208.2..209.6  162.8..163.8          90.5..92.3  99.0..99.8  96.7..99.7
+//   1536 x 768  DET       204.4..209.0  204.4..206.1  145.9..147.4          91.5..91.9  93.6..94.2  75.5..76.6
+// 128 x 128 halves the re-reads but needs twice the splits for the same number of workgroups: with atomics that is twice the
+// read-modify-write traffic on C, which only the long 1536 x 768 product pays back; the deterministic form stores its partials and
+// wins or ties everywhere.  Hence: DET -> 128 x 128; atomic -> 128 x 128 for N1 * N2 >= 1536 * 768 at M >= TN_LARGE_MIN_ROWS (between
+// the two measured lengths; nothing in between was measured), else 64 x 64.  128 x 64 wins nowhere and is kept as an experiment's
+// choice only.  MT_GEMM_TN_TILE=64x64|128x64|128x128 overrides the rule for these products (tools/tn_microbench.py).  Every product
+// below the threshold -- all of the shipped step's -- launches exactly as before.
+struct TnTile { int tm, tn; };
+constexpr int TN_LARGE_MIN_ROWS = 20000;
+static TnTile gemm_tn_tile(int M, int N1, int N2, bool det) {
+  TnTile t = {64, 64};
+  if ((long)N1 * N2 < 768L * 768) return t;
+  if (det || ((long)N1 * N2 >= 1536L * 768 && M >= TN_LARGE_MIN_ROWS)) t = {128, 128};
+  static const char* force = getenv("MT_GEMM_TN_TILE");
+  if (force) {
+    if (!strcmp(force, "128x128")) t = {128, 128};
+    else if (!strcmp(force, "128x64")) t = {128, 64};
+    else if (!strcmp(force, "64x64")) t = {64, 64};
+  }
+  if (N1 % t.tm || N2 % t.tn) t = {64, 64};
+  return t;
+}
+static int gemm_tn_tiles(TnTile t, int N1, int N2) { return (N1 / t.tm) * (N2 / t.tn); }
+
 // The deterministic form (det_reduce.hip) launches as many splits as the default form (same tiles, same XCD rule);
-// slots = min(32-row steps, launched splits): the splits that hold rows (gemm_tn_kernel, DET).
+// slots = min(32-row steps, launched splits): the splits that hold rows (gemm_tn_kernel, DET) -- a function of the tile dispatched,
+// which for this form does not depend on M: the count never shrinks as M grows.
 // partials = [slots][N1][N2], then (with_colsum) [slots][N1].
-static int gemm_tn_det_slots(int M, int N1, int N2) { return min(cdiv(M, 32), gemm_tn_split(M, (N1 / 64) * (N2 / 64))); }
+static int gemm_tn_det_slots(int M, int N1, int N2) {
+  return min(cdiv(M, 32), gemm_tn_split(M, gemm_tn_tiles(gemm_tn_tile(M, N1, N2, true), N1, N2)));
+}
 
 extern "C" long mt_gemm_tn_f16_det_elems(int M, int N1, int N2, int with_colsum) {
   if (M <= 0 || N1 <= 0 || N2 <= 0 || N1 % 64 || N2 % 64) return MT_ERR_BAD_ARG;
   return (long)gemm_tn_det_slots(M, N1, N2) * N1 * ((long)N2 + (with_colsum ? 1 : 0));
+}
+
+template <bool DET>
+static void gemm_tn_launch(TnTile t, int blocks, hipStream_t s, const GemmTnArgs& g) {
+  if (t.tm == 128 && t.tn == 128) hipLaunchKernelGGL((gemm_tn_kernel<128, 128, DET>), dim3(blocks), dim3(256), 0, s, g);
+  else if (t.tm == 128) hipLaunchKernelGGL((gemm_tn_kernel<128, 64, DET>), dim3(blocks), dim3(256), 0, s, g);
+  else hipLaunchKernelGGL((gemm_tn_kernel<64, 64, DET>), dim3(blocks), dim3(256), 0, s, g);
 }
 
 extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, const mt_half* B, long ldb,
@@ -1054,19 +1095,20 @@ extern "C" int mt_gemm_tn_f16(const mt_half* A, long lda, const MtRowMap* amap, 
   // 64 x 64 tiles and ~1024 workgroups (512 for the small products) measured best at M = 30 000 once the tiles of a row range
   // share an XCD (tools/experiments/tn_sweep.sh: 63 / 39 / 39 / 19 us for 384x768 / 192x768 / 768x192 / 192x192; the larger
   // tiles the kernel template allows re-read less but need more splits -- more atomics -- for the same number of workgroups)
-  const int tiles = (N1 / 64) * (N2 / 64);
+  const TnTile tile = gemm_tn_tile(M, N1, N2, partials != nullptr);
+  const int tiles = gemm_tn_tiles(tile, N1, N2);
   const int split = gemm_tn_split(M, tiles);
   hipStream_t s = (hipStream_t)stream;
   if (!partials) {
     g.rows_per_split = cdiv(cdiv(M, split), 32) * 32;
-    hipLaunchKernelGGL((gemm_tn_kernel<64, 64>), dim3(tiles * split), dim3(256), 0, s, g);
+    gemm_tn_launch<false>(tile, tiles * split, s, g);
     MT_CHECK_LAUNCH();
     return MT_OK;
   }
   const int slots = gemm_tn_det_slots(M, N1, N2);
   float* pcs = partials + (long)slots * N1 * N2;
   g.rows_per_split = 0; g.C = partials; g.ldc = N2; g.colsum = colsum ? pcs : nullptr;
-  hipLaunchKernelGGL((gemm_tn_kernel<64, 64, true>), dim3(tiles * split), dim3(256), 0, s, g);
+  gemm_tn_launch<true>(tile, tiles * split, s, g);
   MT_CHECK_LAUNCH();
   int rc = mt_det_reduce_launch(partials, slots, N1, N2, (long)N1 * N2, C, ldc, s);
   if (rc == MT_OK && colsum) rc = mt_det_reduce_launch(pcs, slots, 1, N1, N1, colsum, N1, s);

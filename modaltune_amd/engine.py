@@ -357,11 +357,14 @@ class Engine:
         self._train16 = {}
         self._pack_table = None
         for pref in self._cross_attn_prefixes():
-            self._train16[pref + "q_proj"] = _W16([t[pref + "q_proj.weight"]], dev)
-            self._train16[pref + "q_in"] = _W16([t[pref + "multihead_attn.q_proj_weight"]], dev)
-            self._train16[pref + "kv"] = _W16([t[pref + "multihead_attn.k_proj_weight"], t[pref + "multihead_attn.v_proj_weight"]], dev)
+            Wq, Wk, Wv = self._mha_weights(pref + "multihead_attn.")      # (packed layout: row slices of in_proj_weight, no copy)
+            if cfg.extractor_ffn:
+                self._train16[pref + "q_proj"] = _W16([t[pref + "q_proj.weight"]], dev)
+            self._train16[pref + "q_in"] = _W16([Wq], dev)
+            self._train16[pref + "kv"] = _W16([Wk, Wv], dev)
             self._train16[pref + "out_in"] = _W16([t[pref + "multihead_attn.out_proj.weight"]], dev)
-            self._train16[pref + "output_proj"] = _W16([t[pref + "output_proj.weight"]], dev)
+            if cfg.extractor_ffn:
+                self._train16[pref + "output_proj"] = _W16([t[pref + "output_proj.weight"]], dev)
         self._caches_ready = True
         self.generation += 1              # new fp16 cache tensors: graphs captured against the old ones are stale
 
@@ -969,11 +972,31 @@ class Engine:
 
     def _mha_in(self, pref: str):
         """Views of nn.MultiheadAttention's packed parameters (adapter_modules.py:157-164)."""
-        P, E = self.store.param, self.cfg.adapter_dim
+        E = self.cfg.adapter_dim
         b = self.store.tensors[pref + "in_proj_bias"]
         gb = self.store.grads[pref + "in_proj_bias"]
         bq, bk, bv = (Param(b[i * E:(i + 1) * E], gb[i * E:(i + 1) * E]) for i in range(3))
-        return P(pref + "q_proj_weight"), P(pref + "k_proj_weight"), P(pref + "v_proj_weight"), bq, bk, bv
+        Wq, Wk, Wv = (Param(w, gw) for w, gw in zip(self._mha_weights(pref), self._mha_weights(pref, self.store.grads)))
+        return Wq, Wk, Wv, bq, bk, bv
+
+    def _mha_weights(self, pref: str, src: Optional[Dict[str, torch.Tensor]] = None):
+        """(q, k, v) input projections of the nn.MultiheadAttention at `pref` out of `src` (the parameter tensors; or a gradient set):
+        the three separate matrices, or -- cfg.packed_in_proj, E == 768 -- the row slices [0, E), [E, 2E), [2E, 3E) of the ONE
+        in_proj_weight [3E, E].  Views either way: no second copy of a parameter, and a slice of the gradient is the flat gradient
+        buffer's own memory."""
+        src = self.store.tensors if src is None else src
+        if self.cfg.packed_in_proj:
+            W, E = src[pref + "in_proj_weight"], self.cfg.adapter_dim
+            return W[:E], W[E:2 * E], W[2 * E:]
+        return src[pref + "q_proj_weight"], src[pref + "k_proj_weight"], src[pref + "v_proj_weight"]
+
+    def _mha_kv_grad(self, pref: str, grads: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """The destination of the Extractor's k | v weight-gradient product: ONE [2E, D] run of the flat gradient buffer -- rows
+        [E, 3E) of in_proj_weight's gradient (packed), else k_proj_weight's gradient with v_proj_weight's right behind it (adjacent
+        slots: E * D % 4 == 0)."""
+        if self.cfg.packed_in_proj:
+            return grads[pref + "in_proj_weight"][self.cfg.adapter_dim:]
+        return grads[pref + "k_proj_weight"]
 
     def _prompt_self_attention(self, c: Var, pe: Param, pref: str, i: int = 0) -> Var:
         """SelfAttentionLayer.forward_pre (AM:81-94).  In train mode cfg.prompt_dropout acts twice (AM:42-52): on the softmax
@@ -985,6 +1008,12 @@ class Engine:
         tn = tape.layernorm(c, P(pref + "norm.weight"), P(pref + "norm.bias"))
         kin = tape.add_rows_param(tn, pe)
         Wq, Wk, Wv, bq, bk, bv = self._mha_in(pref + "self_attn.")
+        if not self.cfg.extractor_ffn:
+            # with_cffn False (AM:84-92): no q_proj / output_proj -- q, k, v straight from the packed rows, and the second dropout
+            # site sits on out_proj's result
+            q, k, v = tape.linear_group([(kin, Wq, bq), (kin, Wk, bk), (tn, Wv, bv)])
+            a = tape.token_mha(q, k, v, self.cfg.num_heads, mean_probs=self._maps.get(pref + "self_attn"), drop=d_probs)
+            return tape.linear(a, P(pref + "self_attn.out_proj.weight"), P(pref + "self_attn.out_proj.bias"), drop=d_res, resid=c)
         q1, k, v = tape.linear_group([(kin, P(pref + "q_proj.weight"), P(pref + "q_proj.bias")), (kin, Wk, bk), (tn, Wv, bv)])
         q = tape.linear(q1, Wq, bq)
         a = tape.token_mha(q, k, v, self.cfg.num_heads, mean_probs=self._maps.get(pref + "self_attn"), drop=d_probs)
@@ -1008,11 +1037,20 @@ class Engine:
         xhat = torch.empty(Mp, D, dtype=H16, device=dev)
         st = torch.empty(Mp, 2, dtype=F32, device=dev)
         ops.layernorm_fwd(src, t[ap + "norm.weight"], t[ap + "norm.bias"], xhat, st, Mp, D, xmap=src_map)
-        q1 = torch.empty(Mp, E, dtype=H16, device=dev)
-        ops.gemm_nt(xhat, w16[ap + "q_proj"].w, q1, Mp, E, D, bias=t[ap + "q_proj.bias"])
-        q2 = torch.empty(Mp, E, dtype=H16, device=dev)
+        # cffn (cfg.extractor_ffn): q_proj in front of the attention's own q projection and output_proj behind its out_proj.  Without
+        # it (with_cffn False, AM:220-233) the q rows of the packed in_proj_weight read LN(x) directly and out_proj carries the
+        # Injector's epilogue itself: two GEMMs and, in the backward, two dX stages and two weight-gradient leaves fewer.
+        cffn = cfg.extractor_ffn
         bqi = t[ap + "multihead_attn.in_proj_bias"][:E]
-        ops.gemm_nt(q1, w16[ap + "q_in"].w, q2, Mp, E, E, bias=bqi)
+        if cffn:
+            q1 = torch.empty(Mp, E, dtype=H16, device=dev)
+            ops.gemm_nt(xhat, w16[ap + "q_proj"].w, q1, Mp, E, D, bias=t[ap + "q_proj.bias"])
+            q2 = torch.empty(Mp, E, dtype=H16, device=dev)
+            ops.gemm_nt(q1, w16[ap + "q_in"].w, q2, Mp, E, E, bias=bqi)
+        else:
+            q1 = xhat                                   # (E == D)
+            q2 = torch.empty(Mp, E, dtype=H16, device=dev)
+            ops.gemm_nt(xhat, w16[ap + "q_in"].w, q2, Mp, E, D, bias=bqi)
         a = torch.empty(Mp, E, dtype=H16, device=dev)
         AHn, AHd = cfg.num_heads, cfg.adapter_head_dim
         alse = torch.empty(Mp, AHn, dtype=F32, device=dev)
@@ -1020,39 +1058,55 @@ class Engine:
         wmap = self._maps.get(ap + "multihead_attn")
         if wmap is not None:
             ops.inject_attn_probs(q2, k.data, alse, wmap, Mp, L, T, heads=AHn, head_dim=AHd)
-        o1 = torch.empty(Mp, E, dtype=H16, device=dev)
-        ops.gemm_nt(a, w16[ap + "out_in"].w, o1, Mp, E, E, bias=t[ap + "multihead_attn.out_proj.bias"])
-        ops.gemm_nt(o1, w16[ap + "output_proj"].w, hin, Mp, D, E, cmap=pm, epilogue=ops.EPI_INJECT, bias=t[ap + "output_proj.bias"],
+        if cffn:
+            o1 = torch.empty(Mp, E, dtype=H16, device=dev)
+            ops.gemm_nt(a, w16[ap + "out_in"].w, o1, Mp, E, E, bias=t[ap + "multihead_attn.out_proj.bias"])
+            last = "output_proj"                        # the projection whose epilogue writes hin: (input, fp16 cache, parameter stem)
+            last_in, last_w = o1, w16[ap + "output_proj"]
+        else:
+            last = "multihead_attn.out_proj"
+            last_in, last_w = a, w16[ap + "out_in"]
+        ops.gemm_nt(last_in, last_w.w, hin, Mp, D, E, cmap=pm, epilogue=ops.EPI_INJECT, bias=t[ap + last + ".bias"],
                     resid=src, ldr=D, rmap=src_map, colscale=t[pref + "gamma"])
         g = self.store.grads
+        gWq = self._mha_weights(ap + "multihead_attn.", g)[0]
         ws = ctx["ws"]
         det = ws.get("det")               # deterministic mode: the workspace's partial buffer (None: the atomic forms)
 
         def bwd():
             dh = ws["dh"]
             proj = torch.empty(Mp, D, dtype=H16, device=dev)
-            ops.gemm_nt(o1, w16[ap + "output_proj"].w, proj, Mp, D, E, bias=t[ap + "output_proj.bias"])
+            ops.gemm_nt(last_in, last_w.w, proj, Mp, D, E, bias=t[ap + last + ".bias"])
             dproj = torch.empty(Mp, D, dtype=H16, device=dev)
             # residual path: dh_patch <- (1+gamma) dh_patch (in place; first: block 0's input x0 needs no gradient -- unless the call
             # carries patch points, which pass first=False: their row dot reads it)
             ops.inject_resid_bwd(dh, src, proj, t[pref + "gamma"], dh if not first else ws["scratch32"], dproj,
                                  g[pref + "gamma"], Mp, D, dymap=pm, xmap=src_map, dxmap=pm if not first else None, det=det)
-            self._leaf(lambda: ops.gemm_tn(dproj, o1, g[ap + "output_proj.weight"], Mp, D, E, colsum=g[ap + "output_proj.bias"], det=det), dproj, o1)
-            do1 = torch.empty(Mp, E, dtype=H16, device=dev)
-            ops.gemm_nt(dproj, w16[ap + "output_proj"].wt, do1, Mp, E, D)
-            self._leaf(lambda: ops.gemm_tn(do1, a, g[ap + "multihead_attn.out_proj.weight"], Mp, E, E, colsum=g[ap + "multihead_attn.out_proj.bias"], det=det),
-                       do1, a)
-            da = torch.empty(Mp, E, dtype=H16, device=dev)
-            ops.gemm_nt(do1, w16[ap + "out_in"].wt, da, Mp, E, E)
+            self._leaf(lambda: ops.gemm_tn(dproj, last_in, g[ap + last + ".weight"], Mp, D, E, colsum=g[ap + last + ".bias"], det=det), dproj, last_in)
+            if cffn:
+                do1 = torch.empty(Mp, E, dtype=H16, device=dev)
+                ops.gemm_nt(dproj, w16[ap + "output_proj"].wt, do1, Mp, E, D)
+                self._leaf(lambda: ops.gemm_tn(do1, a, g[ap + "multihead_attn.out_proj.weight"], Mp, E, E, colsum=g[ap + "multihead_attn.out_proj.bias"], det=det),
+                           do1, a)
+                da = torch.empty(Mp, E, dtype=H16, device=dev)
+                ops.gemm_nt(do1, w16[ap + "out_in"].wt, da, Mp, E, E)
+            else:
+                da = torch.empty(Mp, E, dtype=H16, device=dev)
+                ops.gemm_nt(dproj, w16[ap + "out_in"].wt, da, Mp, E, D)
             dq2 = torch.empty(Mp, E, dtype=H16, device=dev)
             ops.inject_attn_bwd(q2, a, alse, da, k.data, v.data, dq2, k.g(), v.g(), Mp, L, T, heads=AHn, head_dim=AHd, det=det)
-            self._leaf(lambda: ops.gemm_tn(dq2, q1, g[ap + "multihead_attn.q_proj_weight"], Mp, E, E, colsum=g[ap + "multihead_attn.in_proj_bias"][:E], det=det),
+            # (cffn False: q1 is xhat, [Mp, D == E] -- dq2 goes straight to the q rows of in_proj_weight.grad and to dxhat)
+            self._leaf(lambda: ops.gemm_tn(dq2, q1, gWq, Mp, E, E, colsum=g[ap + "multihead_attn.in_proj_bias"][:E], det=det),
                        dq2, q1)
-            dq1 = torch.empty(Mp, E, dtype=H16, device=dev)
-            ops.gemm_nt(dq2, w16[ap + "q_in"].wt, dq1, Mp, E, E)
-            self._leaf(lambda: ops.gemm_tn(dq1, xhat, g[ap + "q_proj.weight"], Mp, E, D, colsum=g[ap + "q_proj.bias"], det=det), dq1, xhat)
-            dxhat = torch.empty(Mp, D, dtype=H16, device=dev)
-            ops.gemm_nt(dq1, w16[ap + "q_proj"].wt, dxhat, Mp, D, E)
+            if cffn:
+                dq1 = torch.empty(Mp, E, dtype=H16, device=dev)
+                ops.gemm_nt(dq2, w16[ap + "q_in"].wt, dq1, Mp, E, E)
+                self._leaf(lambda: ops.gemm_tn(dq1, xhat, g[ap + "q_proj.weight"], Mp, E, D, colsum=g[ap + "q_proj.bias"], det=det), dq1, xhat)
+                dxhat = torch.empty(Mp, D, dtype=H16, device=dev)
+                ops.gemm_nt(dq1, w16[ap + "q_proj"].wt, dxhat, Mp, D, E)
+            else:
+                dxhat = torch.empty(Mp, D, dtype=H16, device=dev)
+                ops.gemm_nt(dq2, w16[ap + "q_in"].wt, dxhat, Mp, D, E)
             if first:
                 ops.layernorm_bwd(dxhat, src, t[ap + "norm.weight"], st, ws["scratch32"], Mp, D, xmap=src_map,
                                   dw=g[ap + "norm.weight"], db=g[ap + "norm.bias"], det=det)
@@ -1109,8 +1163,9 @@ class Engine:
         bkv = t[ap + "multihead_attn.in_proj_bias"][E:]
         ops.gemm_nt(xk, w16[ap + "kv"].w, kv, Mp, 2 * E, D, bias=bkv)
         # token side: q = in_proj_q(q_proj(LN(c) + pe))
+        # (cfg.extractor_ffn False, AM:220-223: no q_proj -- the q rows of the packed in_proj_weight read LN(c) + pe)
         t2 = tape.layernorm(c, P(ap + "norm.weight"), P(ap + "norm.bias"), add_rows=pe)
-        q1 = tape.linear(t2, P(ap + "q_proj.weight"), P(ap + "q_proj.bias"))
+        q1 = tape.linear(t2, P(ap + "q_proj.weight"), P(ap + "q_proj.bias")) if cfg.extractor_ffn else t2
         Wq, _, _, bq, _, _ = self._mha_in(ap + "multihead_attn.")
         q2 = tape.linear(q1, Wq, bq)
         out = Var(tape.new(B, T, E))
@@ -1126,19 +1181,24 @@ class Engine:
             ops.extract_attn_probs(q2.data, kv, lse, wmap, B, T, L, heads=AHn, head_dim=AHd)
 
         det = ws.get("det")               # (deterministic mode, as in the injector)
+        gWkv = self._mha_kv_grad(ap + "multihead_attn.", g)
 
         def bwd_core():
             if out.grad is None:
                 return
             dkv = torch.empty(Mp, 2 * E, dtype=H16, device=dev)
             ops.extract_attn_bwd(q2.data, kv, out.data, lse, out.grad, q2.g(), dkv, B, T, L, heads=AHn, head_dim=AHd, det=det)
-            self._leaf(lambda: ops.gemm_tn(dkv, xk, g[ap + "multihead_attn.k_proj_weight"], Mp, 2 * E, D,       # k | v weights are adjacent
+            self._leaf(lambda: ops.gemm_tn(dkv, xk, gWkv, Mp, 2 * E, D,       # k | v weights are adjacent
                                            colsum=g[ap + "multihead_attn.in_proj_bias"][E:], det=det), dkv, xk)
             dxk = torch.empty(Mp, D, dtype=H16, device=dev)
             ops.gemm_nt(dkv, w16[ap + "kv"].wt, dxk, Mp, D, 2 * E)
             ops.layernorm_bwd(dxk, hout, t[ap + "norm_kq.weight"], st, ws["dh"], Mp, D, xmap=pm, dxmap=pm, accumulate=True,
                               dw=g[ap + "norm_kq.weight"], db=g[ap + "norm_kq.bias"], det=det)
         tape.record(bwd_core)
+        if not cfg.extractor_ffn:
+            # with_cffn False (AM:233,317-327): out_proj carries the 2 c + (.) epilogue itself; no FFN, no DropPath site is drawn (the
+            # sites of the other launches keep their numbers)
+            return tape.linear(out, P(ap + "multihead_attn.out_proj.weight"), P(ap + "multihead_attn.out_proj.bias"), resid=c, resid_scale=2.0)
         o = tape.linear(out, P(ap + "multihead_attn.out_proj.weight"), P(ap + "multihead_attn.out_proj.bias"))
         # c1 = query + (tgt + output_proj(.)) with tgt == query (AM:231,324): 2 c + output_proj(.) on the product's epilogue
         c1 = tape.linear(o, P(ap + "output_proj.weight"), P(ap + "output_proj.bias"), resid=c, resid_scale=2.0)

@@ -64,6 +64,10 @@ def _family(key: str, kind: str) -> str:
     """Which recipe a state_dict key belongs to (see the module docstring)."""
     if kind in ("lnw", "lnb", "gamma"):
         return kind
+    if kind == "w" and key.endswith(".in_proj_weight"):
+        # E == 768 (with_cffn False): `_reset_parameters` draws the PACKED [3E, E] matrix as one xavier-uniform tensor
+        # (adapter_modules.py:59-62,177-180): bound sqrt(6 / (3E + E)), not the sqrt(6 / (E + 768)) of three separate matrices
+        return "xavier_packed"
     if key == "cls_token":
         return "normal"
     if key in ("gene_pe", "gene_cls"):       # nn.init.trunc_normal_(std=0.02) (longvit_adapter.py:149,182)
@@ -106,6 +110,9 @@ def init_state_dict(cfg: ModelConfig, group_sizes: Sequence[int], seed: Optional
             t = _trunc_normal(shape, 0.02, g)
         elif fam == "xavier":
             t = _xavier_uniform(shape, g)
+        elif fam == "xavier_packed":
+            assert len(shape) == 2 and shape[0] == 3 * shape[1], (k, shape)
+            t = _uniform(shape, math.sqrt(6.0 / (4 * shape[1])), g)
         elif fam in ("conv_default", "linear_default_bias"):
             stem = k[:-len("weight")] if k.endswith("weight") else k[:-len("bias")]
             t = _uniform(shape, 1.0 / math.sqrt(max(1, fan_in_of[stem])), g)

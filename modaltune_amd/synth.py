@@ -20,23 +20,34 @@ import numpy as np
 from .config import ModelConfig
 
 
-def _cross_attn_keys(p: str, D: int, E: int) -> List[Tuple[str, tuple, str]]:
-    return [
-        (p + "q_proj.weight", (E, D), "w"), (p + "q_proj.bias", (E,), "b"),
-        (p + "output_proj.weight", (D, E), "w"), (p + "output_proj.bias", (D,), "b"),
-        (p + "multihead_attn.q_proj_weight", (E, E), "w"),
-        (p + "multihead_attn.k_proj_weight", (E, D), "w"),
-        (p + "multihead_attn.v_proj_weight", (E, D), "w"),
-        (p + "multihead_attn.in_proj_bias", (3 * E,), "b"),
-        (p + "multihead_attn.out_proj.weight", (E, E), "w"),
-        (p + "multihead_attn.out_proj.bias", (E,), "b"),
+def _mha_keys(p: str, D: int, E: int, packed: bool) -> List[Tuple[str, tuple, str]]:
+    """nn.MultiheadAttention(E, heads, kdim=D, vdim=D): separate q / k / v matrices, or -- E == D -- ONE packed in_proj_weight [3E, E]."""
+    if packed:
+        w = [(p + "in_proj_weight", (3 * E, E), "w")]
+    else:
+        w = [(p + "q_proj_weight", (E, E), "w"), (p + "k_proj_weight", (E, D), "w"), (p + "v_proj_weight", (E, D), "w")]
+    return w + [(p + "in_proj_bias", (3 * E,), "b"), (p + "out_proj.weight", (E, E), "w"), (p + "out_proj.bias", (E,), "b")]
+
+
+def _cffn_keys(p: str, D: int, E: int, cffn: bool) -> List[Tuple[str, tuple, str]]:
+    """q_proj / output_proj of an attention layer: present with with_cffn only (adapter_modules.py:37-40,152-155)."""
+    if not cffn:
+        return []
+    return [(p + "q_proj.weight", (E, D), "w"), (p + "q_proj.bias", (E,), "b"),
+            (p + "output_proj.weight", (D, E), "w"), (p + "output_proj.bias", (D,), "b")]
+
+
+def _cross_attn_keys(p: str, D: int, E: int, cffn: bool = True, packed: bool = False) -> List[Tuple[str, tuple, str]]:
+    return _cffn_keys(p, D, E, cffn) + _mha_keys(p + "multihead_attn.", D, E, packed) + [
         (p + "norm_kq.weight", (D,), "lnw"), (p + "norm_kq.bias", (D,), "lnb"),
         (p + "norm.weight", (D,), "lnw"), (p + "norm.bias", (D,), "lnb"),
     ]
 
 
-def _extractor_keys(p: str, D: int, E: int):
-    return _cross_attn_keys(p + "attn.", D, E) + [
+def _extractor_keys(p: str, D: int, E: int, cffn: bool = True, packed: bool = False):
+    if not cffn:           # no FFN (and no DropPath) without with_cffn (adapter_modules.py:317-319)
+        return _cross_attn_keys(p + "attn.", D, E, cffn, packed)
+    return _cross_attn_keys(p + "attn.", D, E, cffn, packed) + [
         (p + "ffn.linear1.weight", (E, D), "w"), (p + "ffn.linear1.bias", (E,), "b"),
         (p + "ffn.linear2.weight", (D, E), "w"), (p + "ffn.linear2.bias", (D,), "b"),
         (p + "ffn.norm.weight", (D,), "lnw"), (p + "ffn.norm.bias", (D,), "lnb"),
@@ -51,6 +62,7 @@ def param_specs(cfg: ModelConfig, group_sizes: Sequence[int]) -> List[Tuple[str,
     D, E, F, O = cfg.embed_dim, cfg.adapter_dim, cfg.ffn_dim, cfg.output_dim
     G = len(group_sizes)
     T = cfg.num_tokens
+    cffn, packed = cfg.extractor_ffn, cfg.packed_in_proj
     s: List[Tuple[str, tuple, str, bool]] = []
 
     def add(items, trainable):
@@ -80,19 +92,15 @@ def param_specs(cfg: ModelConfig, group_sizes: Sequence[int]) -> List[Tuple[str,
     for i in range(nint):
         p = f"interactions.{i}."
         add([(p + "injector.gamma", (D,), "gamma")], True)
-        add(_cross_attn_keys(p + "injector.attn.", D, E), True)
-        add(_extractor_keys(p + "extractor.", D, E), True)
+        add(_cross_attn_keys(p + "injector.attn.", D, E, cffn, packed), True)
+        add(_extractor_keys(p + "extractor.", D, E, cffn, packed), True)
         if i == nint - 1 and cfg.use_extra_extractor:
             for j in range(2):
-                add(_extractor_keys(p + f"extra_extractors.{j}.", D, E), True)
+                add(_extractor_keys(p + f"extra_extractors.{j}.", D, E, cffn, packed), True)
     for i in range(1, nint if cfg.use_prompt_sa else 1):      # (use_prompt_sa False: Identity_mod, no parameters)
         p = f"prompt_selfattention.{i}."
-        add([(p + "q_proj.weight", (E, D), "w"), (p + "q_proj.bias", (E,), "b"),
-             (p + "output_proj.weight", (D, E), "w"), (p + "output_proj.bias", (D,), "b"),
-             (p + "self_attn.q_proj_weight", (E, E), "w"), (p + "self_attn.k_proj_weight", (E, D), "w"),
-             (p + "self_attn.v_proj_weight", (E, D), "w"), (p + "self_attn.in_proj_bias", (3 * E,), "b"),
-             (p + "self_attn.out_proj.weight", (E, E), "w"), (p + "self_attn.out_proj.bias", (E,), "b"),
-             (p + "norm.weight", (D,), "lnw"), (p + "norm.bias", (D,), "lnb")], True)
+        add(_cffn_keys(p, D, E, cffn) + _mha_keys(p + "self_attn.", D, E, packed)
+            + [(p + "norm.weight", (D,), "lnw"), (p + "norm.bias", (D,), "lnb")], True)
     g = cfg.gene
     Hd = g.latent_dim
     for i, n in enumerate(group_sizes):

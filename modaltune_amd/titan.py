@@ -864,6 +864,9 @@ def titan_model_config(kwargs: Dict[str, Any], multi_task: int, clinical: bool, 
     kw.setdefault("interaction_indexes", [[0, 1], [2, 3], [4, 5]])
     cfg = ModelConfig.from_json(kw, multi_task=multi_task, clinical=clinical, depth=depth, in_chans=768, embed_dim=768,
                                 dropout=0.0)
+    if cfg.packed_in_proj:      # with_cffn False (E == 768): this engine's caches are written for the separate q / k / v matrices
+        raise NotImplementedError(f"with_cffn={cfg.with_cffn}, cffn_ratio={cfg.cffn_ratio}: full-width adapters are built for the LongNet "
+                                  "configurations (the TITAN configuration keeps E < 768)")
     return cfg
 
 

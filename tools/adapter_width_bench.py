@@ -1,13 +1,14 @@
 """Train-step time and the adapter attention kernels' share of it across adapter widths (`cffn_ratio`, `num_heads`).
 
-    python tools/adapter_width_bench.py [steps=10] [L ...=10000 4096]
+    python tools/adapter_width_bench.py [--full-width] [steps=10] [L ...=10000 4096]
 
-For each (E, heads) of the six pairs of tests/test_adapter_width_gpu.py -- head dims 16 / 32 / 64 at E = 192 and 384 -- and each bag
-length: the median ms of a hipGraph-replayed train step (TrainStep.step_graphed, 3 task passes, dropout off), and from ONE eager step
+For each (E, heads) of the six pairs of tests/test_adapter_width_gpu.py -- head dims 16 / 32 / 64 at E = 192 and 384 -- and the full
+width E = 768 at 12 x 64 / 24 x 32 (with_cffn=False: no q_proj / output_proj / FFN wrap)
+(--full-width: the shipped 12 x 16 and the two full-width rows only) -- and each bag length: the median ms of a hipGraph-replayed train step (TrainStep.step_graphed, 3 task passes, dropout off), and from ONE eager step
 with HIP events around every launch (ops.TIMER) the time of the four templated patch-side kernels (inject_attn_fwd / bwd,
 extract_attn_fwd / bwd: 3 / 3 / 5 / 5 launches per step), their share of the eager step's kernel time, and the HBM rate each achieves
 counted from the tensor sizes (patch-side operands read once, outputs written once; the token side is noise at these lengths).
-Prints one JSON line per (pair, L) and a table."""
+`gemm_tn_ms` is the time of the weight-gradient products (mt_gemm_tn_f16) of that step.  Prints one JSON line per (pair, L) and a table."""
 import json
 import os
 import statistics
@@ -21,10 +22,15 @@ from modaltune_amd.config import ModelConfig  # noqa: E402
 from modaltune_amd.engine import Engine  # noqa: E402
 from modaltune_amd.trainer import TrainStep  # noqa: E402
 
-PAIRS = [(192, 12), (192, 6), (192, 3), (384, 24), (384, 12), (384, 6)]
+# (E, heads, with_cffn)
+FULL = [(768, 12, False), (768, 24, False)]
+PAIRS = [(192, 12, True), (192, 6, True), (192, 3, True), (384, 24, True), (384, 12, True), (384, 6, True)] + FULL
+argv = [a for a in sys.argv[1:] if a != "--full-width"]
+if "--full-width" in sys.argv:
+    PAIRS = [(192, 12, True)] + FULL
 KERNELS = ["inject_attn_fwd", "inject_attn_bwd", "extract_attn_fwd", "extract_attn_bwd"]
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
-lengths = [int(a) for a in sys.argv[2:]] or [10000, 4096]
+steps = int(argv[0]) if argv else 10
+lengths = [int(a) for a in argv[1:]] or [10000, 4096]
 dev = torch.device("cuda", 0)
 B = 3
 
@@ -42,9 +48,9 @@ def bytes_per_launch(name, L, E, heads):
 
 rows = []
 for L in lengths:
-    for E, heads in PAIRS:
-        cfg = ModelConfig(cffn_ratio=E / 768, num_heads=heads, dropout=0.0, drop_path_rate=0.0)
-        assert cfg.adapter_dim == E
+    for E, heads, cffn in PAIRS:
+        cfg = ModelConfig(cffn_ratio=E / 768, with_cffn=cffn, num_heads=heads, dropout=0.0, drop_path_rate=0.0)
+        assert cfg.adapter_dim == E and (cffn or E == 768)
         sizes = synth.toy_group_sizes(6)
         eng = Engine(cfg, sizes, dev)
         eng.load_state_dict(synth.synth_state_dict(cfg, sizes, seed=0))
@@ -73,7 +79,8 @@ for L in lengths:
         kt = {k: [e0.elapsed_time(e1) for e0, e1 in v] for k, v in ops.TIMER.items()}
         ops.TIMER = None
         total = sum(sum(v) for v in kt.values())
-        rec = {"patches": L, "E": E, "heads": heads, "head_dim": E // heads, "ms_per_step": round(statistics.median(ms), 3),
+        rec = {"patches": L, "E": E, "heads": heads, "head_dim": E // heads, "with_cffn": cffn, "gemm_tn_ms": round(sum(sum(v) for k, v in kt.items() if k.startswith("gemm_tn")), 4),
+               "ms_per_step": round(statistics.median(ms), 3),
                "ms_min_max": [round(min(ms), 3), round(max(ms), 3)], "eager_kernel_ms": round(total, 3)}
         ad = 0.0
         for k in KERNELS:
@@ -88,7 +95,8 @@ for L in lengths:
         del ts, eng
         torch.cuda.empty_cache()
 
-print(f"{'L':>6} {'E':>4} {'heads x d':>9} {'ms/step':>8} {'attn ms':>8} {'share':>6}  " + "  ".join(f"{k + ' ms GB/s':>26}" for k in KERNELS))
+print(f"{'L':>6} {'E':>4} {'cffn':>5} {'heads x d':>9} {'ms/step':>8} {'tn ms':>7} {'attn ms':>8} {'share':>6}  " + "  ".join(f"{k + ' ms GB/s':>26}" for k in KERNELS))
 for r in rows:
-    print(f"{r['patches']:>6} {r['E']:>4} {str(r['heads']) + ' x ' + str(r['head_dim']):>9} {r['ms_per_step']:>8.2f} {r['adapter_attn_ms']:>8.3f} "
+    print(f"{r['patches']:>6} {r['E']:>4} {str(r['with_cffn']):>5} {str(r['heads']) + ' x ' + str(r['head_dim']):>9} {r['ms_per_step']:>8.2f} "
+          f"{r['gemm_tn_ms']:>7.3f} {r['adapter_attn_ms']:>8.3f} "
           f"{100 * r['adapter_attn_share']:>5.1f}%  " + "  ".join(f"{r[k]['ms_per_step']:>17.4f} {r[k]['gb_per_s']:>8}" for k in KERNELS))
