@@ -10,6 +10,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import gemm_edge_ref  # noqa: E402
 import unit_inputs  # noqa: E402
 from modaltune_amd import synth  # noqa: E402
 from modaltune_amd.config import ModelConfig, branch_table, segment_lengths  # noqa: E402
@@ -36,6 +37,14 @@ def rng(seed):
     return torch.Generator().manual_seed(seed)
 
 
+def assert_within_elementwise_bound(out, ref, A, W, *extra):
+    """Next to rel(): every element within the derived bound of tests/gemm_edge_ref.py (fp32 accumulation over K, one output rounding)."""
+    ref = ref.double()
+    bound = gemm_edge_ref.plain_bound(A, W, ref, out.dtype, *extra)
+    ratio, at = gemm_edge_ref.errors(out.to(ref.device), ref, bound)
+    assert ratio <= 1.0, f"worst |got - ref| / bound = {ratio:.3g} at {gemm_edge_ref.where(at, 256)}"
+
+
 # ------------------------------------------------------------------------------------------ GEMM
 @pytest.mark.parametrize("M,N,K", [(300, 768, 768), (1000, 192, 768), (257, 3072, 768), (130, 768, 3072), (515, 384, 768),
                                    (4100, 768, 768), (2303, 3072, 768), (2049, 768, 3072), (5000, 2304, 768)])   # >= 2048 rows: 8-wave kernel
@@ -50,6 +59,7 @@ def test_gemm_nt_bias(ops, M, N, K):
         ops.gemm_nt(A.to(DEV), W.to(DEV), out, M, N, K, bias=bias.to(DEV))
         torch.cuda.synchronize()
         assert rel(out, ref) < (2e-3 if dt == torch.float16 else 2e-5)
+        assert_within_elementwise_bound(out, ref, A, W, bias)
 
 
 def test_gemm_nt_rowmaps_resid_inject_posemb(ops):
@@ -114,7 +124,9 @@ def test_gemm_nt_256x256_tile(ops, N, K):
     out = torch.zeros(M, N, dtype=torch.float16, device=DEV)
     ops.gemm_nt(A.to(DEV), W.to(DEV), out, M, N, K, bias=bias.to(DEV))
     torch.cuda.synchronize()
-    assert rel(out, A.double() @ W.double().t() + bias.double()) < 2e-3
+    ref = A.double() @ W.double().t() + bias.double()
+    assert rel(out, ref) < 2e-3
+    assert_within_elementwise_bound(out, ref, A, W, bias)
 
 
 @pytest.mark.parametrize("M,N,K,kind", [(30003, 3072, 768, "bias"), (30003, 768, 3072, "bias"), (30003, 2304, 768, "qkv"), (30003, 768, 768, "bias"),
@@ -162,17 +174,20 @@ def test_gemm_nt_pingpong_tile_height_choice(ops, M, N, K, resid):
     W = (torch.randn(N, K, device=DEV, generator=g) * 0.05).half()
     bias = torch.randn(N, device=DEV, generator=g)
     ref = A.double() @ W.double().t() + bias.double()
+    extra = [bias]
     if resid:
         r = torch.randn(M, N, device=DEV, generator=g)
         out = torch.full((M, N), float("nan"), dtype=torch.float32, device=DEV)
         ops.gemm_nt(A, W, out, M, N, K, epilogue=ops.EPI_BIAS_RESID, bias=bias, resid=r, ldr=N)
         ref += r.double()
+        extra.append(r)
     else:
         out = torch.full((M, N), float("nan"), dtype=torch.float16, device=DEV)
         ops.gemm_nt(A, W, out, M, N, K, bias=bias)
     torch.cuda.synchronize()
     assert int(torch.isnan(out).sum()) == 0
     assert rel(out, ref) < 2e-3
+    assert_within_elementwise_bound(out, ref, A, W, *extra)
 
 
 @pytest.mark.parametrize("M", [333, 2600, 8300])
