@@ -609,6 +609,19 @@ long mt_grad_sumsq_partials_elems(long n);
 int mt_grad_clip_coef(const double* sumsq, int nsums, double grad_mult, const float* scale, double max_norm, const int* found_inf,
                       float* out, mt_stream_t stream);
 
+/* Exact 64-bit checksum of `nwords` 32-bit words (data 4-byte aligned, any nwords >= 1), formed on the device:
+ *   out[0] = sum_{i < nwords} mix(index_base + i) * (word_i + 1)  mod 2^64,   mix(j) = splitmix64(j) | 1
+ *   (z = j + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31)
+ * Unsigned 64-bit arithmetic throughout, so every reduction order gives the same value and pieces compose:
+ * cs(a) = cs(a[:k]) + cs(a[k:], index_base = k).  An odd, position-dependent multiplier: any single-word change and any swap of two
+ * unequal words moves the sum; the + 1 tells zero-filled ranges of different lengths apart.  Two launches in the form of mt_grad_sumsq,
+ * no atomics: every stage-1 workgroup stores into its own slot of `partials` (device 8-byte words, at least
+ * mt_checksum64_partials_elems(nwords) of them, no initialisation needed), one workgroup adds the slots.  index_base >= 0. */
+int mt_checksum64(const void* data, long nwords, long index_base, unsigned long long* partials, long partials_elems,
+                  unsigned long long* out, mt_stream_t stream);
+/* host arithmetic: the slots mt_checksum64 needs for nwords words (non-decreasing in nwords); negative for nwords <= 0 */
+long mt_checksum64_partials_elems(long nwords);
+
 /* Measurement aid (bench.py, SURVEY §8d "the builder's own MFMA micro-benchmark peak"): `workgroups` x 4 waves each issue
  * iters x 4 independent v_mfma_f32_32x32x16_f16 on non-trivial register operands = workgroups * 4 * iters * 4 * 32768 FLOP. */
 int mt_mfma_probe(float* sink, int workgroups, int iters, mt_stream_t stream);

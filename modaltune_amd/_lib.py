@@ -151,6 +151,8 @@ SIGNATURES = {
     "mt_grad_sumsq": [P, L, P, L, P, P, P],
     "mt_grad_sumsq_partials_elems": [L],
     "mt_grad_clip_coef": [P, I, D, P, D, P, P, P],
+    "mt_checksum64": [P, L, L, P, L, P, P],
+    "mt_checksum64_partials_elems": [L],
     "mt_absmax_scale": [P, L, F, P, P],
     "mt_axpy_dev": [P, P, P, P, L, P],
     "mt_coords_to_grid": [P, I, F, I, P, P, P, P],
@@ -184,6 +186,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"mt_status_string": C.c_char_p, "mt_build_id": C.c_char_p, "mt_dilated_attn_bwd_workspace_bytes": C.c_long, "mt_pool_attn_workspace_floats": C.c_long,
              "mt_alibi_dist_halves": C.c_long, "mt_grad_sumsq_partials_elems": C.c_long,
+             "mt_checksum64_partials_elems": C.c_long,
              **{n + "_det_elems": C.c_long for n in ("mt_gemm_tn_f16", "mt_colsum_f16", "mt_layernorm_bwd", "mt_inject_resid_bwd",
                                                      "mt_inject_attn_bwd_hd", "mt_extract_attn_bwd_hd")}}
 

@@ -156,6 +156,76 @@ __global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_final_kernel(const d
   }
 }
 
+// Exact 64-bit checksum of a buffer of 32-bit words (the replica canary and the checkpoint seal):
+//   out[0] = sum_i mix(index_base + i) * (word_i + 1)  mod 2^64,   mix(j) = splitmix64(j) | 1
+// Unsigned integer sums are associative: any grid, any reduction order, the same value -- so the two stages take the form of
+// grad_sumsq_partials / final_kernel above (own slot per workgroup, plain stores, no atomics, no initialised workspace) without their
+// ordering rules.  The multiplier is odd (a single-word change always moves the sum) and depends on the position (swapped words move
+// it); the + 1 makes runs of zeros of different lengths differ; index_base makes pieces compose.  The cross-wave step goes through LDS
+// as 8-byte words only (one LDS banking class, common.h).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64;
+
+MT_DEVINL u64 cs_mix(u64 j) {
+  u64 z = j + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return (z ^ (z >> 31)) | 1ull;
+}
+MT_DEVINL u64 cs_term(u64 j, unsigned w) { return cs_mix(j) * ((u64)w + 1ull); }
+MT_DEVINL u64 cs4(u64 j, u32x4 x) { return (cs_term(j, x[0]) + cs_term(j + 1, x[1])) + (cs_term(j + 2, x[2]) + cs_term(j + 3, x[3])); }
+MT_DEVINL u64 wave_sum_u64(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void checksum64_partials_kernel(const unsigned* __restrict__ d, long n, u64 base, int head,
+                                                                            long nvec, u64* __restrict__ partials) {
+  __shared__ u64 red[SUMSQ_THREADS / MT_WAVE];
+  const int tid = threadIdx.x;
+  const u32x4* __restrict__ dv = reinterpret_cast<const u32x4*>(d + head);
+  const long stride = (long)gridDim.x * SUMSQ_THREADS;
+  const u64 vbase = base + (u64)head;       // index of the first word of vector 0
+  u64 acc = 0;
+  long v = (long)blockIdx.x * SUMSQ_THREADS + tid;
+  for (; v + 3 * stride < nvec; v += 4 * stride) {
+    const u32x4 x0 = dv[v], x1 = dv[v + stride], x2 = dv[v + 2 * stride], x3 = dv[v + 3 * stride];
+    acc += (cs4(vbase + 4 * (u64)v, x0) + cs4(vbase + 4 * (u64)(v + stride), x1)) +
+           (cs4(vbase + 4 * (u64)(v + 2 * stride), x2) + cs4(vbase + 4 * (u64)(v + 3 * stride), x3));
+  }
+  for (; v < nvec; v += stride) acc += cs4(vbase + 4 * (u64)v, dv[v]);
+  if (blockIdx.x == 0) {
+    const long tail0 = head + 4 * nvec;
+    if (tid < head) acc += cs_term(base + (u64)tid, d[tid]);
+    if (tail0 + tid < n) acc += cs_term(base + (u64)(tail0 + tid), d[tail0 + tid]);      // (n - tail0 <= 3)
+  }
+  acc = wave_sum_u64(acc);
+  if ((tid & (MT_WAVE - 1)) == 0) red[tid / MT_WAVE] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    u64 s = red[0];
+#pragma unroll
+    for (int w = 1; w < SUMSQ_THREADS / MT_WAVE; ++w) s += red[w];
+    partials[blockIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(SUMSQ_THREADS) void checksum64_final_kernel(const u64* __restrict__ partials, int nparts,
+                                                                         u64* __restrict__ out) {
+  __shared__ u64 red[SUMSQ_THREADS];
+  const int tid = threadIdx.x, per = (nparts + SUMSQ_THREADS - 1) / SUMSQ_THREADS;
+  u64 s = 0;
+  for (int i = tid * per; i < min(nparts, (tid + 1) * per); ++i) s += partials[i];
+  red[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    u64 t = red[0];
+    for (int i = 1; i < SUMSQ_THREADS; ++i) t += red[i];
+    out[0] = t;
+  }
+}
+
 // torch.nn.utils.clip_grad_norm_'s coefficient on the device, one thread, double throughout, each output rounded once:
 //   out[0] = total_norm = sqrt(sum of the slots, ascending) * grad_mult / *scale
 //   out[1] = coef = min(1, max_norm / (total_norm + 1e-6));   out[2] = *scale / coef: the `scale` mt_adamw_step then divides by
@@ -379,6 +449,30 @@ extern "C" int mt_grad_sumsq(const float* g, long n, double* partials, long part
   return MT_OK;
 }
 
+// stage-1 workgroups = slots of the workspace: a pure function of nwords
+extern "C" long mt_checksum64_partials_elems(long nwords) {
+  if (nwords <= 0) return MT_ERR_BAD_ARG;
+  const long wgs = (nwords + SUMSQ_WG_ELEMS - 1) / SUMSQ_WG_ELEMS;
+  return wgs > SUMSQ_MAX_WGS ? SUMSQ_MAX_WGS : wgs;
+}
+
+extern "C" int mt_checksum64(const void* data, long nwords, long index_base, unsigned long long* partials, long partials_elems,
+                             unsigned long long* out, mt_stream_t stream) {
+  if (!data || !partials || !out || nwords <= 0 || index_base < 0) return MT_ERR_BAD_ARG;
+  if (((uintptr_t)data & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)out & 7)) return MT_ERR_BAD_ARG;
+  const int grid = (int)mt_checksum64_partials_elems(nwords);
+  if (partials_elems < grid) return MT_ERR_BAD_ARG;
+  long head = (long)(((16 - ((uintptr_t)data & 15)) & 15) / 4);
+  if (head > nwords) head = nwords;
+  const long nvec = (nwords - head) / 4;
+  hipLaunchKernelGGL(checksum64_partials_kernel, dim3(grid), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, (const unsigned*)data, nwords,
+                     (u64)index_base, (int)head, nvec, partials);
+  MT_CHECK_LAUNCH();
+  hipLaunchKernelGGL(checksum64_final_kernel, dim3(1), dim3(SUMSQ_THREADS), 0, (hipStream_t)stream, (const u64*)partials, grid, out);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
 extern "C" int mt_grad_clip_coef(const double* sumsq, int nsums, double grad_mult, const float* scale, double max_norm,
                                  const int* found_inf, float* out, mt_stream_t stream) {
   if (!sumsq || !out || nsums < 1 || !(max_norm >= 0.0) || !(grad_mult > 0.0)) return MT_ERR_BAD_ARG;
@@ -436,7 +530,7 @@ extern "C" int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_st
   return MT_OK;
 }
 
-extern "C" int mt_version(void) { return 320; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate; the binary itself is identified by mt_build_id(), not by this number)
+extern "C" int mt_version(void) { return 330; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64; the binary itself is identified by mt_build_id(), not by this number)
 
 extern "C" const char* mt_status_string(int status) {
   switch (status) {

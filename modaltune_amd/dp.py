@@ -238,6 +238,25 @@ class GradReducer:
                 work = dist.all_gather_into_tensor(stage, mine.clone(), group=self.group, async_op=True)
                 self._param_pending.append((work, full, stage))
 
+    def gather_shards_(self, buf: torch.Tensor):
+        """Checkpointing (TrainStep.state_dict): a flat buffer laid out like the parameters of which every rank holds valid values for its
+        own shard of each reduce-scattered range only (the AdamW moments) -> complete on every rank, in place and synchronously.  A
+        collective; a no-op without a sharded bucket."""
+        if not self.sharded:
+            return
+        W, r = self.world, self.rank
+        for o, s, _ in self._rs:
+            self.collectives += 1
+            full, mine = buf[o:o + W * s], buf[o + r * s:o + (r + 1) * s]
+            if self._host:
+                h = torch.empty(W * s, dtype=full.dtype)
+                dist.all_gather_into_tensor(h, mine.cpu(), group=self.group)
+                full.copy_(h)
+            else:
+                stage = torch.empty(W * s, dtype=full.dtype, device=full.device)
+                dist.all_gather_into_tensor(stage, mine.clone(), group=self.group)
+                full.copy_(stage)
+
     def wait_params(self):
         for work, full, stage in self._param_pending:
             work.wait()

@@ -677,6 +677,16 @@ def grad_sumsq(g, n, partials, sumsq, found_inf=None):
     check(_lib.load().mt_grad_sumsq(_p(g), n, _p(partials), partials.numel(), _p(sumsq), _p(found_inf), _s()), "grad_sumsq")
 
 
+def checksum64_partials_elems(nwords: int) -> int:
+    return int(_lib.load().mt_checksum64_partials_elems(nwords))
+
+
+def checksum64(data, nwords, partials, out, index_base: int = 0):
+    """out[0] (int64 holding the unsigned 64-bit value) = the exact checksum of the first `nwords` 32-bit words of `data`; `partials`:
+    int64 workspace of at least checksum64_partials_elems(nwords) elements (include/modaltune_hip.h: mt_checksum64)."""
+    check(_lib.load().mt_checksum64(_p(data), nwords, index_base, _p(partials), partials.numel(), _p(out), _s()), "checksum64")
+
+
 def grad_clip_coef(sumsq, nsums, grad_mult, scale, max_norm, found_inf, out):
     """out[0:3] (fp32) = total norm, clip coefficient, *scale / coefficient (include/modaltune_hip.h: mt_grad_clip_coef)."""
     check(_lib.load().mt_grad_clip_coef(_p(sumsq), nsums, float(grad_mult), _p(scale), float(max_norm), _p(found_inf), _p(out), _s()),
@@ -761,6 +771,7 @@ gene_snn_fwd_points = _timed(lambda *a, **k: "token_side")(gene_snn_fwd_points)
 gene_snn_bwd_input = _timed(lambda *a, **k: "token_side")(gene_snn_bwd_input)
 l2norm_row = _timed(lambda *a, **k: "token_side")(l2norm_row)
 distill_loss = _timed(lambda *a, **k: "token_side")(distill_loss)
+checksum64 = _timed(lambda *a, **k: "checksum64")(checksum64)      # (never part of a default step: the replica canary and state_dict())
 
 
 def timer_summary(timer):

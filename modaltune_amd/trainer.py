@@ -41,8 +41,15 @@ class TrainStep:
                  eps: float = 1e-8, init_scale: float = 2.0 ** 15, growth_interval: int = 2000,
                  process_group=None, task_ids: Sequence[int] = (0, 1, 2), text_rows: Sequence[int] = (0, 1, 3),
                  graph_cache_size: int = 8, capture_after: int = 2, split_passes="auto", accumulate: int = 1,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, verify_every: int = 0):
         self.engine, self.dev = engine, engine.device
+        # Replica canary (data parallel): every `verify_every`-th boundary call ends with verify_replicas() -- the 8-byte checksum of the
+        # flat parameter buffer, MIN- and MAX-reduced over the group, raises on every rank when the replicas differ.  The count of
+        # boundary calls is HOST state.  0 (the default): nothing is launched, allocated or synchronised for it.
+        if int(verify_every) < 0:
+            raise ValueError(f"verify_every must be >= 0 (got {verify_every})")
+        self.verify_every, self._boundaries = int(verify_every), 0
+        self._cs_ws = None      # int64: mt_checksum64's workspace, allocated by the first checksum (never inside a capture)
         # Gradient accumulation and global-norm clipping.  A WINDOW is `accumulate` consecutive calls of step() / step_graphed(), mixed
         # freely: calls 1 .. k-1 are micro-steps (dropout counter, forward, loss, backward ADDING into the flat gradient buffer; no
         # collective, no optimiser, no scaler update), the k-th is the boundary (reduce, inf check, AdamW, scaler update) and applies
@@ -470,6 +477,7 @@ class TrainStep:
         elif update:
             self.optimizer_step()
             self.window_pos = 0
+            self._after_boundary()
         return self.loss
 
     def finish_window(self):
@@ -479,6 +487,7 @@ class TrainStep:
             return
         seen, self.window_pos = self.window_pos, 0
         self.optimizer_step(micro_steps=seen)
+        self._after_boundary()
 
     # ------------------------------------------------------------------ hipGraph replay of the whole step
     def step_graphed(self, x, coords, genes, text, clinical=None) -> torch.Tensor:
@@ -555,6 +564,8 @@ class TrainStep:
                 if boundary:
                     self.optimizer_step()
                 self.window_pos = next_pos
+                if boundary:
+                    self._after_boundary()
                 return self.loss
             if ent is None:
                 ent = _Captured(gen)
@@ -577,6 +588,8 @@ class TrainStep:
             self._opt_graph.replay()
             self.reducer.start_param_gather()
         self.window_pos = next_pos
+        if boundary:
+            self._after_boundary()
         return self.loss
 
     def _trial_split(self, x, coords, genes, text, clinical, L: int, key: tuple, reps: int = 3):
@@ -603,7 +616,7 @@ class TrainStep:
             self.accumulate, key = 1, key[:-1]
             self._gcache.size += 1
             self._gcache.visits[key] = max(self._gcache.visits.get(key, 0), self._gcache.capture_after)
-        counters = (self.graph_replays, self.eager_steps)
+        counters = (self.graph_replays, self.eager_steps, self._boundaries)
         res, caps = {}, {}
         try:
             for split in (False, True):
@@ -622,7 +635,7 @@ class TrainStep:
             if k_window > 1:
                 self._gcache.pop(key)
                 self._gcache.size -= 1
-            self.graph_replays, self.eager_steps = counters
+            self.graph_replays, self.eager_steps, self._boundaries = counters
             for t, c in saved:
                 t.copy_(c)
             eng.refresh_trainable_caches()
@@ -659,6 +672,169 @@ class TrainStep:
         """Inside a capture with world_size > 1: close the current graph at a gradient-bucket boundary, open the next."""
         self._cap.cut()
         self._cap_buckets.append(bucket)
+
+    # ------------------------------------------------------------------ replica canary
+    def _checksum_into(self, t: torch.Tensor, out: torch.Tensor):
+        """out[0] (device int64) = mt_checksum64 over the 32-bit words of `t`."""
+        n = t.numel() * t.element_size() // 4
+        need = ops.checksum64_partials_elems(n)
+        if self._cs_ws is None or self._cs_ws.numel() < need:
+            self._cs_ws = torch.empty(need, dtype=torch.int64, device=self.dev)
+        ops.checksum64(t, n, self._cs_ws, out)
+
+    def param_checksum(self) -> torch.Tensor:
+        """The exact 64-bit checksum of the flat parameter buffer as a device int64[1] (the unsigned value's bits); formed by
+        mt_checksum64 on the current stream behind a parameter all-gather in flight, nothing is read back."""
+        self._wait_params()
+        out = torch.empty(1, dtype=torch.int64, device=self.dev)
+        self._checksum_into(self.engine.store.flat, out)
+        return out
+
+    def verify_replicas(self):
+        """Replicated parameters must be bit-identical on every rank after every step: MIN- and MAX-reduce param_checksum() over the group
+        (two 8-byte collectives, outside any graph), read both back, and raise RuntimeError("replicas diverged ...") on EVERY rank
+        when they differ.  A collective: every rank calls it at the same position.  World size 1: returns at once."""
+        if self._world() == 1:
+            return
+        import torch.distributed as dist
+        lo = self.param_checksum()
+        hi = lo.clone()
+        self.reducer.collectives += 2
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.pg)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.pg)
+        lo_v, hi_v = int(lo), int(hi)
+        if lo_v != hi_v:
+            raise RuntimeError(f"replicas diverged: the parameter checksums of the {self._world()} ranks span {lo_v & (2 ** 64 - 1):#018x} .. "
+                               f"{hi_v & (2 ** 64 - 1):#018x} after {int(self.step_dev)} optimiser steps; rank {self.reducer.rank}")
+
+    def _after_boundary(self):
+        if self.verify_every > 0:
+            self._boundaries += 1
+            if self._boundaries % self.verify_every == 0:
+                self.verify_replicas()
+
+    # ------------------------------------------------------------------ checkpoint / resume (the format: checkpoint.py)
+    def state_dict(self, include_frozen: bool = False) -> dict:
+        """Everything a resume needs, as CPU tensors and plain Python values (checkpoint.py has the format): weights, AdamW moments and
+        step count in torch.optim.AdamW.state_dict() format, the loss scaler in GradScaler.state_dict() format, the Philox state, the
+        learning rate, an open accumulation window with its summed gradient, the pass-group decisions, and the checksums of the three
+        flat buffers formed on the device.  Synchronises, as loss_value() does.  Data parallel: a COLLECTIVE -- every rank calls it at
+        the same position, the moments of the sharded bucket are all-gathered from their owners, every rank returns the same complete
+        dict (rank 0 writes it); inside an open window it raises there (micro-step gradients are rank-local): finish_window() first."""
+        from . import _lib, checkpoint
+        eng, store = self.engine, self.engine.store
+        world = self._world()
+        if world > 1 and self.window_pos > 0:
+            raise RuntimeError(f"state_dict() inside an open accumulation window ({self.window_pos} of {self.accumulate} micro-steps) with "
+                               f"world size {world}: the micro-step gradients are rank-local -- call finish_window() first, or save at a boundary")
+        if store.sync is not None:
+            store.sync()
+        self.reducer.gather_shards_(self.m)
+        self.reducer.gather_shards_(self.v)
+        sums = torch.empty(3, dtype=torch.int64, device=self.dev)
+        for i, t in enumerate((store.flat, self.m, self.v)):
+            self._checksum_into(t, sums[i:i + 1])
+        sums = [checkpoint.as_unsigned(c) for c in sums.cpu().tolist()]
+        names = list(store.slots)
+        keys = list(store.tensors) if include_frozen else names
+        window = None
+        if self.window_pos > 0:
+            window = {"pos": int(self.window_pos), "accumulate": int(self.accumulate), "grad_scale": float(self.grad_scale),
+                      "grad": store.flat_grad.detach().cpu()}
+        hyper = {"lr": self._lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd}
+        return {"format": checkpoint.FORMAT,
+                "model": {k: store.tensors[k].detach().cpu().clone() for k in keys},
+                "optimizer": checkpoint.pack_optimizer(self.m, self.v, int(self.step_dev), store.slots, names, hyper),
+                "scaler": checkpoint.pack_scaler(float(self.scale), int(self.tracker), self.growth_interval),
+                "rng": eng.rng.detach().cpu().clone(), "stochastic": bool(eng.stochastic), "lr": float(self._lr), "window": window,
+                "schedule": {"split_decisions": {int(k): bool(v) for k, v in self.split_decisions.items()}},
+                "checksums": {"flat": sums[0], "m": sums[1], "v": sums[2]},
+                "build_id": _lib.build_info()["build_id"], "world": int(world),
+                "config": checkpoint.config_dict(eng.cfg, store.group_sizes)}
+
+    def load_state_dict(self, sd: dict, verify: bool = True):
+        """Resume from state_dict()'s dict -- or from one assembled from the module path, {"model": model.state_dict(), "optimizer":
+        opt.state_dict(), "scaler": scaler.state_dict()} (then the Philox state stays, the window is empty and nothing is verified).
+        Everything is checked first (format, key set, every shape against this engine's slots: ValueError / KeyError naming the tensor;
+        a `stochastic` that differs from the engine's mode and an open window of another `accumulate`: ValueError); then the state is
+        copied IN PLACE into the existing device tensors -- captured graphs stay valid, nothing is re-bound --, the slot padding of the
+        moments is zeroed, the fp16 operand caches are refreshed (the frozen ones rebuilt only when a frozen tensor changed: that
+        retires the captured graphs), and with `verify` the three checksums are recomputed on the device: RuntimeError naming the
+        buffer on a mismatch.  A different build_id only warns: bit equality with the saved run is then not promised.  Data parallel:
+        every rank loads the complete state (a rank never reads the moments outside its shard)."""
+        import warnings
+        from . import _lib, checkpoint
+        eng, store = self.engine, self.engine.store
+        full = checkpoint.check_format(sd)
+        names = list(store.slots)
+        checkpoint.check_model_shapes(sd["model"], {k: tuple(t.shape) for k, t in store.tensors.items()}, names)
+        flat, m, v, step, hyper = checkpoint.flat_buffers(sd, store.slots, store.n_flat)
+        scaler = checkpoint.unpack_scaler(sd["scaler"]) if len(sd["scaler"]) else None      # ({}: a disabled GradScaler -- the scaler stays)
+        window = sd["window"] if full else None
+        if full and bool(sd["stochastic"]) != bool(eng.stochastic):
+            raise ValueError(f"checkpoint: written with stochastic={bool(sd['stochastic'])}, this engine runs stochastic={bool(eng.stochastic)} "
+                             "(Engine.set_stochastic): the Philox state would mean something else")
+        if full and tuple(sd["rng"].shape) != tuple(eng.rng.shape):
+            raise ValueError(f"checkpoint: rng has shape {tuple(sd['rng'].shape)}, this engine holds {tuple(eng.rng.shape)}")
+        if window is not None:
+            if int(window["accumulate"]) != self.accumulate:
+                raise ValueError(f"checkpoint: saved inside an accumulation window of accumulate={int(window['accumulate'])} "
+                                 f"({int(window['pos'])} micro-steps held), this step runs accumulate={self.accumulate}")
+            if self._world() > 1:
+                raise ValueError("checkpoint: saved inside an accumulation window; such a file resumes at world size 1 only")
+            if tuple(window["grad"].shape) != (store.n_flat,) or not 0 < int(window["pos"]) < self.accumulate:
+                raise ValueError(f"checkpoint: window.grad has shape {tuple(window['grad'].shape)} at position {int(window['pos'])}, this "
+                                 f"engine's flat gradient holds {store.n_flat} elements")
+        # ---- everything checked: from here on the state moves, in place
+        if store.sync is not None:
+            store.sync()
+        store.flat.copy_(flat)
+        frozen_changed = False
+        for k, t in sd["model"].items():
+            if k not in store.slots:
+                src = t.detach().to(self.dev, F32)
+                if not torch.equal(store.tensors[k], src):
+                    store.tensors[k].copy_(src)
+                    frozen_changed = True
+        self.m.copy_(m)
+        self.v.copy_(v)
+        self.step_dev.fill_(int(step))
+        if scaler is not None:
+            self.scale.fill_(scaler[0])
+            self.tracker.fill_(scaler[1])
+        baked = (tuple(self.betas), self.eps, self.wd, self.growth_interval)
+        self.betas, self.eps, self.wd = tuple(hyper["betas"]), hyper["eps"], hyper["weight_decay"]
+        if scaler is not None:
+            self.growth_interval = scaler[2]
+        if baked != (tuple(self.betas), self.eps, self.wd, self.growth_interval):
+            self._gcache.clear()          # (these are launch arguments: captured graphs carry the old values)
+            self._opt_graph = None
+        self.set_lr(sd["lr"] if full else hyper["lr"])
+        self.found_inf.zero_()
+        self.window_pos = 0
+        if full:
+            eng.rng.copy_(sd["rng"])
+            self.split_decisions = {int(k): bool(b) for k, b in sd["schedule"]["split_decisions"].items()}
+            if window is not None:
+                store.flat_grad.copy_(window["grad"])
+                self.grad_scale.fill_(float(window["grad_scale"]))
+                self.window_pos = int(window["pos"])
+        if frozen_changed or not eng._caches_ready:
+            eng._build_caches()
+        else:
+            eng.refresh_trainable_caches()
+        if full and verify:
+            sums = torch.empty(3, dtype=torch.int64, device=self.dev)
+            for i, t in enumerate((store.flat, self.m, self.v)):
+                self._checksum_into(t, sums[i:i + 1])
+            for name, have in zip(("flat", "m", "v"), sums.cpu().tolist()):
+                have, want = checkpoint.as_unsigned(have), checkpoint.as_unsigned(sd["checksums"][name])
+                if have != want:
+                    raise RuntimeError(f"checkpoint: checksum of `{name}` on the device is {have:#018x} after the load, the checkpoint "
+                                       f"records {want:#018x}")
+        if full and sd["build_id"] != _lib.build_info()["build_id"]:
+            warnings.warn(f"checkpoint written by build {str(sd['build_id'])[:12]}, this is build {_lib.build_info()['build_id'][:12]}: the "
+                          "resumed run is not promised to continue with the saved run's bits")
 
     def loss_value(self) -> float:
         """The last step's loss on the host.  This is where the trainer synchronises anyway (`loss.item()`, TM:239), so the
