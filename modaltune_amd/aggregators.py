@@ -66,7 +66,7 @@ def _slide_key(x, coords):
 
 
 def _bridge_backward(ctx, dlogits):
-    """Shared by the LongNet and TITAN bridges: returns (gradient of the chain token input or None, tuple of parameter
+    """_ModelFn.backward: returns (gradient of the chain token input or None, tuple of parameter
     gradients or Nones).  A node reached WITHOUT a gradient for its logits (only the chain token's) passes the chain on and keeps
     its tape: a trainer that backpropagates the task losses one by one (`loss_t.backward()` per task instead of the reference's
     single `loss.backward()`) meets the node again later with its own gradient, and every such pass hands over exactly what it
@@ -140,7 +140,7 @@ class _ModelFn(torch.autograd.Function):
             ctx.module, ctx.call, ctx.group, ctx.has_pred = module, "replay", grp, False
             ctx.batched = module.is_multi and logits.shape[0] > 1
             return logits, torch.zeros((), dtype=F32, device=logits.device)
-        if need and grp is not None and pass_groups.eligible(eng, B, L, module.split_min_patches, module.split_passes):
+        if need and grp is not None and eng.PASS_GROUPS and pass_groups.eligible(eng, B, L, module.split_min_patches, module.split_passes):
             # A batched pass over a long bag runs as TWO concurrent pass groups on two HIP streams (pass_groups.py has the mechanics
             # and the measurements) -- own workspace, tape, dropout masks and gradient set per group, the task-independent patch
             # embedding once in front of the fork.
@@ -159,8 +159,8 @@ class _ModelFn(torch.autograd.Function):
             ctx.module, ctx.call, ctx.group, ctx.has_pred = module, calls, grp, token is not None
             ctx.batched = True
             return logits, torch.zeros((), dtype=F32, device=logits.device)
-        logits = eng.forward(x, coords, genes, onehots, need_grad=need, fresh=need, clinical=clinical,
-                             share=grp.share if grp is not None else None)
+        logits = eng.forward_slide(x, coords, genes, onehots, patch_size_lv0=module._extra_key(), need_grad=need, fresh=need,
+                                   clinical=clinical, share=grp.share if grp is not None else None)
         ctx.module, ctx.call, ctx.group, ctx.has_pred = module, (eng.last_call if need else None), grp, token is not None
         ctx.batched = module.is_multi and logits.shape[0] > 1
         return logits.clone(), torch.zeros((), dtype=F32, device=logits.device)
@@ -514,8 +514,7 @@ class LongNetGeneAdapter(Aggregator):
         Like attention_maps, this runs the eval forward -- no Dropout / DropPath -- whatever `model.training` says, and leaves the
         parameters, their gradients and every captured graph as they were."""
         from .attribution import IntegratedGradients
-        if hasattr(self.engine, "forward_slide"):
-            raise NotImplementedError("Integrated Gradients over the gene inputs of the TITAN configuration are not supported")
+        self.engine.refuse("integrated_gradients")
         key = (tuple(int(t) for t in task_ids) if self.is_multi else (0,), int(steps), str(inputs))
         ig = getattr(self, "_ig", None)
         if ig is None or ig[0] != key:

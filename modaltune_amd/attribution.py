@@ -53,8 +53,7 @@ class IntegratedGradients:
 
     def __init__(self, engine: Engine, task_ids: Sequence[int] = (0, 1, 2), steps: int = 64, points_per_pass: int = 3,
                  inputs: str = "genes"):
-        if hasattr(engine, "forward_slide"):
-            raise NotImplementedError("Integrated Gradients over the gene inputs of the TITAN configuration are not supported")
+        engine.refuse("integrated_gradients")
         if inputs not in INPUTS:
             raise ValueError(f"inputs must be one of {INPUTS}, got {inputs!r}")
         if inputs != "genes" and engine.cfg.first_interaction_layer != 0:

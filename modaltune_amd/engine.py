@@ -188,6 +188,20 @@ def deterministic_default() -> bool:
 
 class Engine:
     DETERMINISTIC_REFUSAL = None      # (a subclass that cannot run the deterministic mode says why: TitanEngine)
+    REFUSALS: Dict[str, str] = {}     # feature -> why a subclass cannot do it ("attention_maps", "points", "integrated_gradients"): refuse()
+    # What the callers of the slide protocol (the three *slide* methods behind forward()) ask instead of the engine's type:
+    ROWS_FROM_STAGING = False         # the row count of a slide is only known behind stage_slide()'s read-back (else: its patch count)
+    PASS_GROUPS = True                # pass groups are a schedule of this engine's callers (False: only TrainStep's, and only when forced)
+    MODULE_REPLAY = True              # module_graph.ModuleReplay can capture this engine's calls (it stages with stage_inputs)
+
+    @property
+    def replayable(self) -> bool:
+        """The step from stage_slide()'s read-back on is HIP launches only: it can be captured into a hipGraph."""
+        return True
+
+    def refuse(self, feature: str):
+        if feature in self.REFUSALS:
+            raise NotImplementedError(self.REFUSALS[feature])
 
     def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device="cuda", deterministic: Optional[bool] = None):
         """deterministic (None: deterministic_default()): the train step runs the launchers' deterministic forms (include/modaltune_hip.h:
@@ -662,6 +676,39 @@ class Engine:
         self._maps = {}
         return logits.data
 
+    # -- the slide protocol: what TrainStep, EmbeddingExtractor and the module bridge call, whichever engine they hold (TitanEngine
+    # overrides all three: its slide is gridded first, and only the gridding's read-back says how many rows it has)
+    def stage_slide(self, x, coords, patch_size_lv0=None, B: Optional[int] = None) -> int:
+        """Eager half of a hipGraph-replayed step: the slide uploaded into the static buffers of the B-pass workspace (stage_inputs).
+        Returns its row count -- every shape downstream depends on it, it is the key of the captured geometry and the `staged_rows`
+        of the calls that continue from here."""
+        self.stage_inputs(x, coords, B=B)
+        return int(x.reshape(-1, x.shape[-1]).shape[0])
+
+    def slide_prologue(self, x, coords, share: dict, B: int, staged_rows: Optional[int] = None, patch_size_lv0=None,
+                       need_grad: bool = True) -> int:
+        """The task-independent part of a slide once, in front of a fork: uploaded (unless stage_slide() has: staged_rows) and
+        embedded in the workspace of the first group's B passes, left in `share` for the groups' own calls (share=, staged_rows=).
+        Returns the row count."""
+        if staged_rows is None:
+            x = x.reshape(-1, x.shape[-1])
+            L = x.shape[0]
+            ws = self._workspace(B, L)
+            self.stage_inputs(x, coords, ws)
+        else:
+            L = staged_rows
+            ws = self._workspace(B, L)
+        self._embed_patches(None, None, ws, True, L)
+        share["x0"] = ws["x0"]
+        return L
+
+    def forward_slide(self, x, coords, genes, task_onehots, *, staged_rows: Optional[int] = None, patch_size_lv0=None, **kw) -> torch.Tensor:
+        """forward() of one slide.  staged_rows: what stage_slide() / slide_prologue() returned for it (x / coords are not read
+        again); patch_size_lv0 is for the engines that grid the slide; **kw: forward()'s keywords."""
+        if staged_rows is not None:
+            kw.update(staged=True, geometry=(int(task_onehots.shape[0]), staged_rows))
+        return self.forward(x, coords, genes, task_onehots, **kw)
+
     def prepare_shared(self, x, coords, share: dict):
         """The task-independent part of a slide's forward (input cast, grid indices, patch-embed GEMM + positional term) into buffers
         of its own, left in `share` for the calls that follow: callers that run those calls on SEVERAL streams (the module bridge's
@@ -681,9 +728,7 @@ class Engine:
     def attention_map_shapes(self, B: int, L: int) -> Dict[str, tuple]:
         """site -> shape of its map for B task passes over L patches: injector [B, L, T] (patch rows over tokens), extractor
         [B, T, L] (tokens over patch rows), prompt self-attention [B, T, T]."""
-        if hasattr(self, "forward_slide"):
-            raise NotImplementedError("attention maps of the TITAN configuration are not supported: its adapters attend over gridded "
-                                      "cells, and drawing them on the slide needs the cell-to-coordinate map")
+        self.refuse("attention_maps")
         T = self.T
         return {s: (B, T, T) if s.startswith("prompt_") else (B, L, T) if ".injector." in s else (B, T, L)
                 for s in attention_sites(self.cfg)}
@@ -826,8 +871,7 @@ class Engine:
 
     # ------------------------------------------------------------------ token-side pieces
     def _check_points(self, points: "GenePoints", B: int):
-        if hasattr(self, "forward_slide"):
-            raise NotImplementedError("input gradients of the TITAN configuration are not supported")
+        self.refuse("points")
         if B > ops.GENE_POINTS_MAX:
             raise ValueError(f"points: at most {ops.GENE_POINTS_MAX} points per engine pass, got {B}")
         n = self._gene_total
@@ -839,8 +883,7 @@ class Engine:
                 raise ValueError(f"points.{nm}: expected a contiguous fp32 tensor of {want} element(s) on {self.device}")
 
     def _check_patch_points(self, pp: "PatchPoints", B: int, L: int, need_grad: bool):
-        if hasattr(self, "forward_slide"):
-            raise NotImplementedError("input gradients of the TITAN configuration are not supported")
+        self.refuse("points")
         if self.cfg.first_interaction_layer != 0:
             raise NotImplementedError("patch_points: first_interaction_layer > 0 is not supported (the layers in front of the first "
                                       "interaction run forward-only)")

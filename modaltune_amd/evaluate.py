@@ -51,7 +51,7 @@ class EmbeddingExtractor:
         self.engine, self.dev, self.graphed = engine, engine.device, graphed
         self.sites: Optional[Tuple[str, ...]] = None
         if attention is not None and attention is not False:
-            engine.attention_map_shapes(1, 1)                   # (raises NotImplementedError for the TITAN engine)
+            engine.attention_map_shapes(1, 1)                   # (raises NotImplementedError for an engine that refuses them)
             every = attention_sites(engine.cfg)
             self.sites = tuple(every) if attention is True else tuple(attention)
             bad = [s for s in self.sites if s not in every]
@@ -77,17 +77,16 @@ class EmbeddingExtractor:
         eng, pg = self.engine, self._pg
         groups = pass_groups.group_bounds(B)
         pg.ensure(len(groups))
-        ws0 = eng._workspace(groups[0][1], L)
-        eng._embed_patches(None, None, ws0, True, L)
-        share = {"x0": ws0["x0"]}
+        share = {}
+        eng.slide_prologue(None, None, share, groups[0][1], staged_rows=L, patch_size_lv0=self.patch_size_lv0, need_grad=False)
         out = torch.empty(B, eng.cfg.output_dim, dtype=F32, device=self.dev)
         maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None      # (each group writes its rows)
         pg.fork(len(groups))
         for gi, (lo, hi) in enumerate(groups):
             with pg.group(gi):
-                lg = eng.forward(None, None, self._sgenes, self.onehots[lo:hi], need_grad=False, staged=True, geometry=(hi - lo, L),
-                                 clinical=self._sclin, share=share, tape=pg.tapes[gi], site_group=gi + 1,
-                                 attn_maps={s: w[lo:hi] for s, w in maps.items()} if maps else None)
+                lg = eng.forward_slide(None, None, self._sgenes, self.onehots[lo:hi], staged_rows=L, patch_size_lv0=self.patch_size_lv0,
+                                       need_grad=False, clinical=self._sclin, share=share, tape=pg.tapes[gi], site_group=gi + 1,
+                                       attn_maps={s: w[lo:hi] for s, w in maps.items()} if maps else None)
                 out[lo:hi].copy_(lg)
         pg.join()
         return (out, maps) if maps else out
@@ -95,8 +94,8 @@ class EmbeddingExtractor:
     def _forward_batched(self, B: int, L: int):
         eng = self.engine
         maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None
-        lg = eng.forward(None, None, self._sgenes, self.onehots, need_grad=False, staged=True, geometry=(B, L), clinical=self._sclin,
-                         attn_maps=maps)
+        lg = eng.forward_slide(None, None, self._sgenes, self.onehots, staged_rows=L, patch_size_lv0=self.patch_size_lv0, need_grad=False,
+                               clinical=self._sclin, attn_maps=maps)
         return (lg, maps) if maps else lg
 
     @property
@@ -111,34 +110,26 @@ class EmbeddingExtractor:
         tensor per call: replays write a static buffer that is copied out).  With an attention request: (logits, {site: map}),
         the maps fresh tensors as well."""
         eng = self.engine
-        titan = hasattr(eng, "forward_slide")
         if not eng._caches_ready:
             eng._build_caches()
         x = x.reshape(-1, x.shape[-1])
         L, B = x.shape[0], self.onehots.shape[0]
         if isinstance(genes, dict):
             genes = [genes[k] for k in sorted(genes.keys())]
-        split = False
-        replayable = self.graphed and (not titan or (getattr(eng, "native", False) and getattr(eng.backbone, "embed_w", None) is not None))
-        if not replayable:      # (TITAN on the module's own torch blocks: nothing to capture)
-            if titan:
-                return eng.forward_slide(x, coords, list(genes), self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=False,
-                                         clinical=clinical)
+        if not (self.graphed and eng.replayable):      # (or: TITAN on the module's own torch blocks: nothing to capture)
             maps = eng.new_attention_maps(self.sites, B, L) if self.sites else None
-            lg = eng.forward(x, coords, list(genes), self.onehots, need_grad=False, clinical=clinical, attn_maps=maps)
+            lg = eng.forward_slide(x, coords, list(genes), self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=False,
+                                   clinical=clinical, attn_maps=maps)
             return (lg, maps) if maps else lg
         gflat = flatten_genes(genes)
-        if titan:
-            Lv = eng.stage_slide(x, coords, self.patch_size_lv0)      # eager gridding + the one read-back -> token count
-            eng._workspace(B, Lv)                                     # (may grow the workspace: bumps eng.generation)
-        else:
-            Lv = L
-            # long bags: the task passes as two concurrent groups on two HIP streams, as in the train step
-            split = pass_groups.eligible(eng, B, L, self.split_min_patches, self.split_passes)
-            gB = [hi - lo for lo, hi in pass_groups.group_bounds(B)] if split else [B]
-            for nb in gB[1:]:
-                eng._workspace(nb, L)
-            eng.stage_inputs(x, coords, B=gB[0])                      # (may grow the workspace: bumps eng.generation)
+        # long bags: the task passes as two concurrent groups on two HIP streams, as in the train step
+        split = eng.PASS_GROUPS and pass_groups.eligible(eng, B, L, self.split_min_patches, self.split_passes)
+        gB = [hi - lo for lo, hi in pass_groups.group_bounds(B)] if split else [B]
+        for nb in gB[1:]:
+            eng._workspace(nb, L)
+        # (TITAN configuration: eager gridding + the one read-back -> token count; both lines may grow the workspace: bumps eng.generation)
+        Lv = eng.stage_slide(x, coords, self.patch_size_lv0, B=gB[0])
+        eng._workspace(gB[0], Lv)
         skey = int(gflat.numel())
         if self._static_key != skey:
             self._static_key = skey
@@ -153,13 +144,7 @@ class EmbeddingExtractor:
         key = (L, Lv, eng.generation, self.sites)           # (the maps are static outputs of the capture, like the logits)
         cache = self._cache
         cache.sync(eng.generation)
-        if titan:
-            run = lambda: eng.forward_slide(None, None, self._sgenes, self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=False,
-                                            clinical=self._sclin, staged=True)
-        elif split:
-            run = lambda: self._forward_groups(B, L)
-        else:
-            run = lambda: self._forward_batched(B, L)
+        run = (lambda: self._forward_groups(B, Lv)) if split else (lambda: self._forward_batched(B, Lv))
         ent = cache.get(key)
         if ent is None:
             if not cache.admit(key):

@@ -81,7 +81,7 @@ class ModuleReplay:
         capture that makes the next ones replays; None when the eager path has to run it."""
         m = self.module
         eng = m.engine
-        if not self.enabled or token is not None or eng.collect_taps or hasattr(eng, "forward_slide"):
+        if not self.enabled or token is not None or eng.collect_taps or not eng.MODULE_REPLAY:
             return None
         x2 = x.reshape(-1, x.shape[-1])
         L, B = int(x2.shape[0]), int(onehots.shape[0])

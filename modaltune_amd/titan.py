@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from . import init, ops
-from .aggregators import Aggregator, LongNetGeneAdapter, _bridge_backward
+from .aggregators import Aggregator, LongNetGeneAdapter
 from .config import ModelConfig
 from .engine import Engine, F32, H16, _W16, deterministic_default
 from .tape import Param, Var
@@ -671,6 +671,14 @@ class TitanEngine(Engine):
                              "accumulate the feature grid with fp32 atomics in the forward (scatter_rows_kernel, csrc/optim.hip) and no ordered "
                              "form of it exists yet -- the deterministic mode covers the LongNet configurations only")
 
+    REFUSALS = {"attention_maps": "attention maps of the TITAN configuration are not supported: its adapters attend over gridded "
+                                  "cells, and drawing them on the slide needs the cell-to-coordinate map",
+                "points": "input gradients of the TITAN configuration are not supported",
+                "integrated_gradients": "Integrated Gradients over the gene inputs of the TITAN configuration are not supported"}
+    ROWS_FROM_STAGING = True      # the token count comes back from the gridding
+    PASS_GROUPS = False           # parity-green and never a win (trainer.TrainStep._can_split has the figures)
+    MODULE_REPLAY = False         # the module's calls take the eager bridge
+
     def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], backbone, device="cuda", deterministic: Optional[bool] = None):
         super().__init__(cfg, group_sizes, device, deterministic=deterministic)
         self.backbone = backbone
@@ -680,6 +688,11 @@ class TitanEngine(Engine):
     @property
     def native(self) -> bool:
         return self.backbone is not None and self.backbone.kind == "native"
+
+    @property
+    def replayable(self) -> bool:
+        """Native blocks behind the native embedding: nothing of the module's own torch code runs between the HIP kernels."""
+        return self.backbone is not None and self.native and self.backbone.embed_w is not None
 
     def _build_caches(self):         # no LongNet weights to pack: only the trainable big-M adapter linears
         t, dev = self.store.tensors, self.device
@@ -718,10 +731,10 @@ class TitanEngine(Engine):
             raise ValueError("TITAN slide: non-finite or out-of-range coordinates")
         super().check_inputs()
 
-    def stage_slide(self, x, coords, patch_size_lv0: int = 1024) -> int:
+    def stage_slide(self, x, coords, patch_size_lv0: int = 1024, B: Optional[int] = None) -> int:
         """Eager half of a hipGraph-replayed step: the slide's gridding into static buffers and the one host read-back -> token count
-        (the key of the captured geometry).  forward_slide(..., staged=True) continues from the token gather."""
-        if self.backbone is None or not self.native or self.backbone.embed_w is None:
+        (the key of the captured geometry).  forward_slide(..., staged_rows=) continues from the token gather.  B: not needed here."""
+        if not self.replayable:
             raise NotImplementedError("hipGraph replay of the TITAN configuration needs the native backbone with its native embedding")
         if getattr(self, "_grid_stage", None) is None:
             self._grid_stage = GridStage(self.device)
@@ -732,18 +745,13 @@ class TitanEngine(Engine):
             self.generation += 1            # captured graphs read the old buffers
         return self._grid_stage.run(x, coords, patch_size_lv0, self._titan_err)      # (ONE copy: host / device, any float dtype -> the static fp32 buffer)
 
-    def forward_slide(self, x, coords, genes, task_onehots, patch_size_lv0: int = 1024, need_grad: bool = True, fresh: bool = False,
-                      clinical=None, share: Optional[dict] = None, staged: bool = False, tape=None, site_group: int = 0,
-                      prologue_only: bool = False, ws_slot: int = 0) -> Optional[torch.Tensor]:
-        """x [1, L, C] tile embeddings, coords [1, L, 2] level-0 pixels (TA:329-353) -> logits [B, output_dim].
-        share: see Engine.forward -- here the whole task-independent prologue (gridding, embedding, the ALiBi distance table) is
-        reused by the later calls of one slide; a call with another pass count builds its plan on the shared table.
-        prologue_only: run just that prologue into `share` (TrainStep's pass groups fork behind it); tape / site_group: Engine.forward."""
+    def _prologue(self, x, coords, B: int, patch_size_lv0: int, need_grad: bool, share: Optional[dict], staged: bool) -> int:
+        """The task-independent part of a slide -- gridding, token gather, patch embedding, the ALiBi distance table and the plan of B
+        passes -- or, from the second call of a slide on, what the first one left in `share`.  Returns the token count."""
         bb = self.backbone
         if bb is None:
             raise RuntimeError("titan_gene_adapter needs the TITAN slide encoder: pass backbone=<VisionTransformer from the "
                                "MahmoodLab/TITAN snapshot> (its source is not part of ModalTune; parity unpinned)")
-        B = int(task_onehots.shape[0])
         self._need = need_grad
         if not staged and x is not None and x.reshape(-1, x.shape[-1]).shape[0] < 1:
             raise ValueError("empty bag: 0 tile embeddings (a slide needs at least one)")
@@ -783,13 +791,27 @@ class TitanEngine(Engine):
         if share is not None and "tok" not in share:
             share.update(titan_B=B, tok=self._tok, plan=self._plan, keep=self._plan_keep, bias=getattr(self, "_bias", None),
                          mask=getattr(self, "_mask", None))
-        patches = self._tok[1:]
-        if patches.shape[0] < 1:
+        rows = int(self._tok.shape[0]) - 1
+        if rows < 1:
             raise ValueError("slide has no foreground cell")
-        if prologue_only:
-            return None
-        return self.forward(patches, None, genes, task_onehots, need_grad=need_grad, fresh=fresh, clinical=clinical, share=share,
-                            tape=tape, site_group=site_group, ws_slot=ws_slot)
+        return rows
+
+    def slide_prologue(self, x, coords, share: dict, B: int, staged_rows: Optional[int] = None, patch_size_lv0: int = 1024,
+                       need_grad: bool = True) -> int:
+        """Engine.slide_prologue: the whole prologue once, in front of a fork (TrainStep's pass groups); the groups' own calls take
+        the tokens, the distance table and -- as their patch embedding -- the token rows themselves from `share`."""
+        rows = self._prologue(x, coords, B, patch_size_lv0, need_grad, share, staged_rows is not None)
+        share["x0"] = share["tok"][1:]
+        return rows
+
+    def forward_slide(self, x, coords, genes, task_onehots, *, staged_rows: Optional[int] = None, patch_size_lv0: int = 1024,
+                      need_grad: bool = True, share: Optional[dict] = None, **kw) -> torch.Tensor:
+        """x [1, L, C] tile embeddings, coords [1, L, 2] level-0 pixels (TA:329-353) -> logits [B, output_dim].
+        share: see Engine.forward -- here the whole task-independent prologue (gridding, embedding, the ALiBi distance table) is
+        reused by the later calls of one slide; a call with another pass count builds its plan on the shared table.
+        staged_rows: stage_slide() has gridded the slide; **kw: Engine.forward's keywords (fresh, clinical, tape, site_group, ws_slot, ...)."""
+        self._prologue(x, coords, int(task_onehots.shape[0]), patch_size_lv0, need_grad, share, staged_rows is not None)
+        return self.forward(self._tok[1:], None, genes, task_onehots, need_grad=need_grad, share=share, **kw)
 
     # -- image-side hooks
     def _embed_patches(self, x, coords, ws, staged, L):
@@ -947,6 +969,7 @@ class TITANGeneAdapter(LongNetGeneAdapter):
         self._group = self._token = None
         self._spec = self._hist = self._spec_rows = None
         self.speculate = True
+        self._replay = None      # (TitanEngine.MODULE_REPLAY is False: every call takes the eager bridge)
         self._init_nosync()
         self._call_psz = 1024
         try:
@@ -1042,29 +1065,6 @@ class TITANGeneAdapter(LongNetGeneAdapter):
 
     def _extra_key(self):
         return self._call_psz
-
-    def _apply_bridge(self, x, coords, genes, onehots, need, clinical, token):
-        return _TitanFn.apply(self, x, coords, genes, onehots, need, clinical, self._call_psz, token, *self._trainable.values())
-
-
-class _TitanFn(torch.autograd.Function):
-    """Same bridge as aggregators._ModelFn (chained calls of a step: aggregators._StepGroup) with the TITAN entry point."""
-
-    @staticmethod
-    def forward(ctx, module, x, coords, genes, onehots, need, clinical, psz, token, *params):
-        eng = module.engine
-        ctx.set_materialize_grads(False)
-        grp = module._group if need else None
-        logits = eng.forward_slide(x, coords, genes, onehots, patch_size_lv0=psz, need_grad=need, fresh=need, clinical=clinical,
-                                   share=grp.share if grp is not None else None)
-        ctx.module, ctx.call, ctx.group, ctx.has_pred = module, (eng.last_call if need else None), grp, token is not None
-        ctx.batched = module.is_multi and logits.shape[0] > 1
-        return logits.clone(), torch.zeros((), dtype=F32, device=logits.device)
-
-    @staticmethod
-    def backward(ctx, dlogits, dtoken):
-        tok, grads = _bridge_backward(ctx, dlogits)
-        return (None,) * 8 + (tok,) + grads
 
 
 @Aggregator.register("titan_gene_clinical_adapter")

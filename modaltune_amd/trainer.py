@@ -221,10 +221,7 @@ class TrainStep:
         eng = self.engine
         if not pass_groups.eligible(eng, len(self.onehots), None, 0, self.split_passes, min_passes=2):
             return False
-        if not hasattr(eng, "forward_slide"):
-            return True
-        return bool(pass_groups.split_mode() == "force" and getattr(eng, "native", False)
-                    and getattr(getattr(eng, "backbone", None), "embed_w", None) is not None)
+        return bool(eng.PASS_GROUPS or (pass_groups.split_mode() == "force" and eng.replayable))
 
     def _split_now(self, L: Optional[int] = None) -> bool:
         """This step runs as pass groups: "force" wherever possible, else a trial's decision for L patches, else the threshold."""
@@ -251,28 +248,12 @@ class TrainStep:
             eng.store.sync()
         if not eng._caches_ready:
             eng._build_caches()
-        gB = [b - a for a, b in self._groups]
-        titan = hasattr(eng, "forward_slide")
-        if titan:
-            # TITAN configuration: gridding, token gather, patch-embedding MLP and the ALiBi distance table once, in front of the fork
-            share = {}
-            eng.forward_slide(x, coords, genes, self.onehots[:gB[0]], patch_size_lv0=self.patch_size_lv0, need_grad=True, clinical=clinical,
-                              staged=staged_geometry is not None, share=share, prologue_only=True)
-            share["x0"] = share["tok"][1:]
-            L = int(share["tok"].shape[0]) - 1
-            self._group_workspaces(L, True)
-        else:
-            if staged_geometry is None:
-                x = x.reshape(-1, x.shape[-1])
-                L = x.shape[0]
-                ws0 = eng._workspace(gB[0], L)
-                eng.stage_inputs(x, coords, ws0)
-            else:
-                L = staged_geometry[1]
-                ws0 = eng._workspace(gB[0], L)         # (step_graphed staged the slide into the first group's workspace)
-            self._group_workspaces(L, True, first=1)
-            eng._embed_patches(None, None, ws0, True, L)        # task-independent: once, in front of the fork
-            share = {"x0": ws0["x0"]}
+        # task-independent, once in front of the fork: the upload (step_graphed has staged the slide into the first group's workspace)
+        # and the patch embedding; TITAN configuration: gridding, token gather, patch-embedding MLP and the ALiBi distance table
+        share, staged_rows = {}, None if staged_geometry is None else staged_geometry[1]
+        L = eng.slide_prologue(x, coords, share, self._groups[0][1] - self._groups[0][0], staged_rows=staged_rows,
+                               patch_size_lv0=self.patch_size_lv0)
+        self._group_workspaces(L, True)
         R, O = target.shape
         logits_all = torch.empty(R, O, dtype=F32, device=self.dev)
         self.grad_scale.copy_(self.scale)
@@ -286,12 +267,9 @@ class TrainStep:
         try:
             for gi, (a, b) in enumerate(self._groups):
                 with pg.group(gi, zero="all" if zero else "extra"):
-                    own = dict(need_grad=True, staged=True, clinical=clinical, share=share, tape=pg.tapes[gi], site_group=gi + 1,
-                               ws_slot=self._group_slots[gi])
-                    if titan:
-                        logits = eng.forward_slide(None, None, genes, self.onehots[a:b], patch_size_lv0=self.patch_size_lv0, **own)
-                    else:
-                        logits = eng.forward(None, None, genes, self.onehots[a:b], geometry=(b - a, L), **own)
+                    logits = eng.forward_slide(None, None, genes, self.onehots[a:b], staged_rows=L, patch_size_lv0=self.patch_size_lv0,
+                                               need_grad=True, clinical=clinical, share=share, tape=pg.tapes[gi], site_group=gi + 1,
+                                               ws_slot=self._group_slots[gi])
                     call = eng.last_call
                     dlogits = torch.empty_like(logits)
                     ops.distill_loss(logits, target[a:b], self._loss_parts[gi], dlogits, b - a, O, 1.0, self.scale)
@@ -355,14 +333,9 @@ class TrainStep:
         target = self.project_text(text)
         if zero:
             eng.store.flat_grad.zero_()
-        if hasattr(eng, "forward_slide"):      # TITAN configuration: gridding + backbone embed first (staged: gridding already done)
-            logits = eng.forward_slide(x, coords, genes, self.onehots, patch_size_lv0=self.patch_size_lv0, need_grad=True,
-                                       clinical=clinical, staged=staged_geometry is not None)
-        elif staged_geometry is None:
-            logits = eng.forward(x, coords, genes, self.onehots, need_grad=True, clinical=clinical)
-        else:
-            logits = eng.forward(None, None, genes, self.onehots, need_grad=True, staged=True, geometry=staged_geometry,
-                                 clinical=clinical)
+        # (TITAN configuration: gridding + backbone embed first; staged: step_graphed has uploaded / gridded the slide)
+        logits = eng.forward_slide(x, coords, genes, self.onehots, staged_rows=None if staged_geometry is None else staged_geometry[1],
+                                   patch_size_lv0=self.patch_size_lv0, need_grad=True, clinical=clinical)
         self.last_logits = logits
         R, O = target.shape
         self.grad_scale.copy_(self.scale)
@@ -497,7 +470,6 @@ class TrainStep:
         first.  With world_size > 1 the capture is cut where a gradient bucket becomes final: the reducer starts that
         bucket's all-reduce between two replays, and the optimiser graph runs after the wait."""
         eng = self.engine
-        titan = hasattr(eng, "forward_slide")
         if not eng._caches_ready:
             eng._build_caches()
         x = x.reshape(-1, x.shape[-1])
@@ -511,16 +483,15 @@ class TrainStep:
             self._stext = torch.empty(tuple(text.shape), dtype=F32, device=self.dev)
             self._sclin = torch.empty(1, eng.cfg.clinfeat_dim, dtype=F32, device=self.dev) if eng.cfg.clinical else None
             self._gcache.clear()
-        if titan:
-            # TITAN configuration: the gridding kernels and the one host read-back (the token count: every shape downstream depends
-            # on it) run eagerly; the captured part starts at the token gather and is keyed on (patches, TOKENS).
-            Lv = eng.stage_slide(x, coords, self.patch_size_lv0)
-            self._group_workspaces(Lv, self._split_now(Lv))      # (may grow the workspace: bumps eng.generation)
-        else:
-            Lv = L
-            split = self._split_now(L)
-            self._group_workspaces(L, split, first=1)     # (all groups' workspaces exist -- and have grown -- before anything is captured)
-            eng.stage_inputs(x, coords, B=self._groups[0][1] - self._groups[0][0] if split else B)      # (may grow the workspace: bumps eng.generation)
+        # All workspaces exist -- and have grown, which bumps eng.generation -- before anything is captured.  The engines differ in when
+        # the row count Lv is known: the patch count, so the other groups' workspaces grow in front of the upload into the first one's;
+        # or (TITAN configuration) the token count that the gridding kernels' one host read-back brings, so every workspace grows behind
+        # it -- gridding and read-back run eagerly, the captured part starts at the token gather and is keyed on (patches, TOKENS).
+        split = self._split_now(L)      # (ROWS_FROM_STAGING: forced or never, whatever the length)
+        if not eng.ROWS_FROM_STAGING:
+            self._group_workspaces(L, split, first=1)
+        Lv = eng.stage_slide(x, coords, self.patch_size_lv0, B=self._groups[0][1] - self._groups[0][0] if split else B)
+        self._group_workspaces(Lv, split)
         if self.auto_split and Lv not in self.split_decisions and B >= 3 and Lv >= 2048 and not self._dp() and self._can_split():
             # this geometry's schedule is still to be decided by a trial (below, on the visit that captures it): the workspaces of BOTH
             # schedules exist and have grown NOW, on an eager visit -- a growth bumps eng.generation and retires every capture

@@ -187,19 +187,25 @@ def test_argument_errors_raise_before_the_library_is_loaded(monkeypatch):
     from modaltune_amd import _lib
     from modaltune_amd.attribution import IntegratedGradients
     from modaltune_amd.engine import Engine, PatchPoints
+    from modaltune_amd.titan import TitanEngine
 
     def no_load():
         raise AssertionError("the library was loaded")
     monkeypatch.setattr(_lib, "load", no_load)
     cfg = _case("L37_d3")[0]
-    fake = types.SimpleNamespace(cfg=cfg, device=torch.device("cpu"))
+
+    def bare(cls, **attrs):      # an engine of class `cls` that was never constructed: the checks below read nothing but these attributes
+        eng = object.__new__(cls)
+        eng.__dict__.update(attrs)
+        return eng
+    fake = bare(Engine, cfg=cfg, device=torch.device("cpu"))
     with pytest.raises(ValueError, match="inputs"):
         IntegratedGradients(fake, (0,), steps=4, inputs="pixels")
-    late = types.SimpleNamespace(cfg=types.SimpleNamespace(first_interaction_layer=2), device=torch.device("cpu"))
+    late = bare(Engine, cfg=types.SimpleNamespace(first_interaction_layer=2), device=torch.device("cpu"))
     with pytest.raises(NotImplementedError, match="first_interaction_layer"):
         IntegratedGradients(late, (0,), steps=4, inputs="patches")
     with pytest.raises(NotImplementedError, match="TITAN"):
-        IntegratedGradients(types.SimpleNamespace(forward_slide=None), inputs="patches")
+        IntegratedGradients(bare(TitanEngine), inputs="patches")
     # the engine's own checks: shape, dtype, device and the modes it cannot serve
     B, L, D = 3, 5, cfg.embed_dim
     ok = lambda: PatchPoints(torch.zeros(L, D), torch.zeros(B), torch.zeros(B), torch.zeros(L), torch.ones(1))
@@ -217,4 +223,4 @@ def test_argument_errors_raise_before_the_library_is_loaded(monkeypatch):
     with pytest.raises(NotImplementedError, match="first_interaction_layer"):
         Engine._check_patch_points(late, ok(), B, L, True)
     with pytest.raises(NotImplementedError, match="TITAN"):
-        Engine._check_patch_points(types.SimpleNamespace(forward_slide=None), ok(), B, L, True)
+        Engine._check_patch_points(bare(TitanEngine), ok(), B, L, True)
