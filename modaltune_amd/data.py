@@ -14,6 +14,7 @@ event.  PyTorch is used for files, pinned memory, streams and events only.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -77,6 +78,25 @@ def load_case_shards(prefixes: Sequence[str], threshold: int = 25000, generator:
     if idx is not None:
         feats, coords = feats[idx, :], coords[idx, :]
     return feats, coords
+
+
+def _slide_rows(path: str) -> int:
+    """Patch count of one stored slide from its header alone: a reference `.pt` file (memory-mapped, the coords' shape) or the prefix
+    of an fp16 shard pair (`convert_to_f16_shard`; the memory-mapped feature array's shape)."""
+    if path.endswith(".pt"):
+        return int(torch.load(path, map_location="cpu", mmap=True)["coords"].shape[0])
+    return int(np.load(path + ".features.f16.npy", mmap_mode="r").shape[0])
+
+
+def case_lengths(paths_per_case: Sequence[Sequence[str]], threshold: int = 25000) -> List[int]:
+    """The patch count every case will have after `load_case` / `load_case_shards`: its slides' rows added up, capped at `threshold`
+    (DS:274-281).  No feature is read -- shapes only --, so a whole cohort costs one file open per slide.  A case is a sequence of `.pt`
+    paths or shard prefixes (or one such string).  A plain list: what `dp.shard_indices(lengths=...)` takes, and the caller may cache."""
+    out = []
+    for paths in paths_per_case:
+        paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+        out.append(min(int(threshold), sum(_slide_rows(os.fspath(p)) for p in paths)))
+    return out
 
 
 class StagedCase:

@@ -114,6 +114,9 @@ class TrainStep:
         # compute stream -- ("grad", e0, e1): last backward kernel -> the optimiser may start (bucket all-reduces / the last bucket's
         # reduce-scatter not hidden under the backward); ("param", e0, e1): the next step's wait for the sharded parameter all-gather
         self.comm_events: Optional[list] = None
+        # Measured rank imbalance (optional): a dp.StepTimer whose start() / stop() bracket every call's forward + backward -- two events
+        # on the compute stream, the second ahead of the reducer wait, never inside a capture; nothing is read back before its report().
+        self.step_timer: Optional["dp.StepTimer"] = None
         # The task passes of a step as TWO concurrent groups (B = 2 and B = 1 on two HIP streams) instead of one batched B = 3 pass
         # (pass_groups.py has the mechanics and the measurements).  The groups share the staged input and the patch embedding (computed
         # once before the fork).  The loss is a sum over the task rows (TM:225-233), so each group runs loss + backward behind its own
@@ -443,7 +446,12 @@ class TrainStep:
         if self.accumulate > 1 and not update:
             raise ValueError("step(update=False) is not defined with accumulate > 1: micro-steps accumulate by themselves")
         first, boundary = self._window_role()
+        timer = self.step_timer
+        if timer is not None:
+            timer.start()
         self._fwd_bwd(x, coords, genes, text, clinical, reduce=update and boundary, zero=first, micro=not boundary)
+        if timer is not None:
+            timer.stop()
         self.eager_steps += 1
         if not boundary:
             self.window_pos += 1
@@ -528,9 +536,14 @@ class TrainStep:
                           micro=not boundary)
 
         next_pos = 0 if boundary else self.window_pos + 1      # (window_pos moves behind the work, as in step(): a call that raises leaves it)
+        timer = self.step_timer
         if ent is None or ent.segs is None:
             if not cache.admit(key):              # eager visits (allocator, lazy kernel attributes, the tape's gradient arena
-                fwd_bwd()                         # sized from the last step)
+                if timer is not None:             # sized from the last step)
+                    timer.start()
+                fwd_bwd()
+                if timer is not None:
+                    timer.stop()
                 self.eager_steps += 1
                 if boundary:
                     self.optimizer_step()
@@ -542,10 +555,14 @@ class TrainStep:
                 ent = _Captured(gen)
                 cache.put(key, ent)               # (evicts BEFORE the capture: it may reuse the evicted graphs' blocks)
             self._capture(ent, fwd_bwd, world, boundary)
+        if timer is not None:
+            timer.start()
         for g, bucket in ent.segs:
             g.replay()
             if bucket is not None:
                 self.reducer.start(bucket)
+        if timer is not None:                     # (world == 1: the captured step holds the optimiser too)
+            timer.stop()
         self.last_logits = ent.logits
         self.graph_replays += 1
         if dp_on and boundary:
@@ -581,6 +598,7 @@ class TrainStep:
         saved = [(t, t.clone()) for t in (eng.store.flat, self.m, self.v, self.step_dev, self.scale, self.tracker, self.found_inf, eng.rng,
                                           self._clip_out)]
         was_auto, self.auto_split = self.auto_split, False
+        timer, self.step_timer = self.step_timer, None      # (the trial's replays are not steps of the epoch)
         k_window = self.accumulate
         if k_window > 1:
             assert self.window_pos == 0
@@ -602,7 +620,7 @@ class TrainStep:
                 res["groups" if split else "batched"] = round(1e3 * (time.perf_counter() - t0) / reps, 3)
                 caps[split] = self._gcache.get(key)
         finally:
-            self.auto_split, self.accumulate, self.window_pos = was_auto, k_window, 0
+            self.auto_split, self.accumulate, self.window_pos, self.step_timer = was_auto, k_window, 0, timer
             if k_window > 1:
                 self._gcache.pop(key)
                 self._gcache.size -= 1
