@@ -28,6 +28,16 @@ struct GeneArgs {
   int G, P;              // P task passes: one forward call of the reference each, so each draws its own masks
 };
 constexpr int GP_MAX = 4;
+// the launch's pass count (1 .. GP_MAX: the entry points check) onto the kernels' template argument
+#define GENE_LAUNCH(kernel, passes, grid, stream, args)                                                    \
+  do {                                                                                                     \
+    switch (passes) {                                                                                      \
+      case 1: hipLaunchKernelGGL(kernel<1>, dim3(grid), dim3(GL), 0, stream, args); break;                 \
+      case 2: hipLaunchKernelGGL(kernel<2>, dim3(grid), dim3(GL), 0, stream, args); break;                 \
+      case 3: hipLaunchKernelGGL(kernel<3>, dim3(grid), dim3(GL), 0, stream, args); break;                 \
+      default: hipLaunchKernelGGL(kernel<4>, dim3(grid), dim3(GL), 0, stream, args); break;                \
+    }                                                                                                      \
+  } while (0)
 
 // AlphaDropout(p): kept values pass, dropped ones become alpha' = -selu_scale * selu_alpha; then the affine (a, b) that
 // restores zero mean / unit variance (torch.nn.functional.alpha_dropout)
@@ -37,25 +47,139 @@ MT_DEVINL AlphaAff alpha_affine(float p) {
   const float a = rsqrtf((1.f - p) * (1.f + p * ALPHA_P * ALPHA_P));
   return AlphaAff{a, -a * ALPHA_P * p};
 }
+// The AlphaDropout of one launch.  Pass p draws its own masks: element index (i P + p) 256 + j of pathway i, unit j, at site `site`
+// after the first ELU and `site + 1` after the second -- an index of the pathway and P, never of the grid.
+struct AlphaDrop {
+  DropArgs d; bool on; AlphaAff af;
+  MT_DEVINL explicit AlphaDrop(const DropArgs& d_) : d(d_), on(d_.active() && d_.p > 0.f), af(alpha_affine(d_.p)) {}
+  MT_DEVINL bool keep(int layer, uint64_t idx) const { return !on || drop_keep1(d, d.site + layer, idx); }
+  MT_DEVINL float apply(bool kept, float v) const { return on ? fmaf(af.a, kept ? v : ALPHA_P, af.b) : v; }
+  MT_DEVINL float grad(bool kept) const { return on ? (kept ? af.a : 0.f) : 1.f; }
+};
 
-// y_p[j] = bias[j] + sum_k W[j][k] x_p[k]  (thread j) for P input vectors at once: W row-major [GL][n] is streamed through
-// LDS ONCE for all passes, x_p in LDS
-template <int P>
-MT_DEVINL void gemv_rows(const float* __restrict__ W, int n, const float (*xs)[GL], float (*Ws)[GC + 1], float (&acc)[P]) {
+// ---- The stages of the pathway networks, each stated ONCE and called by every kernel that runs it.  Every accumulation below has one
+// chain -- bias first, k (or r) ascending, one fmaf per term -- so kernels that share a stage give the same bits: the kernels that share a
+// pathway among workgroups against the workgroup-per-pathway ones (a model does not change with the number of pathways it is grouped
+// into; tests/test_kernels_gpu.py: test_gene_snn_families_same_bits -- one exception, the da1 sum of gene_snn_bwd_split_kernel), and the
+// points forward at alpha = 1 / alpha = 0 against the plain forward.  Every LDS read of the loops is in the 4-byte class (lds_f32,
+// common.h).  The backward functions switch the compiler's fp contraction off: there a `+=` IS an add of rounded terms and every fused
+// multiply-add is written fmaf -- which of the two a sum gets is not left to the optimiser, kernel by kernel.
+
+// acc_v[j] += sum_{k < n} W[j][k] x_v[k] (thread j; the caller seeds acc with the bias) for NX input vectors at once: W, row-major with
+// row stride ld, is streamed through LDS ONCE for all of them in 32-column chunks, x_v in LDS
+template <int NX>
+MT_DEVINL void gemv_rows(const float* __restrict__ W, int ld, int n, const float (*xs)[GL], float (*Ws)[GC + 1], float (&acc)[NX]) {
   const int j = threadIdx.x;
   for (int k0 = 0; k0 < n; k0 += GC) {
     const int kc = min(GC, n - k0);
     __syncthreads();
-    for (int i = j; i < GL * GC; i += GL) {       // 8 rows of 32 columns per pass: 128-B coalesced row segments
-      const int r = i / GC, c = i - r * GC;
-      Ws[r][c] = c < kc ? W[(long)r * n + k0 + c] : 0.f;
+    for (int t = j; t < GL * GC; t += GL) {       // 8 rows of 32 columns per step: 128-B coalesced row segments
+      const int r = t / GC, c = t - r * GC;
+      Ws[r][c] = c < kc ? W[(long)r * ld + k0 + c] : 0.f;
     }
     __syncthreads();
 #pragma unroll 8
     for (int c = 0; c < GC; ++c) {
-      const float w = lds_f32(&Ws[j][c]);      // (every LDS read of the loop in the 4-byte class: lds_f32, common.h)
+      const float w = lds_f32(&Ws[j][c]);
 #pragma unroll
-      for (int p = 0; p < P; ++p) acc[p] = fmaf(w, (k0 + c < n) ? lds_f32(&xs[p][k0 + c]) : 0.f, acc[p]);
+      for (int v = 0; v < NX; ++v) acc[v] = fmaf(w, (k0 + c < n) ? lds_f32(&xs[v][k0 + c]) : 0.f, acc[v]);
+    }
+  }
+}
+
+// First layer: acc_v[j] += sum_k W1[j][k] x_v[k] for NX input vectors of n elements in global memory, a null vector being zeros.  n can
+// exceed the LDS vector: the input is walked in pieces of GL, the rows of W1 restricted to a piece.  Uses xs[0 .. NX).
+template <int NX>
+MT_DEVINL void first_layer(const float* W1, int n, const float* const (&x)[NX], float (*xs)[GL], float (*Ws)[GC + 1], float (&acc)[NX]) {
+  const int j = threadIdx.x;
+  for (int p0 = 0; p0 < n; p0 += GL) {
+    const int pn = min(GL, n - p0);
+    __syncthreads();
+    if (j < pn) {
+#pragma unroll
+      for (int v = 0; v < NX; ++v) xs[v][j] = x[v] ? x[v][p0 + j] : 0.f;
+    }
+    __syncthreads();
+    gemv_rows<NX>(W1 + p0, n, pn, xs, Ws, acc);
+  }
+}
+
+// h1_p[j] = AlphaDropout(ELU(pre1[j])) of every pass into LDS (the first layer is the same in every pass: the input is data)
+template <int P>
+MT_DEVINL void stage_h1(const AlphaDrop& ad, int i, float pre1, float (*xs)[GL]) {
+  const int j = threadIdx.x;
+  const float e1 = elu(pre1);
+#pragma unroll
+  for (int p = 0; p < P; ++p) xs[p][j] = ad.apply(ad.keep(0, ((uint64_t)i * P + p) * GL + j), e1);
+}
+
+// Second-layer epilogue of row `row` of pathway i: a2 saved, z = AlphaDropout(ELU(a2))
+template <int P>
+MT_DEVINL void store_second_layer(const AlphaDrop& ad, int i, int row, const float (&acc2)[P], float* a2, float* z) {
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const long e = ((long)i * P + p) * GL + row;
+    a2[e] = acc2[p];
+    z[e] = ad.apply(ad.keep(1, (uint64_t)e), elu(acc2[p]));
+  }
+}
+
+// Backward prologue (thread j of pathway i): both masks regenerated; da2_p = dz_p * mask2_p * elu'(a2_p) and h1_p into LDS, the first
+// mask's factor into g1; returns db2[j] = sum_p da2_p[j]: the ROUNDED da2_p that went to LDS, p ascending, plain adds
+template <int P>
+MT_DEVINL float bwd_prologue(const GeneArgs& a, const AlphaDrop& ad, int i, float pre1, float (*da2s)[GL], float (*h1s)[GL], float (&g1)[P]) {
+#pragma clang fp contract(off)
+  const int j = threadIdx.x;
+  float db2 = 0.f;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const long e = ((long)i * P + p) * GL + j;
+    const float pre2 = a.a2[e];
+    const bool keep1 = ad.keep(0, (uint64_t)e), keep2 = ad.keep(1, (uint64_t)e);
+    g1[p] = ad.grad(keep1);
+    const float da2 = a.dz[e] * ad.grad(keep2) * elu_grad(pre2);
+    da2s[p][j] = da2;
+    h1s[p][j] = ad.apply(keep1, elu(pre1));
+    db2 += da2;
+  }
+  return db2;
+}
+
+// dW2[r][c] += sum_p da2_p[r] h1_p[c] for rows [row_begin, row_end): one wave per row, 16-byte accesses
+template <int P>
+MT_DEVINL void dw2_rows(float* dW2, int row_begin, int row_end, const float (*da2s)[GL], const float (*h1s)[GL]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r = row_begin + wave; r < row_end; r += 4) {
+    float* dst = dW2 + (long)r * GL + lane * 4;
+    f32x4 v = *reinterpret_cast<const f32x4*>(dst);
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      const float d = lds_f32(&da2s[p][r]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = fmaf(d, lds_f32(&h1s[p][lane * 4 + e]), v[e]);
+    }
+    *reinterpret_cast<f32x4*>(dst) = v;
+  }
+}
+
+// dh1_p[k] = sum_r W2[r][k] da2_p[r] (thread k), r ascending from 0: W2 streamed ONCE for all passes, 32 rows at a time, coalesced
+template <int P>
+MT_DEVINL void w2t_stream(const float* W2, const float (*da2s)[GL], float (*Ws)[GL + 1], float (&dh1)[P]) {
+  const int j = threadIdx.x;
+#pragma unroll
+  for (int p = 0; p < P; ++p) dh1[p] = 0.f;
+  for (int r0 = 0; r0 < GL; r0 += GC) {
+    __syncthreads();
+    for (int t = j; t < GC * GL; t += GL) {
+      const int r = t / GL, c = t - r * GL;
+      Ws[r][c] = W2[(long)(r0 + r) * GL + c];
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int r = 0; r < GC; ++r) {
+      const float w = lds_f32(&Ws[r][j]);
+#pragma unroll
+      for (int p = 0; p < P; ++p) dh1[p] = fmaf(w, lds_f32(&da2s[p][r0 + r]), dh1[p]);
     }
   }
 }
@@ -67,120 +191,49 @@ __global__ __launch_bounds__(GL) void gene_snn_fwd_kernel(GeneArgs a) {
   const int i = blockIdx.x, j = threadIdx.x;
   const int n = a.sizes[i];
   const long* o = a.offs + 4L * i;
-  const float* g = a.genes + a.goff[i];
-  float acc = a.params[o[1] + j];
-  // first layer (the same in every pass: the input is data): n can exceed the LDS vector; walk it in pieces of GL
-  for (int p0 = 0; p0 < n; p0 += GL) {
-    const int pn = min(GL, n - p0);
-    __syncthreads();
-    if (j < pn) xs[0][j] = g[p0 + j];
-    __syncthreads();
-    // rows of W1 restricted to columns [p0, p0 + pn): row stride n
-    for (int k0 = 0; k0 < pn; k0 += GC) {
-      const int kc = min(GC, pn - k0);
-      __syncthreads();
-      for (int t = j; t < GL * GC; t += GL) {
-        const int r = t / GC, c = t - r * GC;
-        Ws[r][c] = c < kc ? a.params[o[0] + (long)r * n + p0 + k0 + c] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 8
-      for (int c = 0; c < GC; ++c) acc = fmaf(lds_f32(&Ws[j][c]), (k0 + c < pn) ? lds_f32(&xs[0][k0 + c]) : 0.f, acc);
-    }
-  }
-  a.a1[(long)i * GL + j] = acc;
+  const AlphaDrop ad(a.adrop);
+  const float* const x[1] = {a.genes + a.goff[i]};
+  float acc[1] = {a.params[o[1] + j]};
+  first_layer<1>(a.params + o[0], n, x, xs, Ws, acc);
+  a.a1[(long)i * GL + j] = acc[0];
   __syncthreads();
-  const bool ad = a.adrop.active() && a.adrop.p > 0.f;
-  const AlphaAff af = alpha_affine(a.adrop.p);
-  const float e1 = elu(acc);
+  stage_h1<P>(ad, i, acc[0], xs);
   float acc2[P];
 #pragma unroll
-  for (int p = 0; p < P; ++p) {         // pass p draws its own masks: element index (i P + p) 256 + j
-    float h1 = e1;
-    if (ad) h1 = fmaf(af.a, drop_keep1(a.adrop, a.adrop.site, ((uint64_t)i * P + p) * GL + j) ? h1 : ALPHA_P, af.b);
-    xs[p][j] = h1;
-    acc2[p] = a.params[o[3] + j];
-  }
-  gemv_rows<P>(a.params + o[2], GL, xs, Ws, acc2);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const long e = ((long)i * P + p) * GL + j;
-    a.a2[e] = acc2[p];
-    float zz = elu(acc2[p]);
-    if (ad) zz = fmaf(af.a, drop_keep1(a.adrop, a.adrop.site + 1, (uint64_t)e) ? zz : ALPHA_P, af.b);
-    a.z[e] = zz;
-  }
+  for (int p = 0; p < P; ++p) acc2[p] = a.params[o[3] + j];
+  gemv_rows<P>(a.params + o[2], GL, GL, xs, Ws, acc2);
+  store_second_layer<P>(ad, i, j, acc2, a.a2, a.z);
 }
 
 template <int P>
 __global__ __launch_bounds__(GL) void gene_snn_bwd_kernel(GeneArgs a) {
+#pragma clang fp contract(off)
   __shared__ float Ws[GC][GL + 1];   // 32 rows x 256 columns of W2
   __shared__ float da2s[P][GL], h1s[P][GL], da1s[GL];
-  const int i = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int i = blockIdx.x, j = threadIdx.x;
   const int n = a.sizes[i];
   const long* o = a.offs + 4L * i;
   const float pre1 = a.a1[(long)i * GL + j];
-  const bool ad = a.adrop.active() && a.adrop.p > 0.f;
-  const AlphaAff af = alpha_affine(a.adrop.p);
-  float g1[P], db2 = 0.f;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const long e = ((long)i * P + p) * GL + j;
-    const float pre2 = a.a2[e];
-    const bool keep1 = !ad || drop_keep1(a.adrop, a.adrop.site, (uint64_t)e);
-    const bool keep2 = !ad || drop_keep1(a.adrop, a.adrop.site + 1, (uint64_t)e);
-    const float g2 = ad ? (keep2 ? af.a : 0.f) : 1.f;
-    g1[p] = ad ? (keep1 ? af.a : 0.f) : 1.f;
-    const float da2 = a.dz[e] * g2 * elu_grad(pre2);
-    da2s[p][j] = da2;
-    h1s[p][j] = ad ? fmaf(af.a, keep1 ? elu(pre1) : ALPHA_P, af.b) : elu(pre1);
-    db2 += da2;
-  }
+  const AlphaDrop ad(a.adrop);
+  float g1[P], dh1[P];
+  const float db2 = bwd_prologue<P>(a, ad, i, pre1, da2s, h1s, g1);
   a.grads[o[3] + j] += db2;
   __syncthreads();
-  // dW2[r][c] += sum_p da2_p[r] h1_p[c]: one wave per row, 16-byte accesses
-  for (int r = wave; r < GL; r += 4) {
-    float* dst = a.grads + o[2] + (long)r * GL + lane * 4;
-    f32x4 v = *reinterpret_cast<const f32x4*>(dst);
+  dw2_rows<P>(a.grads + o[2], 0, GL, da2s, h1s);
+  w2t_stream<P>(a.params + o[2], da2s, Ws, dh1);
+  // the first layer's input is the same in every pass: da1 = (sum_p dh1_p * mask_p) * elu'(pre1), the sum over rounded products
+  float s1 = 0.f;
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const float d = lds_f32(&da2s[p][r]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaf(d, lds_f32(&h1s[p][lane * 4 + e]), v[e]);
-    }
-    *reinterpret_cast<f32x4*>(dst) = v;
-  }
-  // dh1_p[k] = sum_r W2[r][k] da2_p[r] (thread k): W2 streamed ONCE, 32 rows at a time, coalesced
-  float dh1[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) dh1[p] = 0.f;
-  for (int r0 = 0; r0 < GL; r0 += GC) {
-    __syncthreads();
-    for (int t = j; t < GC * GL; t += GL) {
-      const int r = t / GL, c = t - r * GL;
-      Ws[r][c] = a.params[o[2] + (long)(r0 + r) * GL + c];
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < GC; ++r) {
-      const float w = lds_f32(&Ws[r][j]);
-#pragma unroll
-      for (int p = 0; p < P; ++p) dh1[p] = fmaf(w, lds_f32(&da2s[p][r0 + r]), dh1[p]);
-    }
-  }
-  // the first layer's input is the same in every pass: da1 = sum_p dh1_p * mask_p * elu'(pre1)
-  float da1 = 0.f;
-#pragma unroll
-  for (int p = 0; p < P; ++p) da1 += dh1[p] * g1[p];
-  da1 *= elu_grad(pre1);
-  a.grads[o[1] + j] += da1;
-  da1s[j] = da1;
+  for (int p = 0; p < P; ++p) s1 += dh1[p] * g1[p];
+  const float eg1 = elu_grad(pre1);
+  a.grads[o[1] + j] = fmaf(eg1, s1, a.grads[o[1] + j]);
+  da1s[j] = eg1 * s1;
   __syncthreads();
   // dW1[r][k] += da1[r] g[k]: rows of n floats (4-byte accesses: the slots are only 4-byte aligned inside a row)
   const float* g = a.genes + a.goff[i];
   for (long t = j; t < (long)GL * n; t += GL) {
     const int r = (int)(t / n), k = (int)(t - (long)r * n);
-    a.grads[o[0] + t] += lds_f32(&da1s[r]) * g[k];
+    a.grads[o[0] + t] = fmaf(lds_f32(&da1s[r]), g[k], a.grads[o[0] + t]);
   }
 }
 
@@ -197,40 +250,16 @@ __global__ __launch_bounds__(GL) void gene_snn_fwd_split_kernel(GeneArgs a) {
   const int i = blockIdx.x / GS, sp = blockIdx.x % GS, j = threadIdx.x;
   const int n = a.sizes[i];
   const long* o = a.offs + 4L * i;
-  const float* g = a.genes + a.goff[i];
-  float acc = a.params[o[1] + j];
-  for (int p0 = 0; p0 < n; p0 += GL) {        // first layer, as gene_snn_fwd_kernel
-    const int pn = min(GL, n - p0);
-    __syncthreads();
-    if (j < pn) xs[0][j] = g[p0 + j];
-    __syncthreads();
-    for (int k0 = 0; k0 < pn; k0 += GC) {
-      const int kc = min(GC, pn - k0);
-      __syncthreads();
-      for (int t = j; t < GL * GC; t += GL) {
-        const int r = t / GC, c = t - r * GC;
-        Ws[r][c] = c < kc ? a.params[o[0] + (long)r * n + p0 + k0 + c] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 8
-      for (int c = 0; c < GC; ++c) acc = fmaf(lds_f32(&Ws[j][c]), (k0 + c < pn) ? lds_f32(&xs[0][k0 + c]) : 0.f, acc);
-    }
-  }
-  if (sp == 0) a.a1[(long)i * GL + j] = acc;
+  const AlphaDrop ad(a.adrop);
+  const float* const x[1] = {a.genes + a.goff[i]};
+  float acc[1] = {a.params[o[1] + j]};
+  first_layer<1>(a.params + o[0], n, x, xs, Ws, acc);
+  if (sp == 0) a.a1[(long)i * GL + j] = acc[0];
   __syncthreads();
-  const bool ad = a.adrop.active() && a.adrop.p > 0.f;
-  const AlphaAff af = alpha_affine(a.adrop.p);
-  const float e1 = elu(acc);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    float h1 = e1;
-    if (ad) h1 = fmaf(af.a, drop_keep1(a.adrop, a.adrop.site, ((uint64_t)i * P + p) * GL + j) ? h1 : ALPHA_P, af.b);
-    xs[p][j] = h1;
-  }
+  stage_h1<P>(ad, i, acc[0], xs);
   __syncthreads();
   // second layer, rows [GR sp, GR sp + GR): the rows are staged in LDS by all threads (8 per row: a wave reads 8 rows x 1 KB,
-  // contiguous), then ONE thread per row runs the k = 0 .. 255 chain in the order of gene_snn_fwd_kernel (bias first, k ascending):
-  // the two kernels give the same bits, so a model does not change with the number of pathways it is grouped into
+  // contiguous), then ONE thread per row runs the chain of gemv_rows (bias first, k = 0 .. 255 ascending): the same bits
   float (*Wl)[GL + 1] = reinterpret_cast<float (*)[GL + 1]>(&Ws[0][0]);      // [GR][GL + 1] in the chunk buffer (8 224 of its 8 448 floats)
   {
     const int r = j >> 3, part = j & 7;
@@ -254,55 +283,26 @@ __global__ __launch_bounds__(GL) void gene_snn_fwd_split_kernel(GeneArgs a) {
 #pragma unroll
       for (int p = 0; p < P; ++p) a2[p] = fmaf(w, lds_f32(&xs[p][k]), a2[p]);
     }
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const long e = ((long)i * P + p) * GL + r;
-      a.a2[e] = a2[p];
-      float zz = elu(a2[p]);
-      if (ad) zz = fmaf(af.a, drop_keep1(a.adrop, a.adrop.site + 1, (uint64_t)e) ? zz : ALPHA_P, af.b);
-      a.z[e] = zz;
-    }
+    store_second_layer<P>(ad, i, r, a2, a.a2, a.z);
   }
 }
 
 template <int P>
 __global__ __launch_bounds__(GL) void gene_snn_bwd_split_kernel(GeneArgs a) {
+#pragma clang fp contract(off)
   __shared__ float da2s[P][GL], h1s[P][GL], Wc[GL][GR + 1], da1s[GR];
-  const int i = blockIdx.x / GS, sp = blockIdx.x % GS, j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int i = blockIdx.x / GS, sp = blockIdx.x % GS, j = threadIdx.x;
   const int n = a.sizes[i];
   const long* o = a.offs + 4L * i;
   const float pre1 = a.a1[(long)i * GL + j];
-  const bool ad = a.adrop.active() && a.adrop.p > 0.f;
-  const AlphaAff af = alpha_affine(a.adrop.p);
-  float db2 = 0.f;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const long e = ((long)i * P + p) * GL + j;
-    const float pre2 = a.a2[e];
-    const bool keep1 = !ad || drop_keep1(a.adrop, a.adrop.site, (uint64_t)e);
-    const bool keep2 = !ad || drop_keep1(a.adrop, a.adrop.site + 1, (uint64_t)e);
-    const float g2 = ad ? (keep2 ? af.a : 0.f) : 1.f;
-    const float da2 = a.dz[e] * g2 * elu_grad(pre2);
-    da2s[p][j] = da2;
-    h1s[p][j] = ad ? fmaf(af.a, keep1 ? elu(pre1) : ALPHA_P, af.b) : elu(pre1);
-    db2 += da2;
-  }
+  const AlphaDrop ad(a.adrop);
+  float g1[P];      // (unit j's, unused: the columns of this workgroup draw theirs below)
+  const float db2 = bwd_prologue<P>(a, ad, i, pre1, da2s, h1s, g1);
   if (j / GR == sp) a.grads[o[3] + j] += db2;
   __syncthreads();
-  // dW2 rows [GR sp, GR sp + GR): one wave per row, 16-byte accesses
-  for (int r = GR * sp + wave; r < GR * sp + GR; r += 4) {
-    float* dst = a.grads + o[2] + (long)r * GL + lane * 4;
-    f32x4 v = *reinterpret_cast<const f32x4*>(dst);
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const float d = lds_f32(&da2s[p][r]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaf(d, lds_f32(&h1s[p][lane * 4 + e]), v[e]);
-    }
-    *reinterpret_cast<f32x4*>(dst) = v;
-  }
+  dw2_rows<P>(a.grads + o[2], GR * sp, GR * sp + GR, da2s, h1s);
   // dh1_p[k] = sum_r W2[r][k] da2_p[r] for the columns k in [GR sp, GR sp + GR): the 256 x GR block of W2 is staged in LDS (each
-  // row's 128 bytes by 8 threads), then one thread per column runs r = 0 .. 255 in the order of gene_snn_bwd_kernel (same bits)
+  // row's 128 bytes by 8 threads), then one thread per column runs the chain of w2t_stream (r = 0 .. 255 ascending): the same bits
   {
     const int part = j & 7;
     for (int r = j >> 3; r < GL; r += GL / 8) {
@@ -323,23 +323,22 @@ __global__ __launch_bounds__(GL) void gene_snn_bwd_split_kernel(GeneArgs a) {
 #pragma unroll
       for (int p = 0; p < P; ++p) dh1[p] = fmaf(w, lds_f32(&da2s[p][r]), dh1[p]);
     }
-    const float prek = a.a1[(long)i * GL + k];
-    float da1 = 0.f;
+    // da1 as in gene_snn_bwd_kernel, but the sum over the passes is ONE fmaf chain here: under AlphaDropout (mask factors other than 1)
+    // db1 and dW1 of the two kernels differ in the last bits; every other tensor, and these two without dropout, have the same bits
+    float s1 = 0.f;
 #pragma unroll
-    for (int p = 0; p < P; ++p) {
-      const bool keep1 = !ad || drop_keep1(a.adrop, a.adrop.site, (uint64_t)(((long)i * P + p) * GL + k));
-      da1 += dh1[p] * (ad ? (keep1 ? af.a : 0.f) : 1.f);
-    }
-    da1 *= elu_grad(prek);
-    a.grads[o[1] + k] += da1;
-    da1s[j] = da1;
+    for (int p = 0; p < P; ++p) s1 = fmaf(dh1[p], ad.grad(ad.keep(0, (uint64_t)(((long)i * P + p) * GL + k))), s1);
+    const float eg1 = elu_grad(a.a1[(long)i * GL + k]);
+    a.grads[o[1] + k] = fmaf(eg1, s1, a.grads[o[1] + k]);
+    da1s[j] = eg1 * s1;
   }
   __syncthreads();
   // dW1 rows [GR sp, GR sp + GR): dW1[r][c] += da1[r] g[c]
   const float* g = a.genes + a.goff[i];
   for (long t = j; t < (long)GR * n; t += GL) {
     const int r = (int)(t / n), c = (int)(t - (long)r * n);
-    a.grads[o[0] + ((long)GR * sp + r) * n + c] += lds_f32(&da1s[r]) * g[c];
+    float* dst = a.grads + o[0] + ((long)GR * sp + r) * n + c;
+    *dst = fmaf(lds_f32(&da1s[r]), g[c], *dst);
   }
 }
 
@@ -358,22 +357,8 @@ extern "C" int mt_gene_snn_fwd(const float* params, const long* offs, const int*
   if (latent != GL || passes > GP_MAX) return MT_ERR_UNSUPPORTED;
   GeneArgs a{params, nullptr, offs, sizes, goff, genes, a1, a2, z, nullptr, make_drop(alpha_drop), G, passes};
   hipStream_t s = (hipStream_t)stream;
-  if (G < GENE_SPLIT_BELOW) {
-    switch (passes) {
-      case 1: hipLaunchKernelGGL(gene_snn_fwd_split_kernel<1>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      case 2: hipLaunchKernelGGL(gene_snn_fwd_split_kernel<2>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      case 3: hipLaunchKernelGGL(gene_snn_fwd_split_kernel<3>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      default: hipLaunchKernelGGL(gene_snn_fwd_split_kernel<4>, dim3(G * GS), dim3(GL), 0, s, a); break;
-    }
-    MT_CHECK_LAUNCH();
-    return MT_OK;
-  }
-  switch (passes) {
-    case 1: hipLaunchKernelGGL(gene_snn_fwd_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(gene_snn_fwd_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(gene_snn_fwd_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
-    default: hipLaunchKernelGGL(gene_snn_fwd_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
-  }
+  if (G < GENE_SPLIT_BELOW) GENE_LAUNCH(gene_snn_fwd_split_kernel, passes, G * GS, s, a);
+  else GENE_LAUNCH(gene_snn_fwd_kernel, passes, G, s, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
@@ -386,22 +371,8 @@ extern "C" int mt_gene_snn_bwd(const float* params, float* grads, const long* of
   GeneArgs a{params, grads, offs, sizes, goff, genes, const_cast<float*>(a1), const_cast<float*>(a2), nullptr, dz,
              make_drop(alpha_drop), G, passes};
   hipStream_t s = (hipStream_t)stream;
-  if (G < GENE_SPLIT_BELOW) {
-    switch (passes) {
-      case 1: hipLaunchKernelGGL(gene_snn_bwd_split_kernel<1>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      case 2: hipLaunchKernelGGL(gene_snn_bwd_split_kernel<2>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      case 3: hipLaunchKernelGGL(gene_snn_bwd_split_kernel<3>, dim3(G * GS), dim3(GL), 0, s, a); break;
-      default: hipLaunchKernelGGL(gene_snn_bwd_split_kernel<4>, dim3(G * GS), dim3(GL), 0, s, a); break;
-    }
-    MT_CHECK_LAUNCH();
-    return MT_OK;
-  }
-  switch (passes) {
-    case 1: hipLaunchKernelGGL(gene_snn_bwd_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(gene_snn_bwd_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(gene_snn_bwd_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
-    default: hipLaunchKernelGGL(gene_snn_bwd_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
-  }
+  if (G < GENE_SPLIT_BELOW) GENE_LAUNCH(gene_snn_bwd_split_kernel, passes, G * GS, s, a);
+  else GENE_LAUNCH(gene_snn_bwd_kernel, passes, G, s, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
@@ -432,57 +403,29 @@ __global__ __launch_bounds__(GL) void gene_snn_fwd_points_kernel(GenePointArgs a
   const int i = blockIdx.x, j = threadIdx.x;
   const int n = a.sizes[i];
   const long* o = a.offs + 4L * i;
-  const float* g = a.genes + a.goff[i];
-  const float* bl = a.baseline ? a.baseline + a.goff[i] : nullptr;
-  // The first layer is affine in alpha: b1 + W1 genes and b1 + W1 baseline are formed ONCE (each in the summation order of
-  // gene_snn_fwd_kernel: bias first, k ascending -- alpha = 1 / alpha = 0 reproduce its bits) and combined per point below
-  float accg = a.params[o[1] + j], accb = accg;
-  for (int p0 = 0; p0 < n; p0 += GL) {
-    const int pn = min(GL, n - p0);
-    __syncthreads();
-    if (j < pn) {
-      xs[0][j] = g[p0 + j];
-      xs[1][j] = bl ? bl[p0 + j] : 0.f;
-    }
-    __syncthreads();
-    for (int k0 = 0; k0 < pn; k0 += GC) {
-      const int kc = min(GC, pn - k0);
-      __syncthreads();
-      for (int t = j; t < GL * GC; t += GL) {
-        const int r = t / GC, c = t - r * GC;
-        Ws[r][c] = c < kc ? a.params[o[0] + (long)r * n + p0 + k0 + c] : 0.f;
-      }
-      __syncthreads();
-#pragma unroll 8
-      for (int c = 0; c < GC; ++c) {
-        const float w = lds_f32(&Ws[j][c]);
-        const bool in = k0 + c < pn;
-        accg = fmaf(w, in ? lds_f32(&xs[0][k0 + c]) : 0.f, accg);
-        accb = fmaf(w, in ? lds_f32(&xs[1][k0 + c]) : 0.f, accb);
-      }
-    }
-  }
+  // The first layer is affine in alpha: b1 + W1 genes and b1 + W1 baseline are formed ONCE (each by the chain of first_layer, so
+  // alpha = 1 / alpha = 0 reproduce the bits of gene_snn_fwd_kernel) and combined per point below
+  const float* const x[2] = {a.genes + a.goff[i], a.baseline ? a.baseline + a.goff[i] : nullptr};
+  const float b1 = a.params[o[1] + j];
+  float acc[2] = {b1, b1};
+  first_layer<2>(a.params + o[0], n, x, xs, Ws, acc);
   __syncthreads();
   float acc2[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const float al = a.alphas[p];
-    const float pre1 = fmaf(al, accg, (1.f - al) * accb);      // exact at alpha = 0 and alpha = 1
+    const float pre1 = fmaf(al, acc[0], (1.f - al) * acc[1]);      // exact at alpha = 0 and alpha = 1
     a.a1[((long)i * P + p) * GL + j] = pre1;
     xs[p][j] = elu(pre1);
     acc2[p] = a.params[o[3] + j];
   }
-  gemv_rows<P>(a.params + o[2], GL, xs, Ws, acc2);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const long e = ((long)i * P + p) * GL + j;
-    a.a2[e] = acc2[p];
-    a.z[e] = elu(acc2[p]);
-  }
+  gemv_rows<P>(a.params + o[2], GL, GL, xs, Ws, acc2);
+  store_second_layer<P>(AlphaDrop(DropArgs{}), i, j, acc2, a.a2, a.z);      // (no dropout on the path)
 }
 
 template <int P>
 __global__ __launch_bounds__(GL) void gene_snn_bwd_input_kernel(GenePointArgs a) {
+#pragma clang fp contract(off)
   __shared__ float Ws[GC][GL + 1];   // 32 rows x 256 columns of W2
   __shared__ float da2s[P][GL], ss[GL];
   const int i = blockIdx.x, j = threadIdx.x;
@@ -493,24 +436,8 @@ __global__ __launch_bounds__(GL) void gene_snn_bwd_input_kernel(GenePointArgs a)
     const long e = ((long)i * P + p) * GL + j;
     da2s[p][j] = a.dz[e] * elu_grad(a.a2[e]);
   }
-  // dh1_p[k] = sum_r W2[r][k] da2_p[r] (thread k): W2 streamed ONCE for all points, 32 rows at a time, coalesced
   float dh1[P];
-#pragma unroll
-  for (int p = 0; p < P; ++p) dh1[p] = 0.f;
-  for (int r0 = 0; r0 < GL; r0 += GC) {
-    __syncthreads();
-    for (int t = j; t < GC * GL; t += GL) {
-      const int r = t / GL, c = t - r * GL;
-      Ws[r][c] = a.params[o[2] + (long)(r0 + r) * GL + c];
-    }
-    __syncthreads();
-#pragma unroll 8
-    for (int r = 0; r < GC; ++r) {
-      const float w = lds_f32(&Ws[r][j]);
-#pragma unroll
-      for (int p = 0; p < P; ++p) dh1[p] = fmaf(w, lds_f32(&da2s[p][r0 + r]), dh1[p]);
-    }
-  }
+  w2t_stream<P>(a.params + o[2], da2s, Ws, dh1);
   // s[k] = sum_p w_p da1_p[k], p ascending: the input gradient is linear in da1, so the quadrature sum is taken before W1^T
   float s = 0.f;
 #pragma unroll
@@ -566,12 +493,7 @@ extern "C" int mt_gene_snn_fwd_points(const float* params, const long* offs, con
   if (latent != GL || points > GP_MAX) return MT_ERR_UNSUPPORTED;
   GenePointArgs a{params, offs, sizes, goff, genes, baseline, alphas, nullptr, nullptr, a1, a2, z, nullptr, nullptr, G, 0};
   hipStream_t s = (hipStream_t)stream;
-  switch (points) {
-    case 1: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
-    default: hipLaunchKernelGGL(gene_snn_fwd_points_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
-  }
+  GENE_LAUNCH(gene_snn_fwd_points_kernel, points, G, s, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
@@ -584,12 +506,7 @@ extern "C" int mt_gene_snn_bwd_input(const float* params, const long* offs, cons
   GenePointArgs a{params, offs, sizes, goff, nullptr, nullptr, nullptr, weights, unscale, const_cast<float*>(a1), const_cast<float*>(a2),
                   nullptr, dz, dgenes, G, accumulate != 0};
   hipStream_t s = (hipStream_t)stream;
-  switch (points) {
-    case 1: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<1>, dim3(G), dim3(GL), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<2>, dim3(G), dim3(GL), 0, s, a); break;
-    case 3: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<3>, dim3(G), dim3(GL), 0, s, a); break;
-    default: hipLaunchKernelGGL(gene_snn_bwd_input_kernel<4>, dim3(G), dim3(GL), 0, s, a); break;
-  }
+  GENE_LAUNCH(gene_snn_bwd_input_kernel, points, G, s, a);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }

@@ -1,6 +1,7 @@
 """GPU parity tests of the individual C-ABI kernels against fp64 torch-CPU restatements / the oracle.
 Run on the MI355X box:  python -m pytest tests -m gpu -x -q
 """
+import functools
 import math
 import os
 
@@ -1062,30 +1063,34 @@ def test_elementwise(ops):
 
 
 # ------------------------------------------------------------------------------------------ grouped pathway networks
+def _pack_pathways(W1, b1, W2, b2):
+    """The flat parameter buffer of the pathway networks: per pathway its W1, b1, W2, b2, every slot padded to a multiple of 4
+    elements (the 16-byte accesses of the dW2 rows).  Returns (flat, offs) with offs[i] = the four element offsets of pathway i."""
+    pieces, offs, cur = [], [], 0
+    for slots in zip(W1, b1, W2, b2):
+        row = []
+        for t in slots:
+            row.append(cur)
+            pieces.append(t.reshape(-1))
+            pad = (-t.numel()) % 4
+            if pad:
+                pieces.append(torch.zeros(pad))
+            cur += t.numel() + pad
+        offs.append(row)
+    return torch.cat(pieces), offs
+
+
 @pytest.mark.parametrize("sizes", [[1, 5, 199, 33, 64, 300, 7], [9] * 40, [5] * 70 + [130, 1]])
 def test_gene_snn_grouped(ops, sizes):
     """All pathway networks in one launch vs per-pathway torch (gene_encoder.py:97-131): forward and weight grads.
     Fewer than 64 pathways run the kernels that share a pathway among 8 workgroups, more the workgroup-per-pathway ones."""
     g = rng(len(sizes))
     G, Lt = len(sizes), 256
-    offs, pieces, cur = [], [], 0
-
-    def slot(t):
-        nonlocal cur
-        o = cur
-        pieces.append(t.reshape(-1))
-        pad = (-t.numel()) % 4
-        if pad:
-            pieces.append(torch.zeros(pad))
-        cur += t.numel() + pad
-        return o
     W1 = [torch.randn(Lt, n, generator=g) * 0.3 for n in sizes]
     b1 = [torch.randn(Lt, generator=g) * 0.1 for _ in sizes]
     W2 = [torch.randn(Lt, Lt, generator=g) * 0.06 for _ in sizes]
     b2 = [torch.randn(Lt, generator=g) * 0.1 for _ in sizes]
-    for i in range(G):
-        offs.append([slot(W1[i]), slot(b1[i]), slot(W2[i]), slot(b2[i])])
-    flat = torch.cat(pieces)
+    flat, offs = _pack_pathways(W1, b1, W2, b2)
     genes = [torch.randn(n, generator=g) for n in sizes]
     dz = torch.randn(G, Lt, generator=g)
     goff = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
@@ -1114,6 +1119,64 @@ def test_gene_snn_grouped(ops, sizes):
         for j, t in enumerate(params[i]):
             got = gc[offs[i][j]:offs[i][j] + t.numel()].view(t.shape)
             assert rel(got, t.grad) < 1e-5, (i, j)
+
+
+_FAMILY_SIZES = [1, 31, 32, 33, 199, 256, 257, 300] + [5] * 64      # the edges of the 32-column chunk and of the 256-wide LDS vector, two pieces
+
+
+@functools.lru_cache(maxsize=None)
+def _family_inputs():
+    g = rng(72)
+    Lt, sizes = 256, _FAMILY_SIZES
+    W1 = [torch.randn(Lt, n, generator=g) * 0.3 for n in sizes]
+    b1 = [torch.randn(Lt, generator=g) * 0.1 for _ in sizes]
+    W2 = [torch.randn(Lt, Lt, generator=g) * 0.06 for _ in sizes]
+    b2 = [torch.randn(Lt, generator=g) * 0.1 for _ in sizes]
+    flat, offs = _pack_pathways(W1, b1, W2, b2)
+    genes = torch.randn(sum(sizes), generator=g)
+    dz = torch.randn(len(sizes), 4, Lt, generator=g)
+    goff = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64))
+    return (flat.to(DEV), offs, torch.tensor(offs, dtype=torch.int64, device=DEV), torch.tensor(sizes, dtype=torch.int32, device=DEV),
+            goff.to(DEV), genes.to(DEV), dz.to(DEV))
+
+
+@pytest.mark.parametrize("p_drop", [0.0, 0.25])
+@pytest.mark.parametrize("passes", [1, 3, 4])
+def test_gene_snn_families_same_bits(ops, passes, p_drop):
+    """The kernels that share a pathway among 8 workgroups (G < 64) and the workgroup-per-pathway ones give the SAME BITS: pathways
+    0..7 of a 72-pathway launch against a launch of those 8 alone, same flat parameters and genes -- forward outputs, saved
+    pre-activations and every gradient slot.  (The AlphaDropout mask index is of the pathway and P, not of G: both draw the same masks.)
+    One exception, as old as the shared-pathway kernels: with more than one pass UNDER AlphaDropout the two families sum
+    da1 = sum_p dh1_p * mask_p differently (rounded products against one fmaf chain), so dW1 and db1 agree to the last bits only
+    (measured: at most 9.5e-7 absolute on values of order 1); they are compared bit for bit without dropout, where the factors are 1."""
+    flat, offs, t_offs, t_sizes, goff, genes, dz_all = _family_inputs()
+    Lt, sub = 256, 8
+    rs = torch.tensor([9, 8, 3, 0], dtype=torch.int32, device=DEV)      # (the spec holds its address: it stays alive for the launches)
+    spec = ops.dropout_spec(rs, 300, p_drop) if p_drop else None
+    dz = dz_all[:, :passes].contiguous()
+    got = []
+    for G in (len(_FAMILY_SIZES), sub):
+        a1, a2, z = torch.zeros(G, Lt, device=DEV), torch.zeros(G, passes, Lt, device=DEV), torch.zeros(G, passes, Lt, device=DEV)
+        grads = torch.zeros_like(flat)
+        ops.gene_snn_fwd(flat, t_offs[:G], t_sizes[:G], goff[:G], genes, G, Lt, a1, a2, z, alpha_drop=spec, passes=passes)
+        ops.gene_snn_bwd(flat, grads, t_offs[:G], t_sizes[:G], goff[:G], genes, G, Lt, a1, a2, dz[:G].contiguous(), alpha_drop=spec,
+                         passes=passes)
+        torch.cuda.synchronize()
+        out = {"z": z[:sub], "a1": a1[:sub], "a2": a2[:sub]}
+        for i in range(sub):
+            for s, name in enumerate(("dW1", "db1", "dW2", "db2")):
+                end = offs[i][s + 1] if s < 3 else (offs[i + 1][0] if i + 1 < len(offs) else flat.numel())
+                out[f"{name}[{i}]"] = grads[offs[i][s]:end]
+        got.append(out)
+    assert float(got[0]["z"].abs().max()) > 0 and float(got[0]["dW1[7]"].abs().max()) > 0
+    differ = [k for k in got[0] if not torch.equal(got[0][k], got[1][k])]
+    for k in differ:
+        print(k, "max |difference|", float((got[0][k] - got[1][k]).abs().max()))
+    if p_drop and passes > 1:
+        for k in [k for k in differ if k.startswith(("dW1", "db1"))]:
+            differ.remove(k)
+            assert rel(got[0][k], got[1][k]) < 1e-5, k      # (the bar of each family against torch)
+    assert not differ
 
 
 def test_gene_encoder_331_pathways_vs_reference_golden(ops, golden_dir):
@@ -1234,18 +1297,8 @@ def test_gene_snn_alpha_dropout(ops, G):
     b1 = torch.randn(G, Lt, generator=gen) * 0.1
     W2 = torch.randn(G, Lt, Lt, generator=gen) * 0.06
     b2 = torch.randn(G, Lt, generator=gen) * 0.1
-    pieces, offs, cur = [], [], 0
-    for i in range(G):
-        row = []
-        for tns in (W1[i], b1[i], W2[i], b2[i]):
-            row.append(cur)
-            pieces.append(tns.reshape(-1))
-            pad = (-tns.numel()) % 4
-            if pad:
-                pieces.append(torch.zeros(pad))
-            cur += tns.numel() + pad
-        offs.append(row)
-    flat = torch.cat(pieces).to(DEV)
+    flat, offs = _pack_pathways(W1, b1, W2, b2)
+    flat = flat.to(DEV)
     genes = torch.randn(G * n, generator=gen).to(DEV)
     goff = torch.arange(G, dtype=torch.int64, device=DEV) * n
     t_offs = torch.tensor(offs, dtype=torch.int64, device=DEV)
