@@ -4,6 +4,9 @@
 //   token   : T x T self-attention among the modal tokens                               (AM:87)
 // These are tiny-FLOP, HBM/latency-bound ops; they run on the VALU in fp32 with the small operand (the token
 // side) resident in LDS, one streaming pass over the patch-side operand.
+#include <cstddef>
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -50,16 +53,112 @@ MT_DEVINL h16 scaled_h16(float x) {
   (void)NC; (void)NA; (void)NG; (void)KP; (void)TPV; (void)ASCALE;                                                       \
   const int AH = HC ? HC : heads, AE = AH * AD
 
-MT_DEVINL void load16(const h16* p, float* out) {
-  const h16x8 a = ldg8(p), b = ldg8(p + 8);
+// ---------------------------------------------------------------- shared stages ------------------
+// The MFMA kernels below (injector, extractor, maps) are sequences of these stages; each states its register layout here, once.
+// Every function that reads LDS reads ONE banking class (common.h): 16-byte rows, or 8-byte halves of a transposed image.
+//
+// Lane coordinates of a 256-thread workgroup: four waves; hh = the lane's 32-lane half, l31 = its row (A operand) / column (B operand
+// and accumulator) of a 32 x 32 tile; drow = the row of a [HD][.] image it reads as an A operand (at HD = 16 lanes 16..31 of a half
+// re-read rows 0..15: they fill the unused rows 16..31 of the accumulator).
+#define AD_LANE                                                                                                          \
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;                        \
+  const int drow = HD == 16 ? (l31 & 15) : l31;                                                                          \
+  (void)wave; (void)drow
+// v_mfma_f32_32x32x16_f16: A and B operands hold k = 8 hh .. 8 hh + 7 of row / column l31; element i of the accumulator is
+// row acc_row(i, hh) of column l31 -- four groups of four consecutive rows, 8 apart, the upper half of the wave 4 further.
+MT_DEVINL int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
+MT_DEVINL void zero(f32x16& a) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { out[i] = (float)a[i]; out[8 + i] = (float)b[i]; }
+  for (int i = 0; i < 16; ++i) a[i] = 0.f;
 }
-MT_DEVINL void store16(h16* p, const float* v) {
-  h16x8 a, b;
+template <int N>
+MT_DEVINL void zero(f32x16 (&a)[N]) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { a[i] = (h16)v[i]; b[i] = (h16)v[8 + i]; }
-  stg8(p, a); stg8(p + 8, b);
+  for (int j = 0; j < N; ++j) zero(a[j]);
+}
+template <int N, int M>
+MT_DEVINL void zero(f32x16 (&a)[N][M]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) zero(a[j]);
+}
+MT_DEVINL h16x8 cat8h(h16x4 lo, h16x4 hi) { return (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
+// B operands of one fp16 global row: frag[c] = dims 16 c + 8 hh .. + 7 (p already points at dim 8 hh); zero for a row out of range
+template <int NC>
+MT_DEVINL void row_frags(const h16* p, bool valid, h16x8 (&frag)[NC]) {
+  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int c = 0; c < NC; ++c) frag[c] = valid ? ldg8(p + 16 * c) : zero8;
+}
+// Score chain: acc += A . B over the head dim, A = row `row` (32 tb + l31) of an fp16 row image [.][KP] in LDS (one 16-byte read per
+// 16-dim chunk), B = the register fragments of row_frags; NC MFMAs on the one accumulator.
+template <int HD>
+MT_DEVINL void score_chain(const h16* img, int row, int hh, const h16x8 (&frag)[AdDim<HD>::NC], f32x16& acc) {
+#pragma unroll
+  for (int c = 0; c < AdDim<HD>::NC; ++c) {
+    const h16x8 af = *reinterpret_cast<const h16x8*>(&img[row * AdDim<HD>::KP + 16 * c + 8 * hh]);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, frag[c], acc, 0, 0, 0);
+  }
+}
+// A operand from a transposed fp16 image [HD][TPV]: row 32 j + drow, k = tokens tok + {0..3} and tok + 8 + {0..3} with
+// tok = 32 tb + 16 s2 + 4 hh -- the accumulator-order permutation of k, so that elements 8 s2 .. 8 s2 + 7 of a score accumulator are
+// the matching B operand as they stand (two 8-byte reads).
+template <int HD>
+MT_DEVINL h16x8 tr_frag(const h16* img, int j, int drow, int tok) {
+  const h16* p = &img[(32 * j + drow) * AdDim<HD>::TPV + tok];
+  return cat8h(*reinterpret_cast<const h16x4*>(p), *reinterpret_cast<const h16x4*>(p + 8));
+}
+// Initial accumulator from a per-token fp32 vector in LDS (vec points at token 32 tb): element i = vec[acc_row(i, hh)], four 16-byte reads
+MT_DEVINL f32x16 acc_from_rows(const float* vec, int hh) {
+  f32x16 a;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(&vec[8 * g4 + 4 * hh]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[4 * g4 + e] = x[e];
+  }
+  return a;
+}
+// Store of a [dim][row] accumulator tile (O^T, dQ^T, dK^T, dV^T) to the lane's fp16 row: rows d = 32 j + acc_row(i, hh) (i < 8 at
+// HD = 16), so group g of accumulator j is the four consecutive dims 32 j + 8 g + 4 hh .. + 3: one 8-byte store.  scale: the injector
+// forward's 1 / l, applied as an fp32 product before the rounding; the other callers leave it at 1 (exact, folded away).
+template <int HD>
+MT_DEVINL void store_dim_tile(h16* dst, const f32x16 (&acc)[AdDim<HD>::NA], int hh, float scale = 1.f) {
+#pragma unroll
+  for (int j = 0; j < AdDim<HD>::NA; ++j)
+#pragma unroll
+    for (int g = 0; g < AdDim<HD>::NG; ++g)
+      *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) = (h16x4){(h16)(acc[j][4 * g] * scale), (h16)(acc[j][4 * g + 1] * scale),
+                                                                        (h16)(acc[j][4 * g + 2] * scale), (h16)(acc[j][4 * g + 3] * scale)};
+}
+// Staging of the token-side operand: G heads of tokens 0 .. NT - 1 of an fp32 [T][AE] operand (src at the pass's token 0, first head
+// of the group) go to LDS as fp16 -- to a row image row[G][NT][KP], to a transposed image tr[HD][TPV] (G = 1), or both; zero past T.
+// An image that is not wanted is passed as the literal nullptr: its TYPE switches the store off at compile time.  One loop stages up to
+// two operands (their loads overlap).  SCALED: operand a goes through scaled_h16 (the extractor's q).
+template <class R, class C>
+struct TokOp {
+  const float* src; R row; C tr;
+  static constexpr bool ROW = !std::is_same_v<R, std::nullptr_t>, TR = !std::is_same_v<C, std::nullptr_t>;
+};
+template <class R, class C>
+MT_DEVINL TokOp<R, C> tok_op(const float* src, R row, C tr) { return {src, row, tr}; }
+using NoTokOp = TokOp<std::nullptr_t, std::nullptr_t>;
+template <int HD, bool SCALED = false, class A, class B = NoTokOp>
+MT_DEVINL void stage_token_rows(int tid, int T, int NT, int AE, int G, A a, B b = {nullptr, nullptr, nullptr}) {
+  const int GE = G * HD;
+  for (int i = tid; i < NT * GE; i += 256) {
+    const int t = i / GE, e = i % GE;
+    const bool ok = t < T;
+    const int ro = ((e / HD) * NT + t) * AdDim<HD>::KP + e % HD, to = (e % HD) * AdDim<HD>::TPV + t;
+    const float xa = ok ? a.src[(long)t * AE + e] : 0.f;
+    const h16 ha = SCALED ? scaled_h16<HD>(xa) : (h16)xa;
+    if constexpr (A::ROW) a.row[ro] = ha;
+    if constexpr (A::TR) a.tr[to] = ha;
+    if constexpr (B::ROW || B::TR) {
+      const h16 hb = (h16)(ok ? b.src[(long)t * AE + e] : 0.f);
+      if constexpr (B::ROW) b.row[ro] = hb;
+      if constexpr (B::TR) b.tr[to] = hb;
+    }
+  }
 }
 
 // ---------------------------------------------------------------- injector -----------------------
@@ -67,48 +166,34 @@ MT_DEVINL void store16(h16* p, const float* v) {
 // v_mfma_f32_32x32x16_f16 is a whole 32-token x 32-row score block (a chain of 2 / 4 at d = 32 / 64): S^T = K . Q^T (K rows from an fp16 LDS image, Q^T
 // straight from global memory), softmax lane-local (row = lane, tokens in registers + one cross-half shuffle),
 // O^T += V^T . P^T with P^T taken from the score accumulators (V^T from a transposed fp16 LDS image).
-MT_DEVINL h16x8 cat8h(h16x4 lo, h16x4 hi) { return (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
-
 template <int HD, int HC>
 __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restrict__ q, int rows_per_pass, const float* __restrict__ k,
                                                               const float* __restrict__ v, int T, int heads, h16* __restrict__ a,
                                                               float* __restrict__ lse) {
   AD_DIMS;
+  AD_LANE;
   __shared__ __attribute__((aligned(16))) h16 ksh[TMAX * KP];     // K[t][d]
   __shared__ __attribute__((aligned(16))) h16 vT[AD * TPV];       // V^T[d][t]
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
-  for (int i = tid; i < TMAX * AD; i += 256) {
-    const int t = i / AD, d = i % AD;
-    const bool ok = t < T;
-    ksh[t * KP + d] = (h16)(ok ? k[((long)b * T + t) * AE + h * AD + d] : 0.f);
-    vT[d * TPV + t] = (h16)(ok ? v[((long)b * T + t) * AE + h * AD + d] : 0.f);
-  }
+  const int h = blockIdx.y, b = blockIdx.z;
+  const long tok0 = (long)b * T * AE + h * AD;
+  stage_token_rows<HD>(tid, T, TMAX, AE, 1, tok_op(k + tok0, ksh, nullptr), tok_op(v + tok0, nullptr, vT));
   __syncthreads();
   const int ntb = (T + 31) / 32;
   const int r = blockIdx.x * 128 + wave * 32 + l31;
   const bool valid = r < rows_per_pass;
   const long m = (long)b * rows_per_pass + (valid ? r : 0);
-  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int drow = HD == 16 ? (l31 & 15) : l31;                              // row of a [HD][.] transposed image this lane reads
   h16x8 qf[NC];                                                               // B operands: Q^T[d = 16 c + 8 hh + j][row]
-#pragma unroll
-  for (int c = 0; c < NC; ++c) qf[c] = valid ? ldg8(q + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
+  row_frags(q + m * AE + h * AD + 8 * hh, valid, qf);
   f32x16 sc[TMAX / 32];
   float mx = -1.0e30f;
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
     if (tb < ntb) {
+      zero(sc[tb]);
+      score_chain<HD>(ksh, tb * 32 + l31, hh, qf, sc[tb]);
 #pragma unroll
-      for (int i = 0; i < 16; ++i) sc[tb][i] = 0.f;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-        sc[tb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc[tb], 0, 0, 0);
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens: (i&3) + 8 (i>>2) + 4 hh
-        if (tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh >= T) sc[tb][i] = -1.0e30f;
+      for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens
+        if (tb * 32 + acc_row(i, hh) >= T) sc[tb][i] = -1.0e30f;
         mx = fmaxf(mx, sc[tb][i]);
       }
     }
@@ -116,10 +201,7 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   const float c = ASCALE * 1.4426950408889634f;
   f32x16 acc[NA];
-#pragma unroll
-  for (int j = 0; j < NA; ++j)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+  zero(acc);
   float l = 0.f;
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
@@ -133,27 +215,15 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
           l += pv;
           pf[e] = (h16)pv;
         }
-        // A operand: V^T[d = 32 j + drow][token 16 s2 + 8 (e>>2) + 4 hh + (e&3)] (the accumulator-order k permutation)
 #pragma unroll
-        for (int j = 0; j < NA; ++j) {
-          const h16* vr = &vT[(32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh];
-          const h16x8 vf = cat8h(*reinterpret_cast<const h16x4*>(vr), *reinterpret_cast<const h16x4*>(vr + 8));
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, acc[j], 0, 0, 0);
-        }
+        for (int j = 0; j < NA; ++j)
+          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag<HD>(vT, j, drow, tb * 32 + 16 * s2 + 4 * hh), pf, acc[j], 0, 0, 0);
       }
     }
   }
   l += __shfl_xor(l, 32, 64);
   if (valid) {
-    const float inv = 1.0f / l;
-    // O^T rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh (i < 8 at HD = 16): group g of accumulator j holds d = 32 j + 8 g + 4 hh + {0..3}
-    h16* dst = a + m * AE + h * AD;
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-        *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
-            (h16x4){(h16)(acc[j][4 * g] * inv), (h16)(acc[j][4 * g + 1] * inv), (h16)(acc[j][4 * g + 2] * inv), (h16)(acc[j][4 * g + 3] * inv)};
+    store_dim_tile<HD>(a + m * AE + h * AD, acc, hh, 1.0f / l);      // O^T
     if (lse && hh == 0) lse[m * AH + h] = mx * ASCALE + __logf(l);
   }
 }
@@ -169,6 +239,60 @@ __global__ __launch_bounds__(256) void inject_attn_fwd_kernel(const h16* __restr
 // and 32..63).  LDS at T = 128: 93 / 113 / 155 KiB at HD = 16 / 32 / 64; at T = 65: 56 / 75 / 112 KiB (two workgroups per CU at 16 and
 // 32, one at 64).
 constexpr int IBR = 128, ITILES = 4, RSTR = IBR + 8;   // RSTR: halves per transposed row (272 B: conflict-free b128)
+constexpr int LDS_MAX = 160 * 1024;
+// The LDS layout of each dynamic-LDS kernel is ONE struct, built as Lds{run-time arguments} by the kernel (which takes its pointers
+// from the offsets) and by the launcher (which allocates bytes()): the two cannot drift apart.  Each member is the offset of an image in
+// elements of the image's own type from the start of the allocation, computed from the members before it.
+constexpr int tok_blocks(int T) { return (T + 31) / 32 * 32; }      // TB: T up to whole 32-token blocks
+template <int HD>
+struct InjectBwdLds {      // halves
+  int T, TB = tok_blocks(T);
+  int ksh = 0;                                  // [TB][KP]   K rows
+  int vsh = ksh + TB * AdDim<HD>::KP;           // [TB][KP]   V rows
+  int kT = vsh + TB * AdDim<HD>::KP;            // [HD][TPV]  K^T
+  int psT = kT + HD * AdDim<HD>::TPV;           // [T][RSTR]
+  int dssT = psT + T * RSTR;                    // [T][RSTR]
+  int qT = dssT + T * RSTR;                     // [HD][RSTR]
+  int daT = qT + HD * RSTR;                     // [HD][RSTR]
+  int end = daT + HD * RSTR;
+  constexpr size_t bytes() const { return sizeof(h16) * (size_t)end; }
+};
+// Phase 2 of both backward kernels, one 128-row tile: acc[j] += A . B with the tile's row index as the reduction dimension, A = row
+// trow of a transposed image [tokens][RSTR] (ds or p), B = rows 32 j + drow of a transposed image [HD][RSTR] (q, da or k); 16-byte
+// reads of both.  Accumulator rows are tokens, columns dims.
+template <int HD>
+MT_DEVINL void rowtile_product(const h16* A, int trow, const h16* B, int drow, int hh, f32x16 (&acc)[AdDim<HD>::NA]) {
+#pragma unroll
+  for (int kk = 0; kk < IBR / 16; ++kk) {
+    const h16x8 afr = *reinterpret_cast<const h16x8*>(&A[trow * RSTR + kk * 16 + hh * 8]);
+#pragma unroll
+    for (int j = 0; j < AdDim<HD>::NA; ++j) {
+      const h16x8 bfr = *reinterpret_cast<const h16x8*>(&B[(32 * j + drow) * RSTR + kk * 16 + hh * 8]);
+      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr, bfr, acc[j], 0, 0, 0);
+    }
+  }
+}
+// The close of both backward kernels: the phase-2 accumulators of token block tb (rows = tokens 32 tb + acc_row(i, hh), column = dim
+// 32 j + l31, 16 valid at HD = 16) go to the head's columns of the pass's [T][AE] block of dst [B][T][AE] -- one atomic per (token, dim);
+// DET: of the partial workspace [gridDim.x][B][T][AE], slot blockIdx.x, with plain stores.
+template <bool DET>
+MT_DEVINL long flush_pass(int b) { return DET ? (long)blockIdx.x * gridDim.z + b : b; }
+template <int HD, bool DET>
+MT_DEVINL void flush_token_dim(float* dst, const f32x16 (&acc)[AdDim<HD>::NA], int tb, int T, int AE, int hh, int l31) {
+  if (HD == 16 && l31 >= HD) return;
+#pragma unroll
+  for (int j = 0; j < AdDim<HD>::NA; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int t = tb * 32 + acc_row(i, hh);
+      float* p = &dst[(long)t * AE + 32 * j + l31];
+      if constexpr (DET) {
+        if (t < T) *p = acc[j][i];
+      } else {
+        if (t < T) atomicAdd(p, acc[j][i]);
+      }
+    }
+}
 // DET (deterministic mode, det_reduce.hip): dk / dv are partial workspaces [gridDim.x][B][T][E]; the workgroup stores its sums to slot
 // blockIdx.x (its row block) with plain stores -- every (t < T, column) of a slot is owned by one lane of one (head, pass) workgroup.
 template <int HD, int HC, bool DET = false>
@@ -178,34 +302,18 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
                                                               const float* __restrict__ v, int T, int heads, h16* __restrict__ dq,
                                                               float* __restrict__ dk, float* __restrict__ dv) {
   AD_DIMS;
+  AD_LANE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
-  h16* ksh = reinterpret_cast<h16*>(smem);            // [TB][KP]   K rows
-  h16* vsh = ksh + TB * KP;                           // [TB][KP]   V rows
-  h16* kT = vsh + TB * KP;                            // [HD][TPV]  K^T
-  h16* psT = kT + AD * TPV;                           // [T][RSTR]
-  h16* dssT = psT + T * RSTR;                         // [T][RSTR]
-  h16* qT = dssT + T * RSTR;                          // [HD][RSTR]
-  h16* daT = qT + AD * RSTR;                          // [HD][RSTR]
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
-  for (int i = tid; i < TB * AD; i += 256) {
-    const int t = i / AD, d = i % AD;
-    const bool ok = t < T;
-    const h16 kv_ = (h16)(ok ? k[((long)b * T + t) * AE + h * AD + d] : 0.f);
-    ksh[t * KP + d] = kv_;
-    kT[d * TPV + t] = kv_;
-    vsh[t * KP + d] = (h16)(ok ? v[((long)b * T + t) * AE + h * AD + d] : 0.f);
-  }
-  const int drow = HD == 16 ? (l31 & 15) : l31;
+  const InjectBwdLds<HD> lds{T};
+  h16* sh = reinterpret_cast<h16*>(smem);
+  h16 *ksh = sh + lds.ksh, *vsh = sh + lds.vsh, *kT = sh + lds.kT, *psT = sh + lds.psT, *dssT = sh + lds.dssT, *qT = sh + lds.qT,
+      *daT = sh + lds.daT;
+  const int h = blockIdx.y, b = blockIdx.z;
+  const long tok0 = (long)b * T * AE + h * AD;
+  stage_token_rows<HD>(tid, T, TB, AE, 1, tok_op(k + tok0, ksh, kT), tok_op(v + tok0, vsh, nullptr));
   f32x16 acc[TMAX / 64][NA];        // phase 2: token blocks (wave >> 1) and (wave >> 1) + 2 of product (wave & 1), dims 32 j2 + lane
-#pragma unroll
-  for (int j = 0; j < TMAX / 64; ++j)
-#pragma unroll
-    for (int j2 = 0; j2 < NA; ++j2)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[j][j2][i] = 0.f;
-  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  zero(acc);
   const float c = ASCALE * 1.4426950408889634f;
   __syncthreads();
   for (int tile = 0; tile < ITILES; ++tile) {
@@ -216,11 +324,8 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
     const bool valid = r < rows_per_pass;
     const long m = (long)b * rows_per_pass + (valid ? r : 0);
     h16x8 qf[NC], daf[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      qf[c] = valid ? ldg8(q + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
-      daf[c] = valid ? ldg8(da + m * AE + h * AD + 16 * c + 8 * hh) : zero8;
-    }
+    row_frags(q + m * AE + h * AD + 8 * hh, valid, qf);
+    row_frags(da + m * AE + h * AD + 8 * hh, valid, daf);
     const float nl2 = valid ? -lse[m * AH + h] * 1.4426950408889634f : -1.0e30f;
     float delta = 0.f;
 #pragma unroll
@@ -235,27 +340,19 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
     }
     delta += __shfl_xor(delta, 32, 64);
     f32x16 dqa[NA];
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) dqa[j][i] = 0.f;
+    zero(dqa);
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
         f32x16 sc, dpv;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { sc[i] = 0.f; dpv[i] = 0.f; }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-          const h16x8 vf = *reinterpret_cast<const h16x8*>(&vsh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-          sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc, 0, 0, 0);
-          dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, daf[c], dpv, 0, 0, 0);
-        }
+        zero(sc);
+        zero(dpv);
+        score_chain<HD>(ksh, tb * 32 + l31, hh, qf, sc);
+        score_chain<HD>(vsh, tb * 32 + l31, hh, daf, dpv);
         h16x8 dsf[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;      // accumulator rows are tokens
+          const int t = tb * 32 + acc_row(i, hh);      // accumulator rows are tokens
           const float pv = t < T ? __builtin_amdgcn_exp2f(fmaf(sc[i], c, nl2)) : 0.f;
           const float ds = pv * (dpv[i] - delta) * ASCALE;
           dsf[i >> 3][i & 7] = (h16)ds;
@@ -265,66 +362,27 @@ __global__ __launch_bounds__(256) void inject_attn_bwd_kernel(const h16* __restr
           }
         }
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
+        for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
-          for (int j = 0; j < NA; ++j) {
-            const h16* kr = &kT[(32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh];
-            const h16x8 ktf = cat8h(*reinterpret_cast<const h16x4*>(kr), *reinterpret_cast<const h16x4*>(kr + 8));
-            dqa[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ktf, dsf[s2], dqa[j], 0, 0, 0);
-          }
-        }
+          for (int j = 0; j < NA; ++j)
+            dqa[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag<HD>(kT, j, drow, tb * 32 + 16 * s2 + 4 * hh), dsf[s2], dqa[j], 0, 0, 0);
       }
     }
-    if (valid) {
-      h16* dst = dq + m * AE + h * AD;
-#pragma unroll
-      for (int j = 0; j < NA; ++j)
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-          *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
-              (h16x4){(h16)dqa[j][4 * g], (h16)dqa[j][4 * g + 1], (h16)dqa[j][4 * g + 2], (h16)dqa[j][4 * g + 3]};
-    }
+    if (valid) store_dim_tile<HD>(dq + m * AE + h * AD, dqa, hh);
     __syncthreads();
-    const h16* Asrc = (wave & 1) ? psT : dssT;
-    const h16* Bsrc = (wave & 1) ? daT : qT;
 #pragma unroll
     for (int j = 0; j < TMAX / 64; ++j) {
       const int tb = (wave >> 1) + 2 * j;
-      if (tb < ntb) {
-        const int trow = min(tb * 32 + l31, T - 1);   // rows >= T: valid memory, results never flushed
-#pragma unroll
-        for (int kk = 0; kk < IBR / 16; ++kk) {
-          const h16x8 afr = *reinterpret_cast<const h16x8*>(&Asrc[trow * RSTR + kk * 16 + hh * 8]);
-#pragma unroll
-          for (int j2 = 0; j2 < NA; ++j2) {
-            const h16x8 bfr = *reinterpret_cast<const h16x8*>(&Bsrc[(32 * j2 + drow) * RSTR + kk * 16 + hh * 8]);
-            acc[j][j2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afr, bfr, acc[j][j2], 0, 0, 0);
-          }
-        }
-      }
+      // rows >= T: valid memory, results never flushed
+      if (tb < ntb) rowtile_product<HD>((wave & 1) ? psT : dssT, min(tb * 32 + l31, T - 1), (wave & 1) ? daT : qT, drow, hh, acc[j]);
     }
     __syncthreads();
   }
-  // accumulator rows are tokens: row(i) = (i&3) + 8 (i>>2) + 4 hh; column = lane & 31 = dim 32 j2 + lane (16 valid at HD = 16)
-  float* dst = (wave & 1) ? dv : dk;
-  if (HD != 16 || l31 < AD) {
+  float* dst = ((wave & 1) ? dv : dk) + flush_pass<DET>(b) * T * AE + h * AD;
 #pragma unroll
-    for (int j = 0; j < TMAX / 64; ++j) {
-      const int tb = (wave >> 1) + 2 * j;
-      if (tb < ntb) {
-#pragma unroll
-        for (int j2 = 0; j2 < NA; ++j2)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            if constexpr (DET) {
-              if (t < T) dst[(((long)blockIdx.x * gridDim.z + b) * T + t) * AE + h * AD + 32 * j2 + l31] = acc[j][j2][i];
-            } else {
-              if (t < T) atomicAdd(&dst[((long)b * T + t) * AE + h * AD + 32 * j2 + l31], acc[j][j2][i]);
-            }
-          }
-      }
-    }
+  for (int j = 0; j < TMAX / 64; ++j) {
+    const int tb = (wave >> 1) + 2 * j;
+    if (tb < ntb) flush_token_dim<HD, DET>(dst, acc[j], tb, T, AE, hh, l31);
   }
 }
 
@@ -343,31 +401,43 @@ MT_DEVINL h16x4 ad_tr4(const h16* p) {
       (__attribute__((address_space(3))) s16x4*)(__attribute__((address_space(3))) void*)p);
   return __builtin_bit_cast(h16x4, r);
 }
+// MT = the tokens the merge image is sized for: TMAX in the static form (HD = 16), T in the dynamic one
+template <int HD>
+struct ExtractFwdLds {
+  static constexpr int VSH = 4 * 32 * AdDim<HD>::VP;      // halves: the waves' V blocks [4][32][VP], at offset 0
+  static constexpr int MS = HD + 2;                       // floats per (wave, token) of the merge image: HD sums, m, l
+  int MT, MW = MT * MS;                                   // floats per wave of the merge image
+  int mrg = VSH / 2;                                      // floats: the merge image [4][MT][MS]
+  constexpr size_t bytes() const { return sizeof(float) * ((size_t)mrg + 4 * (size_t)MW); }
+};
 template <int HD, int HC>
 __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv, int T, int L, int heads,
                                                                int keys_per_split, float* __restrict__ part_acc, float* __restrict__ part_ml) {
   AD_DIMS;
-  constexpr int VP = Dm::VP, MS = AD + 2, NV = 4 * NG;      // MS: floats per (wave, token) of the merge image; NV: valid accumulator rows
+  AD_LANE;
+  using Lds = ExtractFwdLds<HD>;
+  constexpr int VP = Dm::VP, MS = Lds::MS, NV = 4 * NG;      // NV: valid accumulator rows
+  const Lds lds{HD == 16 ? TMAX : T};
   h16* vsh;                         // [4][32 * VP]
   float* mrg;                       // [4][MT][MS]
   if constexpr (HD == 16) {
-    __shared__ __attribute__((aligned(16))) h16 vsh_s[4 * 32 * VP];
-    __shared__ float mrg_s[4 * TMAX * MS];
+    __shared__ __attribute__((aligned(16))) h16 vsh_s[Lds::VSH];
+    __shared__ float mrg_s[4 * Lds{TMAX}.MW];
     vsh = vsh_s; mrg = mrg_s;
   } else {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     vsh = reinterpret_cast<h16*>(smem);
-    mrg = smem + 4 * 32 * VP / 2;
+    mrg = smem + lds.mrg;
   }
-  const int MW = (HD == 16 ? TMAX : T) * MS;                // floats per wave of the merge image
-  const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+  const int MW = lds.MW;                                    // floats per wave of the merge image
+  const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
   const int nsplit = gridDim.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
   const int li = lane & 15, tq = li >> 2, tp = li & 3;
   const int ntb = (T + 31) / 32;
   h16x8 qf[TMAX / 32][NC];          // B operands: Q^T[d = 16 c + 8 hh + j][token]
   f32x16 acc[TMAX / 32][NA];
   float mrun[TMAX / 32], lrun[TMAX / 32];
+  zero(acc);
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
     const int t = tb * 32 + l31;
@@ -375,10 +445,6 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
     for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int e = 0; e < 8; ++e) qf[tb][c][e] = scaled_h16<HD>(t < T ? q[((long)b * T + t) * AE + h * AD + 16 * c + 8 * hh + e] : 0.f);
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[tb][j][i] = 0.f;
     mrun[tb] = -1.0e30f; lrun[tb] = 0.f;
   }
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -404,21 +470,19 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         const h16* vr = &vw[(s2 * 16 + 4 * hh + tq) * VP + 32 * j + dcol + 4 * tp];
-        const h16x4 lo = ad_tr4(vr), hi = ad_tr4(vr + 8 * VP);
-        vt[j][s2] = (h16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        vt[j][s2] = cat8h(ad_tr4(vr), ad_tr4(vr + 8 * VP));
       }
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
         f32x16 sc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) sc[i] = 0.f;
+        zero(sc);
 #pragma unroll
         for (int c = 0; c < NC; ++c) sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[c], qf[tb][c], sc, 0, 0, 0);
         float mx = -1.0e30f;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {      // accumulator rows are keys (i&3) + 8 (i>>2) + 4 hh
-          if (k0 + (i & 3) + 8 * (i >> 2) + 4 * hh >= kend) sc[i] = -1.0e30f;
+        for (int i = 0; i < 16; ++i) {      // accumulator rows are keys
+          if (k0 + acc_row(i, hh) >= kend) sc[i] = -1.0e30f;
           mx = fmaxf(mx, sc[i]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -445,7 +509,7 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
       }
     }
   }
-  // per-wave partials -> LDS: O^T rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh (i < 8 at HD = 16), column = token
+  // per-wave partials -> LDS: O^T rows d = 32 j + acc_row(i, hh) (i < 8 at HD = 16), column = token
 #pragma unroll
   for (int tb = 0; tb < TMAX / 32; ++tb) {
     const int t = tb * 32 + l31;
@@ -454,7 +518,7 @@ __global__ __launch_bounds__(EFT) void extract_attn_fwd_kernel(const float* __re
 #pragma unroll
       for (int j = 0; j < NA; ++j)
 #pragma unroll
-        for (int i = 0; i < NV; ++i) mr[32 * j + (i & 3) + 8 * (i >> 2) + 4 * hh] = acc[tb][j][i];
+        for (int i = 0; i < NV; ++i) mr[32 * j + acc_row(i, hh)] = acc[tb][j][i];
       if (hh == 0) { mr[AD] = mrun[tb]; mr[AD + 1] = lrun[tb]; }
     }
   }
@@ -512,6 +576,21 @@ __global__ void extract_attn_reduce_kernel(const float* __restrict__ part_acc, c
 // token block w); one atomic per (token, dim) per workgroup at the end.  q (pre-scaled by 1/sqrt(HD)) and dout are rounded to
 // fp16 for the MFMA, as in the forward.  LDS at T = 128: 60 KiB at HD = 16 (two workgroups per CU), 80 KiB at 32, 121 KiB at 64 (one).
 constexpr int EBK = 128, ETILES = 4;
+static_assert(EBK == IBR, "rowtile_product and RSTR serve both backward kernels");
+template <int HD>
+struct ExtractBwdLds {      // floats, then halves
+  int T, TB = tok_blocks(T);
+  int nls = 0;                                    // [TB]  -lse (natural log) ; big negative past T
+  int ndl = nls + TMAX;                           // [TB]  -delta
+  int qsh = 2 * (ndl + TMAX);                     // [TB][KP]   Q rows (scaled)
+  int dosh = qsh + TB * AdDim<HD>::KP;            // [TB][KP]   dO rows
+  int qT = dosh + TB * AdDim<HD>::KP;             // [HD][TPV]  Q^T
+  int doT = qT + HD * AdDim<HD>::TPV;             // [HD][TPV]  dO^T
+  int dssT = doT + HD * AdDim<HD>::TPV;           // [T][RSTR]
+  int kT = dssT + T * RSTR;                       // [HD][RSTR]
+  int end = kT + HD * RSTR;
+  constexpr size_t bytes() const { return sizeof(h16) * (size_t)end; }
+};
 // DET (deterministic mode): dq is the partial workspace [gridDim.x][B][T][E], slot = blockIdx.x (the key block), plain stores.
 template <int HD, int HC, bool DET = false>
 __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
@@ -519,26 +598,16 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
                                                                const float* __restrict__ dout, int T, int L, int heads, float* __restrict__ dq,
                                                                h16* __restrict__ dkv) {
   AD_DIMS;
+  AD_LANE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
-  float* nls = smem;                                  // [TB]  -lse (natural log) ; big negative past T
-  float* ndl = nls + TMAX;                            // [TB]  -delta
-  h16* qsh = reinterpret_cast<h16*>(ndl + TMAX);      // [TB][KP]   Q rows (scaled)
-  h16* dosh = qsh + TB * KP;                          // [TB][KP]   dO rows
-  h16* qT = dosh + TB * KP;                           // [HD][TPV]  Q^T
-  h16* doT = qT + AD * TPV;                           // [HD][TPV]  dO^T
-  h16* dssT = doT + AD * TPV;                         // [T][RSTR]
-  h16* kT = dssT + T * RSTR;                          // [HD][RSTR]
-  const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
-  for (int i = tid; i < TB * AD; i += 256) {
-    const int t = i / AD, d = i % AD;
-    const bool ok = t < T;
-    const h16 qv_ = scaled_h16<HD>(ok ? q[((long)b * T + t) * AE + h * AD + d] : 0.f);
-    const h16 dv_ = (h16)(ok ? dout[((long)b * T + t) * AE + h * AD + d] : 0.f);
-    qsh[t * KP + d] = qv_; qT[d * TPV + t] = qv_;
-    dosh[t * KP + d] = dv_; doT[d * TPV + t] = dv_;
-  }
+  const ExtractBwdLds<HD> lds{T};
+  float *nls = smem + lds.nls, *ndl = smem + lds.ndl;
+  h16* sh = reinterpret_cast<h16*>(smem);
+  h16 *qsh = sh + lds.qsh, *dosh = sh + lds.dosh, *qT = sh + lds.qT, *doT = sh + lds.doT, *dssT = sh + lds.dssT, *kT = sh + lds.kT;
+  const int h = blockIdx.y, b = blockIdx.z;
+  const long tok0 = (long)b * T * AE + h * AD;
+  stage_token_rows<HD, true>(tid, T, TB, AE, 1, tok_op(q + tok0, qsh, qT), tok_op(dout + tok0, dosh, doT));
   for (int t = tid; t < TB; t += 256) {
     float d = 0.f, l = 1.0e30f;
     if (t < T) {
@@ -547,12 +616,8 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
     }
     nls[t] = -l; ndl[t] = -d;
   }
-  const int drow = HD == 16 ? (l31 & 15) : l31;
   f32x16 accq[NA];                  // phase 2: token block `wave`, dims 32 j + lane
-#pragma unroll
-  for (int j = 0; j < NA; ++j)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accq[j][i] = 0.f;
+  zero(accq);
   const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   __syncthreads();
   for (int tile = 0; tile < ETILES; ++tile) {
@@ -571,32 +636,18 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
       for (int e = 0; e < 8; ++e) kT[(16 * c + 8 * hh + e) * RSTR + kl] = kf[c][e];
     }
     f32x16 dka[NA], dva[NA];
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { dka[j][i] = 0.f; dva[j][i] = 0.f; }
+    zero(dka);
+    zero(dva);
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
-        f32x16 sc, dpv;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh
-          const f32x4 l4 = *reinterpret_cast<const f32x4*>(&nls[tb * 32 + 8 * g4 + 4 * hh]);
-          const f32x4 d4 = *reinterpret_cast<const f32x4*>(&ndl[tb * 32 + 8 * g4 + 4 * hh]);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sc[4 * g4 + e] = l4[e]; dpv[4 * g4 + e] = d4[e]; }
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-          const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-          const h16x8 da = *reinterpret_cast<const h16x8*>(&dosh[(tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-          sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf[c], sc, 0, 0, 0);
-          dpv = __builtin_amdgcn_mfma_f32_32x32x16_f16(da, vf[c], dpv, 0, 0, 0);
-        }
+        f32x16 sc = acc_from_rows(nls + tb * 32, hh), dpv = acc_from_rows(ndl + tb * 32, hh);      // accumulator rows are tokens
+        score_chain<HD>(qsh, tb * 32 + l31, hh, kf, sc);
+        score_chain<HD>(dosh, tb * 32 + l31, hh, vf, dpv);
         h16x8 pf[2], dsf[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          const int t = tb * 32 + acc_row(i, hh);
           const float pv = valid ? __expf(sc[i]) : 0.f;       // rows past T carry -1e30 -> 0
           const float ds = pv * dpv[i];
           pf[i >> 3][i & 7] = (h16)pv;
@@ -607,57 +658,23 @@ __global__ __launch_bounds__(256) void extract_attn_bwd_kernel(const float* __re
         for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
           for (int j = 0; j < NA; ++j) {
-            const int toff = (32 * j + drow) * TPV + tb * 32 + 16 * s2 + 4 * hh;
-            const h16x8 qtf = cat8h(*reinterpret_cast<const h16x4*>(&qT[toff]), *reinterpret_cast<const h16x4*>(&qT[toff + 8]));
-            const h16x8 dtf = cat8h(*reinterpret_cast<const h16x4*>(&doT[toff]), *reinterpret_cast<const h16x4*>(&doT[toff + 8]));
-            dka[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(qtf, dsf[s2], dka[j], 0, 0, 0);
-            dva[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(dtf, pf[s2], dva[j], 0, 0, 0);
+            const int tok = tb * 32 + 16 * s2 + 4 * hh;
+            dka[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag<HD>(qT, j, drow, tok), dsf[s2], dka[j], 0, 0, 0);
+            dva[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(tr_frag<HD>(doT, j, drow, tok), pf[s2], dva[j], 0, 0, 0);
           }
         }
       }
     }
-    if (valid) {      // rows d = 32 j + (i&3) + 8 (i>>2) + 4 hh of the d x key accumulators (i < 8 at HD = 16; qsh already carries the scale)
+    if (valid) {      // the d x key accumulators (qsh already carries the scale)
       h16* dst = dkv + ((long)b * L + key) * (2 * AE) + h * AD;
-#pragma unroll
-      for (int j = 0; j < NA; ++j) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-          *reinterpret_cast<h16x4*>(dst + 32 * j + 8 * g + 4 * hh) =
-              (h16x4){(h16)dka[j][4 * g], (h16)dka[j][4 * g + 1], (h16)dka[j][4 * g + 2], (h16)dka[j][4 * g + 3]};
-#pragma unroll
-        for (int g = 0; g < NG; ++g)
-          *reinterpret_cast<h16x4*>(dst + AE + 32 * j + 8 * g + 4 * hh) =
-              (h16x4){(h16)dva[j][4 * g], (h16)dva[j][4 * g + 1], (h16)dva[j][4 * g + 2], (h16)dva[j][4 * g + 3]};
-      }
+      store_dim_tile<HD>(dst, dka, hh);
+      store_dim_tile<HD>(dst + AE, dva, hh);
     }
     __syncthreads();
-    if (wave < ntb) {               // uniform per wave
-      const int trow = min(wave * 32 + l31, T - 1);
-#pragma unroll
-      for (int kk = 0; kk < EBK / 16; ++kk) {
-        const h16x8 af = *reinterpret_cast<const h16x8*>(&dssT[trow * RSTR + kk * 16 + hh * 8]);
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-          const h16x8 bf = *reinterpret_cast<const h16x8*>(&kT[(32 * j + drow) * RSTR + kk * 16 + hh * 8]);
-          accq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, accq[j], 0, 0, 0);
-        }
-      }
-    }
+    if (wave < ntb) rowtile_product<HD>(dssT, min(wave * 32 + l31, T - 1), kT, drow, hh, accq);      // uniform per wave
     __syncthreads();
   }
-  if ((HD != 16 || l31 < AD) && wave < ntb) {
-#pragma unroll
-    for (int j = 0; j < NA; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int t = wave * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-        if constexpr (DET) {
-          if (t < T) dq[(((long)blockIdx.x * gridDim.z + b) * T + t) * AE + h * AD + 32 * j + l31] = accq[j][i];
-        } else {
-          if (t < T) atomicAdd(&dq[((long)b * T + t) * AE + h * AD + 32 * j + l31], accq[j][i]);
-        }
-      }
-  }
+  if (wave < ntb) flush_token_dim<HD, DET>(dq + flush_pass<DET>(b) * T * AE + h * AD, accq, wave, T, AE, hh, l31);
 }
 
 // ---------------------------------------------------------------- token self-attention -----------
@@ -672,15 +689,15 @@ MT_DEVINL f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p);
 // Score rows of the forward: T entries padded to a multiple of four, row stride S1 = 4 x odd >= that (sixteen tokens of a wave then start
 // on sixteen different 16-byte bank groups), so that the value sweep reads FOUR probabilities with one 16-byte read -- every LDS read of
 // that loop is in the 8 / 16-byte banking class (common.h: no counted lgkmcnt wait may span both classes).
-MT_DEVINL int mha_t4(int T) { return (T + 3) & ~3; }
-MT_DEVINL int mha_s1(int T) { const int t4 = mha_t4(T); return ((t4 >> 2) & 1) ? t4 : t4 + 4; }
+__host__ __device__ constexpr int mha_t4(int T) { return (T + 3) & ~3; }
+__host__ __device__ constexpr int mha_s1(int T) { return ((mha_t4(T) >> 2) & 1) ? mha_t4(T) : mha_t4(T) + 4; }
 // DROP (nn.MultiheadAttention(dropout = p) in train(): dropout on the softmax, adapter_modules.py:42-52): P~ = P o m / (1 - p), m the
 // element-dropout keep mask of drop.site at linear index ((b heads + h) T + i) T + j -- the mask mt_dropout_f32 draws over the flat
 // [B heads T T] tensor.  The workgroup's T x T keep flags live in LDS as a BIT image, built once before the first barrier: byte x holds the
 // elements of linear index 8 (base / 8 + x) .. + 7 (base = the head's first element; two Philox calls, each yielding four consecutive
 // elements), so element (i, j) is bit (base & 7) + i T + j.  Writers store bytes, readers load 4-byte words: one banking class.
 // mha_keep_bytes(T): the image's LDS, a multiple of four that covers the word of the last bit (2052 bytes at T = 128).
-__host__ __device__ __forceinline__ int mha_keep_bytes(int T) { return (((T * T + 14) >> 3) + 3) & ~3; }
+__host__ __device__ constexpr int mha_keep_bytes(int T) { return (((T * T + 14) >> 3) + 3) & ~3; }
 MT_DEVINL uint32_t lds_u32(const uint32_t* p) { return *reinterpret_cast<const volatile uint32_t*>(p); }
 MT_DEVINL void mha_keep_image(uint32_t* mb, int T, uint64_t base, const DropArgs& d, int tid) {
   uint8_t* mb8 = reinterpret_cast<uint8_t*>(mb);
@@ -693,6 +710,34 @@ MT_DEVINL void mha_keep_image(uint32_t* mb, int T, uint64_t base, const DropArgs
   }
 }
 MT_DEVINL bool mha_keep(const uint32_t* mb, int bit) { return (lds_u32(mb + (bit >> 5)) >> (bit & 31)) & 1u; }
+// x o m / (1 - p) for the element at `bit` of the keep image (keep = 1 / (1 - p)): a dropped entry is SELECTED to 0, never multiplied
+// by it (0 x inf, 0 x nan stay out)
+MT_DEVINL float mha_drop_sel(const uint32_t* mb, int bit, float x, float keep) { return mha_keep(mb, bit) ? x * keep : 0.f; }
+// Staging of forward and backward: rows 0 .. T - 1 of the head's slice (src[n] + o0 + t E) of N fp32 operands go to the LDS images
+// img[n] [.][HD] as 16-byte copies; rows T .. NT - 1 of the image zpad are zeroed (NT = T and the literal nullptr: no such rows).
+template <int HD, int N, class Z>
+MT_DEVINL void mha_stage(int tid, int T, int NT, long o0, int E, const float* const (&src)[N], float* const (&img)[N], Z zpad) {
+  constexpr int C4 = HD / 4;      // 16-byte chunks per row
+  for (int i = tid; i < NT * C4; i += 512) {
+    const int tt = i / C4, c = (i % C4) * 4;
+    if (std::is_same_v<Z, std::nullptr_t> || tt < T) {
+      const long o = o0 + (long)tt * E + c;
+#pragma unroll
+      for (int n = 0; n < N; ++n) *reinterpret_cast<f32x4*>(img[n] + tt * HD + c) = ld4(src[n] + o);
+    } else if constexpr (!std::is_same_v<Z, std::nullptr_t>) {
+      *reinterpret_cast<f32x4*>(zpad + tt * HD + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+template <int HD, bool DROP>
+struct TokenFwdLds {      // floats
+  int T, T4 = mha_t4(T), S1 = mha_s1(T);
+  int ks = 0;                   // [T][HD]
+  int vs = ks + T * HD;         // [T4][HD], rows T .. T4 - 1 zero
+  int ss = vs + T4 * HD;        // [T][S1], entries T .. T4 - 1 of a row zero
+  int mb = ss + T * S1;         // DROP: the keep-bit image, mha_keep_bytes(T)
+  constexpr size_t bytes() const { return sizeof(float) * (size_t)mb + (DROP ? mha_keep_bytes(T) : 0); }
+};
 template <int HD, bool DROP = false>
 __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                             int T, int E, int heads, float* __restrict__ out, float* __restrict__ probs,
@@ -700,24 +745,14 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
   constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;      // C4: 16-byte chunks per row; DS: dims a thread owns in the value sweep
   constexpr float ASCALE = AdDim<HD>::SCALE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int T4 = mha_t4(T), S1 = mha_s1(T);
-  float* ks = smem;                 // [T][HD]
-  float* vs = ks + T * AD;          // [T4][HD], rows T .. T4 - 1 zero
-  float* ss = vs + T4 * AD;         // [T][S1], entries T .. T4 - 1 of a row zero
+  const TokenFwdLds<HD, DROP> lds{T};
+  const int T4 = lds.T4, S1 = lds.S1;
+  float *ks = smem + lds.ks, *vs = smem + lds.vs, *ss = smem + lds.ss;
+  uint32_t* mb = reinterpret_cast<uint32_t*>(smem + lds.mb);
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3;
-  uint32_t* mb = reinterpret_cast<uint32_t*>(ss + T * S1);      // DROP: the keep-bit image, mha_keep_bytes(T)
   const uint64_t mbase = ((uint64_t)b * heads + h) * T * T;
   if constexpr (DROP) mha_keep_image(mb, T, mbase, drop, tid);
-  for (int i = tid; i < T4 * C4; i += 512) {
-    const int tt = i / C4, c = (i % C4) * 4;
-    if (tt < T) {
-      const long o = ((long)b * T + tt) * E + h * AD + c;
-      *reinterpret_cast<f32x4*>(ks + tt * AD + c) = ld4(k + o);
-      *reinterpret_cast<f32x4*>(vs + tt * AD + c) = ld4(v + o);
-    } else {
-      *reinterpret_cast<f32x4*>(vs + tt * AD + c) = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
+  mha_stage<HD>(tid, T, T4, (long)b * T * E + h * AD, E, {k, v}, {ks, vs}, vs);
   const int t = tid >> 2;
   const bool act = t < T;
   float qv[AD];
@@ -750,13 +785,13 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
     l += __shfl_xor(l, 2, 64);
     const float inv = 1.0f / l;
     float* pr = probs + (((long)b * heads + h) * T + t) * T;
-    if constexpr (DROP) {      // probs keeps P (the backward and the attention maps read it), the value sweep sees P~; a dropped entry is
-      const float keep = 1.f / (1.f - drop.p);      // selected to 0, never multiplied by it
+    if constexpr (DROP) {      // probs keeps P (the backward and the attention maps read it), the value sweep sees P~
+      const float keep = 1.f / (1.f - drop.p);
       const int bit0 = (int)(mbase & 7) + t * T;
       for (int j = sub; j < T; j += 4) {
         const float p = ss[t * S1 + j] * inv;
         pr[j] = p;
-        ss[t * S1 + j] = mha_keep(mb, bit0 + j) ? p * keep : 0.f;
+        ss[t * S1 + j] = mha_drop_sel(mb, bit0 + j, p, keep);
       }
     } else {
       for (int j = sub; j < T; j += 4) { const float p = ss[t * S1 + j] * inv; ss[t * S1 + j] = p; pr[j] = p; }
@@ -791,37 +826,39 @@ __global__ __launch_bounds__(512) void token_mha_fwd_kernel(const float* __restr
 // sits behind the images above: + mha_keep_bytes(T), so the DROP instantiations change form one token earlier where the sum was
 // within 2 KiB of the limit:
 //   0  T <= 126 at HD = 16, <= 113 at 32, <= 92 at 64        1  every T <= 128 at 16 and 32, T <= 110 at 64        2  the rest
+// (All these limits are TokenBwdLds<HD, FORM, DROP>(T).bytes() <= LDS_MAX: the launcher takes the first FORM that fits.)
+template <int HD, int FORM, bool DROP>
+struct TokenBwdLds {      // floats
+  int T;
+  int qs = 0;                                       // [T][HD]     (Q and K: not in FORM 2)
+  int ks = qs + T * HD;
+  int vs = FORM == 2 ? 0 : ks + T * HD;
+  int dos = vs + T * HD;
+  int dss = dos + T * HD;                           // [T][T + 1]  dS (already scaled)
+  int pls = dss + T * (T + 1);                      // [T][T + 1]  P (FORM 0 only)
+  int mb = FORM == 0 ? pls + T * (T + 1) : pls;     // DROP: the keep-bit image, mha_keep_bytes(T)
+  constexpr size_t bytes() const { return sizeof(float) * (size_t)mb + (DROP ? mha_keep_bytes(T) : 0); }
+};
 template <int HD, int FORM, bool DROP = false>
 __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                             const float* __restrict__ probs, const float* __restrict__ dout, int T, int E,
                                                             int heads, float* __restrict__ dq, float* __restrict__ dk, float* __restrict__ dv,
                                                             DropArgs drop) {
-  constexpr int AD = HD, C4 = HD / 4, DS = HD / 4;
+  constexpr int AD = HD, DS = HD / 4;
   constexpr float ASCALE = AdDim<HD>::SCALE;
   constexpr bool PL = FORM == 0, GQK = FORM == 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* qs = smem;                 // [T][HD]     (Q and K: not in FORM 2)
-  float* ks = qs + T * AD;
-  float* vs = GQK ? smem : ks + T * AD;
-  float* dos = vs + T * AD;
-  float* dss = dos + T * AD;        // [T][T + 1]  dS (already scaled)
-  float* pls = dss + T * (T + 1);   // [T][T + 1]  P (FORM 0 only)
+  const TokenBwdLds<HD, FORM, DROP> lds{T};
+  float *qs = smem + lds.qs, *ks = smem + lds.ks, *vs = smem + lds.vs, *dos = smem + lds.dos, *dss = smem + lds.dss, *pls = smem + lds.pls;
+  uint32_t* mb = reinterpret_cast<uint32_t*>(smem + lds.mb);
   const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, sub = tid & 3, S1 = T + 1;
   const float* pbase = probs + ((long)b * heads + h) * T * T;
-  uint32_t* mb = reinterpret_cast<uint32_t*>(PL ? pls + T * (T + 1) : pls);      // DROP: the keep-bit image, mha_keep_bytes(T)
   const uint64_t mbase = ((uint64_t)b * heads + h) * T * T;
   const float keep = DROP ? 1.f / (1.f - drop.p) : 1.f;
   if constexpr (DROP) mha_keep_image(mb, T, mbase, drop, tid);
-  for (int i = tid; i < T * C4; i += 512) {
-    const int tt = i / C4, c = (i % C4) * 4;
-    const long o = ((long)b * T + tt) * E + h * AD + c;
-    if (!GQK) {
-      *reinterpret_cast<f32x4*>(qs + tt * AD + c) = ld4(q + o);
-      *reinterpret_cast<f32x4*>(ks + tt * AD + c) = ld4(k + o);
-    }
-    *reinterpret_cast<f32x4*>(vs + tt * AD + c) = ld4(v + o);
-    *reinterpret_cast<f32x4*>(dos + tt * AD + c) = ld4(dout + o);
-  }
+  const long o0 = (long)b * T * E + h * AD;
+  if constexpr (GQK) mha_stage<HD>(tid, T, T, o0, E, {v, dout}, {vs, dos}, nullptr);
+  else mha_stage<HD>(tid, T, T, o0, E, {q, k, v, dout}, {qs, ks, vs, dos}, nullptr);
   if (PL)
     for (int i = tid; i < T * T; i += 512) pls[(i / T) * S1 + i % T] = pbase[i];
   __syncthreads();
@@ -847,7 +884,7 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
     if constexpr (DROP) {      // dP = dP~ o m / (1 - p), written back over the thread's own entries (4-byte class: mask words, P, dP)
       const int bit0 = (int)(mbase & 7) + t * T;
       for (int j = sub; j < T; j += 4) {
-        const float dp = mha_keep(mb, bit0 + j) ? lds_f32(&dss[t * S1 + j]) * keep : 0.f;
+        const float dp = mha_drop_sel(mb, bit0 + j, lds_f32(&dss[t * S1 + j]), keep);
         dss[t * S1 + j] = dp;
         delta = fmaf(lds_f32(&pr[j]), dp, delta);
       }
@@ -874,7 +911,7 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
 #pragma unroll
       for (int x = 0; x < DS / 4; ++x) ak[x] += dsk * lds_f32x4_by_dword(qr + j * rst + 4 * x);
       float pv = lds_f32(&pc[j * pst]);
-      if constexpr (DROP) pv = mha_keep(mb, (int)(mbase & 7) + j * T + t) ? pv * keep : 0.f;      // P~[j][t]
+      if constexpr (DROP) pv = mha_drop_sel(mb, (int)(mbase & 7) + j * T + t, pv, keep);      // P~[j][t]
 #pragma unroll
       for (int x = 0; x < DS / 4; ++x) av[x] += pv * lds_f32x4_by_dword(dos + j * AD + DS * sub + 4 * x);
     }
@@ -891,7 +928,8 @@ __global__ __launch_bounds__(512) void token_mha_bwd_kernel(const float* __restr
 // ---------------------------------------------------------------- attention maps (forward only) ---
 // The head-averaged softmax of each adapter attention (nn.MultiheadAttention's `need_weights` output), recomputed in one streaming
 // pass from what the forward already keeps: the fp16 operands and the row log-sum-exp.  The scores are rounded exactly as the
-// forward rounds them, so every row of every head sums to one against the saved LSE.
+// forward rounds them -- through the same stage_token_rows / scaled_h16 / score_chain -- so every row of every head sums to one
+// against the saved LSE.
 constexpr int PBR = 128;          // keys (extractor) / patch rows (injector) per workgroup: 4 waves x 32
 
 // Extractor: w[b, t, l] = 1/heads sum_h exp(s_bthl - lse_bth), s = fp16(q / sqrt(HD)) . fp16(k) (extract_attn_fwd's rounding).
@@ -902,34 +940,41 @@ constexpr int PBR = 128;          // keys (extractor) / patch rows (injector) pe
 // that two workgroups (8 waves) share a CU in every form -- all 12 heads at once at 12 x 16 (78 KiB at T = 128, as before the
 // template), 3 passes of 4 heads at 9 x 64 rather than a 162 KiB image of all nine or fewer tokens per workgroup.
 constexpr int PROBS_LDS = 80 * 1024;
+// heads per LDS image of the attention-map kernels: all of them when that fits PROBS_LDS, else the largest group that does
+inline int probs_group(int heads, size_t per_head) {
+  const int g = (int)((size_t)PROBS_LDS / per_head);
+  return g < 1 ? 1 : g > heads ? heads : g;
+}
+template <int HD>
+struct ExtractProbsLds {
+  int T, G, TB = tok_blocks(T);
+  int nls = 0;                      // floats: [G][TB]      -lse; -1e30 past T
+  int qsh = 2 * (nls + G * TB);     // halves: [G][TB][KP]  q / sqrt(HD) (fp16); zero past T
+  constexpr size_t bytes() const { return sizeof(h16) * ((size_t)qsh + (size_t)G * TB * AdDim<HD>::KP); }
+  constexpr size_t per_head() const { return bytes() / G; }
+};
 template <int HD, int HC>
 __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __restrict__ q, const h16* __restrict__ kv,
                                                                  const float* __restrict__ lse, int T, int L, int heads, int hgroup,
                                                                  float* __restrict__ w) {
   AD_DIMS;
+  AD_LANE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
   const int G = HC ? HC : hgroup;                         // heads per LDS image
-  float* nls = smem;                                      // [G][TB]      -lse; -1e30 past T
-  h16* qsh = reinterpret_cast<h16*>(nls + G * TB);        // [G][TB][KP]  q / sqrt(HD) (fp16); zero past T
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
+  const ExtractProbsLds<HD> lds{T, G};
+  float* nls = smem + lds.nls;
+  h16* qsh = reinterpret_cast<h16*>(smem) + lds.qsh;
+  const int b = blockIdx.y;
   const int key = blockIdx.x * PBR + wave * 32 + l31;
   const bool valid = key < L;
   const h16* row = kv + ((long)b * L + (valid ? key : 0)) * (2 * AE) + 8 * hh;
-  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   f32x16 acc[TMAX / 32];
-#pragma unroll
-  for (int tb = 0; tb < TMAX / 32; ++tb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
+  zero(acc);
   for (int h0 = 0; h0 < AH; h0 += G) {
-    const int gh = min(G, AH - h0), GE = gh * AD;
+    const int gh = min(G, AH - h0);
     if (h0) __syncthreads();          // the previous group's image has been read by every wave
-    for (int i = tid; i < TB * GE; i += 256) {
-      const int t = i / GE, e = i % GE;
-      qsh[((e / AD) * TB + t) * KP + e % AD] = scaled_h16<HD>(t < T ? q[((long)b * T + t) * AE + h0 * AD + e] : 0.f);
-    }
+    stage_token_rows<HD, true>(tid, T, TB, AE, gh, tok_op(q + (long)b * T * AE + h0 * AD, qsh, nullptr));
     for (int i = tid; i < TB * gh; i += 256) {
       const int t = i / gh, h = i % gh;
       nls[h * TB + t] = t < T ? -lse[((long)b * T + t) * AH + h0 + h] : -1.0e30f;
@@ -937,23 +982,12 @@ __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __
     __syncthreads();
     for (int h = 0; h < gh; ++h) {
       h16x8 kf[NC];                   // B operands: K^T[d = 16 c + 8 hh + j][key]
-#pragma unroll
-      for (int c = 0; c < NC; ++c) kf[c] = valid ? ldg8(row + (h0 + h) * AD + 16 * c) : zero8;
+      row_frags(row + (h0 + h) * AD, valid, kf);
 #pragma unroll
       for (int tb = 0; tb < TMAX / 32; ++tb) {
         if (tb < ntb) {
-          f32x16 sc;
-#pragma unroll
-          for (int g4 = 0; g4 < 4; ++g4) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh
-            const f32x4 l4 = *reinterpret_cast<const f32x4*>(&nls[h * TB + tb * 32 + 8 * g4 + 4 * hh]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sc[4 * g4 + e] = l4[e];
-          }
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            const h16x8 qa = *reinterpret_cast<const h16x8*>(&qsh[(h * TB + tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf[c], sc, 0, 0, 0);
-          }
+          f32x16 sc = acc_from_rows(nls + h * TB + tb * 32, hh);      // accumulator rows are tokens
+          score_chain<HD>(qsh, h * TB + tb * 32 + l31, hh, kf, sc);
 #pragma unroll
           for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(sc[i]);
         }
@@ -967,7 +1001,7 @@ __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __
       if (tb < ntb) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          const int t = tb * 32 + acc_row(i, hh);
           if (t < T) w[((long)b * T + t) * L + key] = acc[tb][i] * inv;
         }
       }
@@ -980,51 +1014,46 @@ __global__ __launch_bounds__(256) void extract_attn_probs_kernel(const float* __
 // per 32-token block (K rows from an fp16 LDS image of a group of G heads, 16-byte reads; G as above: the image or the 65 KiB output
 // tile, whichever is larger, stays within 80 KiB -- two workgroups per CU in every form).  The [128 rows][T] tile then goes through LDS
 // (4-byte writes, a barrier, 4-byte reads; odd row stride) and leaves as one contiguous, coalesced run of the [M, T] output.
-MT_DEVINL int probs_stride(int T) { return T | 1; }
+template <int HD>
+struct InjectProbsLds {
+  int T, G, TB = tok_blocks(T), S = T | 1;      // S: floats per row of the output tile (odd)
+  int ksh = 0;      // halves: [G][TB][KP]  fp16(k); zero past T
+  int osh = 0;      // floats: [128][S]     the output tile, over the K image once every wave is done with it
+  constexpr size_t per_head() const { return sizeof(h16) * (size_t)TB * AdDim<HD>::KP; }
+  constexpr size_t bytes() const { return per_head() * G > sizeof(float) * PBR * S ? per_head() * G : sizeof(float) * PBR * S; }
+};
 template <int HD, int HC>
 __global__ __launch_bounds__(256) void inject_attn_probs_kernel(const h16* __restrict__ q, int rows_per_pass, const float* __restrict__ k,
                                                                 const float* __restrict__ lse, int T, int heads, int hgroup,
                                                                 float* __restrict__ w) {
   AD_DIMS;
+  AD_LANE;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ntb = (T + 31) / 32, TB = ntb * 32;
   const int G = HC ? HC : hgroup;                         // heads per LDS image
-  h16* ksh = reinterpret_cast<h16*>(smem);                // [G][TB][KP]  fp16(k); zero past T
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6, hh = lane >> 5, l31 = lane & 31;
+  const InjectProbsLds<HD> lds{T, G};
+  h16* ksh = reinterpret_cast<h16*>(smem) + lds.ksh;
+  const int b = blockIdx.y;
   const int r0 = blockIdx.x * PBR, rl = wave * 32 + l31;
   const bool valid = r0 + rl < rows_per_pass;
   const long m = (long)b * rows_per_pass + (valid ? r0 + rl : 0);
-  const h16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   f32x16 acc[TMAX / 32];
-#pragma unroll
-  for (int tb = 0; tb < TMAX / 32; ++tb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[tb][i] = 0.f;
+  zero(acc);
   for (int h0 = 0; h0 < AH; h0 += G) {
-    const int gh = min(G, AH - h0), GE = gh * AD;
+    const int gh = min(G, AH - h0);
     if (h0) __syncthreads();          // the previous group's image has been read by every wave
-    for (int i = tid; i < TB * GE; i += 256) {
-      const int t = i / GE, e = i % GE;
-      ksh[((e / AD) * TB + t) * KP + e % AD] = (h16)(t < T ? k[((long)b * T + t) * AE + h0 * AD + e] : 0.f);
-    }
+    stage_token_rows<HD>(tid, T, TB, AE, gh, tok_op(k + (long)b * T * AE + h0 * AD, ksh, nullptr));
     __syncthreads();
     for (int h = 0; h < gh; ++h) {
       h16x8 qf[NC];                   // B operands: Q^T[d = 16 c + 8 hh + j][row]
-#pragma unroll
-      for (int c = 0; c < NC; ++c) qf[c] = valid ? ldg8(q + m * AE + (h0 + h) * AD + 16 * c + 8 * hh) : zero8;
+      row_frags(q + m * AE + (h0 + h) * AD + 8 * hh, valid, qf);
       const float nl = valid ? -lse[m * AH + h0 + h] : 0.f;
 #pragma unroll
       for (int tb = 0; tb < TMAX / 32; ++tb) {
         if (tb < ntb) {
           f32x16 sc;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-#pragma unroll
-          for (int c = 0; c < NC; ++c) {
-            const h16x8 kf = *reinterpret_cast<const h16x8*>(&ksh[(h * TB + tb * 32 + l31) * KP + 16 * c + 8 * hh]);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[c], sc, 0, 0, 0);
-          }
+          zero(sc);
+          score_chain<HD>(ksh, h * TB + tb * 32 + l31, hh, qf, sc);
 #pragma unroll
           for (int i = 0; i < 16; ++i) acc[tb][i] += __expf(fmaf(sc[i], ASCALE, nl));
         }
@@ -1032,16 +1061,16 @@ __global__ __launch_bounds__(256) void inject_attn_probs_kernel(const h16* __res
     }
   }
   __syncthreads();                  // every wave is done with the K image: its storage takes the output tile
-  const int S = probs_stride(T);
-  float* osh = smem;                // [128][S]
+  const int S = lds.S;
+  float* osh = smem + lds.osh;      // [128][S]
   const float inv = 1.0f / (float)AH;
   if (valid) {
 #pragma unroll
     for (int tb = 0; tb < TMAX / 32; ++tb) {
       if (tb < ntb) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens (i&3) + 8 (i>>2) + 4 hh, column = the lane's row
-          const int t = tb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+        for (int i = 0; i < 16; ++i) {      // accumulator rows are tokens, column = the lane's row
+          const int t = tb * 32 + acc_row(i, hh);
           if (t < T) osh[rl * S + t] = acc[tb][i] * inv;
         }
       }
@@ -1085,178 +1114,107 @@ __global__ void token_probs_mean_kernel(const float* __restrict__ probs, int B, 
     return rc__;                                            \
   } while (0)
 
-constexpr int LDS_MAX = 160 * 1024;
+// Every launch of this file: K with `shm` bytes of dynamic LDS (its layout's bytes(); more than LDS_MAX: unsupported).  A kernel that takes
+// dynamic LDS is opted into LDS_MAX once per instantiation (one static per K).
+template <auto K, class... Args>
+int ad_launch(dim3 grid, int block, size_t shm, hipStream_t stream, Args... args) {
+  if (shm > (size_t)LDS_MAX) return MT_ERR_UNSUPPORTED;
+  static bool attr_set = false;
+  if (shm && !attr_set) {
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(K, grid, dim3(block), shm, stream, args...);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
 
 template <int HD, int HC>
 int launch_inject_fwd(const h16* q, int rows_per_pass, int B, const float* k, const float* v, int T, int heads, h16* a, float* lse,
                       hipStream_t stream) {
-  hipLaunchKernelGGL((inject_attn_fwd_kernel<HD, HC>), dim3(cdiv(rows_per_pass, 128), heads, B), dim3(256), 0, stream, q, rows_per_pass, k,
-                     v, T, heads, a, lse);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return ad_launch<inject_attn_fwd_kernel<HD, HC>>(dim3(cdiv(rows_per_pass, 128), heads, B), 256, 0, stream, q, rows_per_pass, k, v, T, heads, a,
+                                                   lse);
 }
 
 template <int HD, int HC, bool DET = false>
 int launch_inject_bwd(const h16* q, const h16* a, const float* lse, const h16* da, int rows_per_pass, int B, const float* k, const float* v,
                       int T, int heads, h16* dq, float* dk, float* dv, hipStream_t stream) {
-  using Dm = AdDim<HD>;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t shm = sizeof(h16) * ((size_t)2 * TBk * Dm::KP + HD * Dm::TPV + (size_t)(2 * T + 2 * HD) * RSTR);
-  if (shm > (size_t)LDS_MAX) return MT_ERR_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)inject_attn_bwd_kernel<HD, HC, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((inject_attn_bwd_kernel<HD, HC, DET>), dim3(cdiv(rows_per_pass, IBR * ITILES), heads, B), dim3(256), shm, stream, q, a, lse,
-                     da, rows_per_pass, k, v, T, heads, dq, dk, dv);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  return ad_launch<inject_attn_bwd_kernel<HD, HC, DET>>(dim3(cdiv(rows_per_pass, IBR * ITILES), heads, B), 256, InjectBwdLds<HD>{T}.bytes(), stream,
+                                                        q, a, lse, da, rows_per_pass, k, v, T, heads, dq, dk, dv);
 }
 
 template <int HD, int HC>
 int launch_extract_fwd(const float* q, const h16* kv, int B, int T, int L, int heads, int kps, float* out, float* lse, float* part_acc,
                        float* part_ml, int nsplit, hipStream_t stream) {
   // (HD = 16: static LDS; beyond, the V blocks and the merge image [4][T][HD + 2] are dynamic)
-  const size_t shm = HD == 16 ? 0 : sizeof(h16) * 4 * 32 * AdDim<HD>::VP + sizeof(float) * 4 * (size_t)T * (HD + 2);
-  if (HD != 16) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)extract_attn_fwd_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-      attr_set = true;
-    }
-  }
-  hipLaunchKernelGGL((extract_attn_fwd_kernel<HD, HC>), dim3(nsplit, heads, B), dim3(EFT), shm, stream, q, kv, T, L, heads, kps, part_acc,
-                     part_ml);
-  hipLaunchKernelGGL((extract_attn_reduce_kernel<HD, HC>), dim3(B * heads), dim3(TMAX), 0, stream, part_acc, part_ml, T, nsplit, heads, out,
-                     lse);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  const size_t shm = HD == 16 ? 0 : ExtractFwdLds<HD>{T}.bytes();
+  if (int rc = ad_launch<extract_attn_fwd_kernel<HD, HC>>(dim3(nsplit, heads, B), EFT, shm, stream, q, kv, T, L, heads, kps, part_acc, part_ml))
+    return rc;
+  return ad_launch<extract_attn_reduce_kernel<HD, HC>>(dim3(B * heads), TMAX, 0, stream, (const float*)part_acc, (const float*)part_ml, T, nsplit,
+                                                       heads, out, lse);
 }
 
 template <int HD, int HC, bool DET = false>
 int launch_extract_bwd(const float* q, const h16* kv, const float* out, const float* lse, const float* dout, int B, int T, int L, int heads,
                        float* dq, h16* dkv, hipStream_t stream) {
-  using Dm = AdDim<HD>;
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t shm = sizeof(float) * (2 * TMAX) + sizeof(h16) * ((size_t)2 * TBk * Dm::KP + 2 * HD * Dm::TPV + (size_t)(T + HD) * RSTR);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)extract_attn_bwd_kernel<HD, HC, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((extract_attn_bwd_kernel<HD, HC, DET>), dim3(cdiv(L, EBK * ETILES), heads, B), dim3(256), shm, stream, q, kv, out, lse, dout,
-                     T, L, heads, dq, dkv);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-
-// heads per LDS image of the attention-map kernels: all of them when that fits PROBS_LDS, else the largest group that does
-inline int probs_group(int heads, size_t per_head) {
-  const int g = (int)((size_t)PROBS_LDS / per_head);
-  return g < 1 ? 1 : g > heads ? heads : g;
+  return ad_launch<extract_attn_bwd_kernel<HD, HC, DET>>(dim3(cdiv(L, EBK * ETILES), heads, B), 256, ExtractBwdLds<HD>{T}.bytes(), stream, q, kv, out,
+                                                         lse, dout, T, L, heads, dq, dkv);
 }
 
 template <int HD, int HC>
 int launch_extract_probs(const float* q, const h16* kv, const float* lse, int B, int T, int L, int heads, float* w, hipStream_t stream) {
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t per_head = sizeof(float) * TBk + sizeof(h16) * (size_t)TBk * AdDim<HD>::KP;
-  const int G = HC ? HC : probs_group(heads, per_head);
-  const size_t shm = per_head * G;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)extract_attn_probs_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((extract_attn_probs_kernel<HD, HC>), dim3(cdiv(L, PBR), B), dim3(256), shm, stream, q, kv, lse, T, L, heads, G, w);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  const int G = HC ? HC : probs_group(heads, ExtractProbsLds<HD>{T, 1}.per_head());
+  return ad_launch<extract_attn_probs_kernel<HD, HC>>(dim3(cdiv(L, PBR), B), 256, ExtractProbsLds<HD>{T, G}.bytes(), stream, q, kv, lse, T, L, heads,
+                                                      G, w);
 }
 
 template <int HD, int HC>
 int launch_inject_probs(const h16* q, int rows_per_pass, int B, const float* k, const float* lse, int T, int heads, float* w,
                         hipStream_t stream) {
-  const int TBk = cdiv(T, 32) * 32;
-  const size_t per_head = sizeof(h16) * (size_t)TBk * AdDim<HD>::KP;
-  const int G = HC ? HC : probs_group(heads, per_head);
-  const size_t kimg = per_head * G, otile = sizeof(float) * (size_t)PBR * (T | 1);
-  const size_t shm = kimg > otile ? kimg : otile;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)inject_attn_probs_kernel<HD, HC>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((inject_attn_probs_kernel<HD, HC>), dim3(cdiv(rows_per_pass, PBR), B), dim3(256), shm, stream, q, rows_per_pass, k, lse,
-                     T, heads, G, w);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  const int G = HC ? HC : probs_group(heads, InjectProbsLds<HD>{T, 1}.per_head());
+  return ad_launch<inject_attn_probs_kernel<HD, HC>>(dim3(cdiv(rows_per_pass, PBR), B), 256, InjectProbsLds<HD>{T, G}.bytes(), stream, q,
+                                                     rows_per_pass, k, lse, T, heads, G, w);
 }
 
 // d: the softmax dropout (make_drop of the entry's MtDropout); inactive = the DROP = false kernel, which never reads it
 template <int HD, bool DROP>
 int launch_token_fwd_drop(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out, float* probs,
                           const DropArgs& d, hipStream_t stream) {
-  const int T4 = (T + 3) & ~3, S1 = ((T4 >> 2) & 1) ? T4 : T4 + 4;      // (mha_t4 / mha_s1 of the kernel)
-  const size_t shm = sizeof(float) * ((size_t)T * HD + (size_t)T4 * HD + (size_t)T * S1) + (DROP ? mha_keep_bytes(T) : 0);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_fwd_kernel<HD, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((token_mha_fwd_kernel<HD, DROP>), dim3(heads, B), dim3(512), shm, stream, q, k, v, T, E, heads, out, probs, d);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-template <int HD>
-int launch_token_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out, float* probs,
-                     const DropArgs& d, hipStream_t stream) {
-  return d.active() ? launch_token_fwd_drop<HD, true>(q, k, v, B, T, E, heads, out, probs, d, stream)
-                    : launch_token_fwd_drop<HD, false>(q, k, v, B, T, E, heads, out, probs, d, stream);
+  return ad_launch<token_mha_fwd_kernel<HD, DROP>>(dim3(heads, B), 512, TokenFwdLds<HD, DROP>{T}.bytes(), stream, q, k, v, T, E, heads, out, probs, d);
 }
 
 template <int HD, int FORM, bool DROP>
-void launch_token_bwd_form(size_t shm, const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
-                           int E, int heads, float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)token_mha_bwd_kernel<HD, FORM, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((token_mha_bwd_kernel<HD, FORM, DROP>), dim3(heads, B), dim3(512), shm, stream, q, k, v, probs, dout, T, E, heads, dq, dk,
-                     dv, d);
+int launch_token_bwd_form(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E,
+                          int heads, float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
+  return ad_launch<token_mha_bwd_kernel<HD, FORM, DROP>>(dim3(heads, B), 512, TokenBwdLds<HD, FORM, DROP>{T}.bytes(), stream, q, k, v, probs, dout, T,
+                                                         E, heads, dq, dk, dv, d);
 }
-
+// the first FORM whose images fit at this T (the T limits of the kernel's comment); FORM 2 fits at every T <= TMAX
 template <int HD, bool DROP>
 int launch_token_bwd_drop(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E,
                           int heads, float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
-  // FORM 0 while the four operand images and both T x T images (dS, P) fit (T <= 127 / 114 / 92 at HD = 16 / 32 / 64), FORM 1 while the
-  // operands and dS do (every T at 16 and 32, T <= 111 at 64), FORM 2 (V, dO, dS) beyond.  DROP: plus the keep-bit image (T <= 126 / 113 /
-  // 92, then T <= 110 at 64: the kernel's comment)
-  const size_t op = sizeof(float) * (size_t)T * HD, tt = sizeof(float) * (size_t)T * (T + 1), mk = DROP ? mha_keep_bytes(T) : 0;
-  if (4 * op + 2 * tt + mk <= (size_t)LDS_MAX)
-    launch_token_bwd_form<HD, 0, DROP>(4 * op + 2 * tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
-  else if (4 * op + tt + mk <= (size_t)LDS_MAX)
-    launch_token_bwd_form<HD, 1, DROP>(4 * op + tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
-  else
-    launch_token_bwd_form<HD, 2, DROP>(2 * op + tt + mk, q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-template <int HD>
-int launch_token_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T, int E, int heads,
-                     float* dq, float* dk, float* dv, const DropArgs& d, hipStream_t stream) {
-  return d.active() ? launch_token_bwd_drop<HD, true>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream)
-                    : launch_token_bwd_drop<HD, false>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  static_assert(TokenBwdLds<HD, 2, DROP>{TMAX}.bytes() <= (size_t)LDS_MAX, "token backward: FORM 2 at TMAX");
+  int rc = launch_token_bwd_form<HD, 0, DROP>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  if (rc == MT_ERR_UNSUPPORTED) rc = launch_token_bwd_form<HD, 1, DROP>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  if (rc == MT_ERR_UNSUPPORTED) rc = launch_token_bwd_form<HD, 2, DROP>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, stream);
+  return rc;
 }
 
+// the shape predicates of the entry points
 inline bool ad_heads_ok(int heads, int head_dim) { return heads >= 1 && head_dim >= 1 && heads <= 1024; }
+inline bool ad_head_dim_ok(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64; }
+inline bool inject_shape_ok(int M, int rows_per_pass, int T, int heads, int head_dim) {
+  return !(M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim));
+}
+inline bool extract_shape_ok(int B, int T, int L, int heads, int head_dim) {
+  return !(B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim));
+}
 
 }  // namespace
 
 extern "C" int mt_inject_attn_fwd_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* v, int T, int heads,
                                      int head_dim, mt_half* a, float* lse, mt_stream_t stream) {
-  if (!q || !k || !v || !a || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim))
-    return MT_ERR_BAD_ARG;
+  if (!q || !k || !v || !a || !inject_shape_ok(M, rows_per_pass, T, heads, head_dim)) return MT_ERR_BAD_ARG;
 #define AD_CALL(HD, HC) \
   launch_inject_fwd<HD, HC>((const h16*)q, rows_per_pass, M / rows_per_pass, k, v, T, heads, (h16*)a, lse, (hipStream_t)stream)
   AD_DISPATCH(heads, head_dim, AD_CALL);
@@ -1271,9 +1229,7 @@ extern "C" int mt_inject_attn_fwd(const mt_half* q, int M, int rows_per_pass, co
 // partials = dk slots [row blocks][B][T][E], then dv slots likewise; row blocks = cdiv(rows_per_pass, 512), E = heads * head_dim.
 // Rows t >= T of a slot do not exist.
 extern "C" long mt_inject_attn_bwd_hd_det_elems(int M, int rows_per_pass, int T, int heads, int head_dim) {
-  if (M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim) ||
-      (head_dim != 16 && head_dim != 32 && head_dim != 64))
-    return MT_ERR_BAD_ARG;
+  if (!inject_shape_ok(M, rows_per_pass, T, heads, head_dim) || !ad_head_dim_ok(head_dim)) return MT_ERR_BAD_ARG;
   return 2L * cdiv(rows_per_pass, IBR * ITILES) * (M / rows_per_pass) * T * heads * head_dim;
 }
 
@@ -1283,8 +1239,7 @@ extern "C" int mt_inject_attn_bwd_hd(const mt_half* q, const mt_half* a, const f
                                      const MtLaunchOpts* opt, mt_stream_t stream) {
   if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
   float* partials = mt_opt_partials(opt);
-  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 ||
-      T > TMAX || !ad_heads_ok(heads, head_dim))
+  if (!q || !a || !lse || !da || !k || !v || !dq || !dk || !dv || !inject_shape_ok(M, rows_per_pass, T, heads, head_dim))
     return MT_ERR_BAD_ARG;
   const int B = M / rows_per_pass, slots = cdiv(rows_per_pass, IBR * ITILES), E = heads * head_dim;
   const long slot = (long)B * T * E;
@@ -1315,8 +1270,7 @@ extern "C" int mt_inject_attn_bwd(const mt_half* q, const mt_half* a, const floa
 
 extern "C" int mt_extract_attn_fwd_hd(const float* q, const mt_half* kv, int B, int T, int L, int heads, int head_dim, float* out,
                                       float* lse, float* part_acc, float* part_ml, int nsplit, mt_stream_t stream) {
-  if (!q || !kv || !out || !lse || !part_acc || !part_ml || B < 1 || T < 1 || T > TMAX || L < 1 || nsplit < 1 ||
-      !ad_heads_ok(heads, head_dim))
+  if (!q || !kv || !out || !lse || !part_acc || !part_ml || nsplit < 1 || !extract_shape_ok(B, T, L, heads, head_dim))
     return MT_ERR_BAD_ARG;
   const int kps = cdiv(cdiv(L, nsplit), EKT) * EKT;
   if ((long)kps * (nsplit - 1) >= L && nsplit > 1) return MT_ERR_BAD_ARG;   // every split must own >= 1 key
@@ -1333,8 +1287,7 @@ extern "C" int mt_extract_attn_fwd(const float* q, const mt_half* kv, int B, int
 
 // partials = dq slots [key blocks][B][T][E], key blocks = cdiv(L, 512)
 extern "C" long mt_extract_attn_bwd_hd_det_elems(int B, int T, int L, int heads, int head_dim) {
-  if (B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim) || (head_dim != 16 && head_dim != 32 && head_dim != 64))
-    return MT_ERR_BAD_ARG;
+  if (!extract_shape_ok(B, T, L, heads, head_dim) || !ad_head_dim_ok(head_dim)) return MT_ERR_BAD_ARG;
   return (long)cdiv(L, EBK * ETILES) * B * T * heads * head_dim;
 }
 
@@ -1344,8 +1297,7 @@ extern "C" int mt_extract_attn_bwd_hd(const float* q, const mt_half* kv, const f
                                       mt_stream_t stream) {
   if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
   float* partials = mt_opt_partials(opt);
-  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim))
-    return MT_ERR_BAD_ARG;
+  if (!q || !kv || !out || !lse || !dout || !dq || !dkv || !extract_shape_ok(B, T, L, heads, head_dim)) return MT_ERR_BAD_ARG;
   if (partials) {
     const long need = mt_extract_attn_bwd_hd_det_elems(B, T, L, heads, head_dim);
     if (need < 0 || opt->partials_elems < need) return MT_ERR_BAD_ARG;
@@ -1372,25 +1324,28 @@ static bool mha_ptrs_ok(const float* const* ps, int n, int E) {
     if (!ps[i] || ((uintptr_t)ps[i] & 15)) return false;
   return (E & 3) == 0;
 }
-// head dim of the prompt self-attention: E / heads, one of 16 / 32 / 64 (0: none of them)
-static int mha_head_dim(int E, int heads) {
-  const int hd = E / heads;
-  return (hd == 16 || hd == 32 || hd == 64) ? hd : 0;
+// the shapes of the prompt self-attention entries, and its softmax dropout: element dropout only (no DropPath at this site), p in [0, 1)
+static bool mha_shape_ok(int B, int T, int E, int heads, const MtDropout* drop) {
+  return !(B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads) &&
+         (!drop || (drop->p >= 0.f && drop->p < 1.f && drop->path_p == 0.f));
 }
-// the softmax dropout of the _drop entries: element dropout only (no DropPath at this site), p in [0, 1)
-static bool mha_drop_ok(const MtDropout* drop) { return !drop || (drop->p >= 0.f && drop->p < 1.f && drop->path_p == 0.f); }
+// one instantiation per head dim E / heads in 16 / 32 / 64 and per form of the dropout d (active or not): CALL(HD, DROP) is the launcher's call
+#define MHA_DISPATCH(E, heads, d, CALL)                                             \
+  do {                                                                              \
+    const int hd__ = (E) / (heads);                                                 \
+    if (hd__ == 16) return (d).active() ? CALL(16, true) : CALL(16, false);         \
+    if (hd__ == 32) return (d).active() ? CALL(32, true) : CALL(32, false);         \
+    if (hd__ == 64) return (d).active() ? CALL(64, true) : CALL(64, false);         \
+    return MT_ERR_UNSUPPORTED;                                                      \
+  } while (0)
 extern "C" int mt_token_mha_fwd_drop(const float* q, const float* k, const float* v, int B, int T, int E, int heads, float* out,
                                      float* probs, const MtDropout* drop, mt_stream_t stream) {
   const float* ps[] = {q, k, v, out};
-  if (!mha_ptrs_ok(ps, 4, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads || !mha_drop_ok(drop))
-    return MT_ERR_BAD_ARG;
+  if (!mha_ptrs_ok(ps, 4, E) || !probs || !mha_shape_ok(B, T, E, heads, drop)) return MT_ERR_BAD_ARG;
   const DropArgs d = make_drop(drop);
-  switch (mha_head_dim(E, heads)) {
-    case 16: return launch_token_fwd<16>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
-    case 32: return launch_token_fwd<32>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
-    case 64: return launch_token_fwd<64>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream);
-    default: return MT_ERR_UNSUPPORTED;
-  }
+#define MHA_CALL(HD, DROP) launch_token_fwd_drop<HD, DROP>(q, k, v, B, T, E, heads, out, probs, d, (hipStream_t)stream)
+  MHA_DISPATCH(E, heads, d, MHA_CALL);
+#undef MHA_CALL
 }
 extern "C" int mt_token_mha_fwd(const float* q, const float* k, const float* v, int B, int T, int E, int heads,
                                 float* out, float* probs, mt_stream_t stream) {
@@ -1400,15 +1355,11 @@ extern "C" int mt_token_mha_fwd(const float* q, const float* k, const float* v, 
 extern "C" int mt_token_mha_bwd_drop(const float* q, const float* k, const float* v, const float* probs, const float* dout, int B, int T,
                                      int E, int heads, float* dq, float* dk, float* dv, const MtDropout* drop, mt_stream_t stream) {
   const float* ps[] = {q, k, v, dout, dq, dk, dv};
-  if (!mha_ptrs_ok(ps, 7, E) || !probs || B < 1 || T < 1 || T > TMAX || heads < 1 || E < 1 || E % heads || !mha_drop_ok(drop))
-    return MT_ERR_BAD_ARG;
+  if (!mha_ptrs_ok(ps, 7, E) || !probs || !mha_shape_ok(B, T, E, heads, drop)) return MT_ERR_BAD_ARG;
   const DropArgs d = make_drop(drop);
-  switch (mha_head_dim(E, heads)) {
-    case 16: return launch_token_bwd<16>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
-    case 32: return launch_token_bwd<32>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
-    case 64: return launch_token_bwd<64>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream);
-    default: return MT_ERR_UNSUPPORTED;
-  }
+#define MHA_CALL(HD, DROP) launch_token_bwd_drop<HD, DROP>(q, k, v, probs, dout, B, T, E, heads, dq, dk, dv, d, (hipStream_t)stream)
+  MHA_DISPATCH(E, heads, d, MHA_CALL);
+#undef MHA_CALL
 }
 extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, const float* probs, const float* dout,
                                 int B, int T, int E, int heads, float* dq, float* dk, float* dv, mt_stream_t stream) {
@@ -1417,7 +1368,7 @@ extern "C" int mt_token_mha_bwd(const float* q, const float* k, const float* v, 
 
 extern "C" int mt_extract_attn_probs_hd(const float* q, const mt_half* kv, const float* lse, int B, int T, int L, int heads, int head_dim,
                                         float* w, mt_stream_t stream) {
-  if (!q || !kv || !lse || !w || B < 1 || T < 1 || T > TMAX || L < 1 || !ad_heads_ok(heads, head_dim)) return MT_ERR_BAD_ARG;
+  if (!q || !kv || !lse || !w || !extract_shape_ok(B, T, L, heads, head_dim)) return MT_ERR_BAD_ARG;
 #define AD_CALL(HD, HC) launch_extract_probs<HD, HC>(q, (const h16*)kv, lse, B, T, L, heads, w, (hipStream_t)stream)
   AD_DISPATCH(heads, head_dim, AD_CALL);
 #undef AD_CALL
@@ -1430,8 +1381,7 @@ extern "C" int mt_extract_attn_probs(const float* q, const mt_half* kv, const fl
 
 extern "C" int mt_inject_attn_probs_hd(const mt_half* q, int M, int rows_per_pass, const float* k, const float* lse, int T, int heads,
                                        int head_dim, float* w, mt_stream_t stream) {
-  if (!q || !k || !lse || !w || M <= 0 || rows_per_pass <= 0 || M % rows_per_pass || T < 1 || T > TMAX || !ad_heads_ok(heads, head_dim))
-    return MT_ERR_BAD_ARG;
+  if (!q || !k || !lse || !w || !inject_shape_ok(M, rows_per_pass, T, heads, head_dim)) return MT_ERR_BAD_ARG;
 #define AD_CALL(HD, HC) \
   launch_inject_probs<HD, HC>((const h16*)q, rows_per_pass, M / rows_per_pass, k, lse, T, heads, (float*)w, (hipStream_t)stream)
   AD_DISPATCH(heads, head_dim, AD_CALL);

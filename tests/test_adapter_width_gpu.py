@@ -234,6 +234,56 @@ def test_maps_match_f64_recomputation_at_width(E, heads, T, L):
     assert float((wi.double().sum(-1) - 1).abs().max()) <= 1e-4
 
 
+def _tile_positions(n):
+    """Where a row can sit in a launch of n rows: lane 0, the last row of the first wave tile, the first row of the second wave tile,
+    the last row of the first workgroup, the first row of the second workgroup, the last row (the tail mask)."""
+    return sorted({r for r in (0, 31, 32, 127, 128, n - 1) if r < n})
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.float16 else torch.int32)
+
+
+@pytest.mark.parametrize("T", [33, 65])
+@pytest.mark.parametrize("E,heads", [(192, 12), (192, 6), (192, 3)])
+def test_adapter_rows_do_not_depend_on_their_tile(E, heads, T):
+    """A patch row's injector output, LSE and map row, and a key's column of the extractor map, are functions of the row's own operand
+    and of the token-side LDS image only: the same row gives the same BITS as the only row of a launch and as row 0 / 31 / 32 / 127 /
+    128 / last of launches of 127, 129 and 513 rows (every lane position, wave tile and workgroup, and the tail masks, of the shared
+    accumulator-row, tile-store and staging helpers).  The reference is the 1-row launch.  Holds for the library before the kernels'
+    stages were stated once as well (run there through MODALTUNE_HIP_LIB: 6 passed), no exception to record."""
+    _gpu()
+    hd = E // heads
+    g = torch.Generator(device=DEV).manual_seed(100 * T + heads)
+    k, v = torch.randn(1, T, E, device=DEV, generator=g), torch.randn(1, T, E, device=DEV, generator=g)
+    qrow = torch.randn(E, device=DEV, generator=g).half()
+    tq = torch.randn(1, T, E, device=DEV, generator=g)                           # the extractor's tokens, their lse fixed and passed in
+    tlse = 3.0 + torch.rand(1, T, heads, device=DEV, generator=g)
+    kvrow = torch.randn(2 * E, device=DEV, generator=g).half()
+    ref = None
+    for n in (1, 127, 129, 513):
+        pos = _tile_positions(n)
+        q = torch.randn(n, E, device=DEV, generator=g).half()
+        kv = torch.randn(n, 2 * E, device=DEV, generator=g).half()
+        q[pos], kv[pos] = qrow, kvrow
+        a = torch.full((n, E), float("nan"), dtype=torch.float16, device=DEV)
+        lse = torch.full((n, heads), float("nan"), device=DEV)
+        wi = torch.full((n, T), float("nan"), device=DEV)
+        we = torch.full((1, T, n), float("nan"), device=DEV)
+        ops.inject_attn_fwd(q, k, v, a, n, n, T, lse=lse, heads=heads, head_dim=hd)
+        ops.inject_attn_probs(q, k, lse, wi, n, n, T, heads=heads, head_dim=hd)
+        ops.extract_attn_probs(tq, kv, tlse, we, 1, T, n, heads=heads, head_dim=hd)
+        torch.cuda.synchronize()
+        for t in (a, lse, wi, we):
+            assert not bool(torch.isnan(t).any()), "an element was not written"
+        if ref is None:
+            ref = [_bits(x).clone() for x in (a[0], lse[0], wi[0], we[0, :, 0])]
+        for r in pos:
+            got = (a[r], lse[r], wi[r], we[0, :, r])
+            for name, x, y in zip(("a", "lse", "inject map", "extract map"), got, ref):
+                assert torch.equal(_bits(x), y), (name, n, r)
+
+
 # ---------------------------------------------------------------- 6. train step against the reference goldens
 @pytest.mark.parametrize("tag", WIDTH_TAGS)
 def test_train_step_matches_reference_golden_at_width(golden_dir, tag):
