@@ -51,7 +51,8 @@ typedef struct {
 } MtLaunchOpts;
 
 /* major * 100 + minor * 10.  3.0: the optional inputs of a launcher travel in MtLaunchOpts; the suffixed twin entries (_eps, _det, _grid,
- * _live) of 2.x are gone, so a 2.x caller does not link against this library.  3.1: + mt_token_mha_fwd_drop / _bwd_drop. */
+ * _live) of 2.x are gone, so a 2.x caller does not link against this library.  3.1: + mt_token_mha_fwd_drop / _bwd_drop.  3.2: + mt_patch_points_fwd / mt_patch_ig_accumulate.
+ * 3.3: + mt_checksum64.  3.4: + mt_adamw_step_groups. */
 int mt_version(void);
 const char* mt_status_string(int status);
 /* Build provenance: sha256 (hex) over the kernel sources, this header and the compiler flags the library was built from
@@ -584,6 +585,24 @@ int mt_adamw_step(float* p, const float* g, float* m, float* v, long n, double l
                   const float* scale, int* found_inf, const float* lr_dev /* device scalar: the schedule's current
                   learning rate (overrides lr; a captured graph replays with whatever it holds -- the reference steps
                   GradualWarmupScheduler + CosineAnnealingLR every epoch, TM:151-154,242) or NULL */, mt_stream_t stream);
+/* mt_adamw_step with PARAMETER GROUPS: the flat buffer is a run of segments (neighbouring tensors of one group), and a segment's group
+ * supplies two values; betas, eps, the bias corrections, grad_mult / *scale and the found_inf skip are shared.  Per element the
+ * arithmetic is mt_adamw_step's with
+ *   lr_g    = (float)((double)lr_f32 * lr_mult)           lr_f32 = *lr_dev or (float)lr; rounded once: lr_mult == 1.0 gives the base bits
+ *   decay_g = (float)(1.0 - (double)lr_g * weight_decay)
+ * so one launch equals mt_adamw_step over every segment alone with lr = lr_g and the group's weight_decay, bit for bit.
+ * `p` is the piece [index_base, index_base + n) of a 16-byte aligned flat buffer (pieces compose, as in mt_checksum64): p, g, m, v are
+ * 4-byte aligned and lie in their buffers as index_base says (address / 4 = index_base mod 4), else MT_ERR_BAD_ARG.  Segment s covers the
+ * ABSOLUTE indices [seg_end[s - 1], seg_end[s]), seg_end[-1] = 0; the ends are ascending multiples of 4 (slot padding lies inside a
+ * segment and stays +0), the last one at or behind index_base + n.  seg_end / seg_group are DEVICE tables of nseg entries, group ids
+ * < ngroups; `groups` is a HOST array of ngroups entries that travels as kernel arguments.  ngroups outside 1 .. MT_ADAM_MAX_GROUPS:
+ * MT_ERR_UNSUPPORTED.  lr_mult = 0 with weight_decay = 0 holds a group's parameter bits still while its moments keep updating. */
+#define MT_ADAM_MAX_GROUPS 16
+typedef struct { double lr_mult; double weight_decay; } MtAdamGroup;
+int mt_adamw_step_groups(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                         const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr, double beta1,
+                         double beta2, double eps, int step_count, const int* step_dev, float grad_mult, const float* scale,
+                         int* found_inf, const float* lr_dev, mt_stream_t stream);
 /* GradScaler.update on device (TM:237): *found_inf ? scale *= backoff : (every `interval` clean steps scale *= growth,
  * unless the product is not finite: then the scale stays, as in torch._amp_update_scale_); *found_inf is cleared */
 int mt_scaler_update(float* scale, int* growth_tracker, int* found_inf, int* step_dev /* ++ on a clean step, or NULL */,

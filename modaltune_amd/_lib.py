@@ -34,6 +34,11 @@ class MtLaunchOpts(C.Structure):
     _fields_ = [("eps", F), ("live", P), ("live_rows", I), ("partials", P), ("partials_elems", L), ("grid_wgs", I)]
 
 
+class MtAdamGroup(C.Structure):
+    _fields_ = [("lr_mult", D), ("weight_decay", D)]
+
+
+MT_ADAM_MAX_GROUPS = 16
 MT_SGEMM_MAX = 3
 
 
@@ -146,6 +151,7 @@ SIGNATURES = {
     "mt_l2norm_rows": [P, P, I, I, P],
     "mt_distill_loss": [P, P, I, I, F, P, P, P, P],
     "mt_adamw_step": [P, P, P, P, L, D, D, D, D, D, I, P, F, P, P, P, P],
+    "mt_adamw_step_groups": [P, P, P, P, L, L, P, P, I, C.POINTER(MtAdamGroup), I, D, D, D, D, I, P, F, P, P, P, P],
     "mt_scaler_update": [P, P, P, P, F, F, I, P],
     "mt_check_finite": [P, L, P, P],
     "mt_grad_sumsq": [P, L, P, L, P, P, P],

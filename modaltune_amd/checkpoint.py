@@ -8,6 +8,9 @@ read back with `torch.load(..., weights_only=True)`):
     model       {key: tensor}: the trainable tensors under the reference's state_dict names (include_frozen: every tensor)
     optimizer   torch.optim.AdamW.state_dict() format: state[i] = {"step", "exp_avg", "exp_avg_sq"} of the i-th TRAINABLE tensor in
                 ParamStore.specs order (= the order filter(requires_grad, model.parameters()) gives the reference trainer), one param group
+                -- or, with TrainStep(param_groups=...), one torch param group per resolved group: `lr` = base lr x lr_mult,
+                its `weight_decay`, `params` = the indices of its tensors, and two extra keys torch carries along: `lr_mult`
+                and `names` (the tensors' names; torch renumbers `params` on its way through an optimiser, the names stay)
     scaler      torch.amp.GradScaler.state_dict() format
     rng         int32[4]: the Philox seed / step counter of the dropout masks;  stochastic: whether the masks were on
     lr          the learning rate on the device (the scheduler's last set_lr)
@@ -119,9 +122,11 @@ def _flat_from(tensors: Dict[str, torch.Tensor], slots: Dict[str, tuple], n_flat
 
 # ------------------------------------------------------------------------------------------------ optimiser
 def pack_optimizer(m_flat: torch.Tensor, v_flat: torch.Tensor, step: int, slots: Dict[str, tuple], trainable_names: Sequence[str],
-                   hyper: dict) -> dict:
+                   hyper: dict, groups: Optional[Sequence[dict]] = None) -> dict:
     """The flat AdamW moments as a torch.optim.AdamW.state_dict(): state[i] belongs to trainable_names[i], exp_avg / exp_avg_sq keep the
-    parameter's shape, `step` is torch's fp32 scalar; hyper: lr, betas, eps, weight_decay.  Slot padding is not stored."""
+    parameter's shape, `step` is torch's fp32 scalar; hyper: lr, betas, eps, weight_decay.  Slot padding is not stored.
+    groups (TrainStep.param_groups: [{"names", "lr_mult", "weight_decay"}]): one torch param group each -- lr = hyper lr x lr_mult, the
+    group's weight_decay, params = the indices of its tensors, plus the keys `lr_mult` and `names`.  None: the one group as ever."""
     m_flat, v_flat = m_flat.detach().to("cpu"), v_flat.detach().to("cpu")
     state = {}
     for i, k in enumerate(trainable_names):
@@ -132,22 +137,50 @@ def pack_optimizer(m_flat: torch.Tensor, v_flat: torch.Tensor, step: int, slots:
     group = {"lr": float(hyper["lr"]), "betas": (float(b1), float(b2)), "eps": float(hyper["eps"]),
              "weight_decay": float(hyper["weight_decay"]), "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
              "differentiable": False, "fused": None, "decoupled_weight_decay": True, "params": list(range(len(trainable_names)))}
-    return {"state": state, "param_groups": [group]}
+    if groups is None:
+        return {"state": state, "param_groups": [group]}
+    index = {k: i for i, k in enumerate(trainable_names)}
+    listed = [k for g in groups for k in g["names"]]
+    if sorted(listed) != sorted(trainable_names):
+        raise ValueError(f"optimizer: the groups list {len(listed)} tensors, this engine trains {len(trainable_names)} (every trainable "
+                         "tensor belongs to exactly one group)")
+    out = []
+    for g in groups:
+        out.append({**group, "lr": float(hyper["lr"]) * float(g["lr_mult"]), "weight_decay": float(g["weight_decay"]),
+                    "params": [index[k] for k in g["names"]], "lr_mult": float(g["lr_mult"]), "names": list(g["names"])})
+    return {"state": state, "param_groups": out}
 
 
-def unpack_optimizer(opt_sd: dict, slots: Dict[str, tuple], trainable_names: Sequence[str], n_flat: int):
+def unpack_optimizer(opt_sd: dict, slots: Dict[str, tuple], trainable_names: Sequence[str], n_flat: int, base_lr: Optional[float] = None):
     """pack_optimizer's inverse, for any torch.optim.AdamW.state_dict() over the trainable tensors in order: (m_flat, v_flat, step,
     hyper) with zero slot padding.  An optimiser that never stepped (empty state) gives zero moments and step 0.  The per-parameter
-    `step` entries map to ONE device counter: they must agree."""
+    `step` entries map to ONE device counter: they must agree.
+    A GROUPED dict comes back with hyper["groups"] = [{"names", "lr_mult", "weight_decay"}] and hyper["lr"] the BASE rate.  Grouped is
+    said by the dict's KEYS before its values: a group with an `lr_mult` other than 1, or more than one group of which any carries
+    `lr_mult` or `names` (what pack_optimizer and the optim helpers write), or -- a plain torch dict -- groups whose lr / weight_decay
+    differ.  The written lr = base x lr_mult alone cannot say it: at base 0 (a warm-up's first epoch), with one multiplier everywhere
+    or with a single frozen group the products of a grouped step are equal.  The base: `base_lr` (a checkpoint's `lr`), else the first
+    group's lr / lr_mult (exact for lr_mult 1, the default group; for another multiplier the quotient may be one ulp off the double
+    that was multiplied -- a full checkpoint carries `lr` and does not depend on it), else the first group's lr; a group without an
+    `lr_mult` key (the dict came from a torch optimiser) takes lr / base.  Which tensor an entry of `params` is: the group's
+    `names` (pack_optimizer, optim.no_decay_groups and optim.groups_by_name write them, torch carries them through) -- without names
+    the entries of all groups in order are the trainable tensors in order, as for one group.  A uniform dict: the 4-tuple as ever."""
     if "state" not in opt_sd or "param_groups" not in opt_sd:
         raise KeyError("optimizer: `state` / `param_groups` missing (not a torch.optim.AdamW.state_dict())")
-    ids = [i for g in opt_sd["param_groups"] for i in g["params"]]
+    pgs = opt_sd["param_groups"]
+    ids = [i for g in pgs for i in g["params"]]
     if len(ids) != len(trainable_names):
         raise ValueError(f"optimizer: {len(ids)} parameters in its groups, this engine trains {len(trainable_names)} tensors")
+    if all("names" in g for g in pgs):
+        order = [k for g in pgs for k in g["names"]]
+        if len(order) != len(ids) or any(len(g["names"]) != len(g["params"]) for g in pgs) or sorted(order) != sorted(trainable_names):
+            raise ValueError("optimizer: the `names` of its param groups are not this engine's trainable tensors, one entry of `params` each")
+    else:
+        order = list(trainable_names)
     state = opt_sd["state"]
     m, v = torch.zeros(n_flat, dtype=torch.float32), torch.zeros(n_flat, dtype=torch.float32)
     steps = {}
-    for k, i in zip(trainable_names, ids):
+    for k, i in zip(order, ids):
         s = state.get(i, state.get(str(i)))
         if s is None or "exp_avg" not in s:
             continue
@@ -166,12 +199,33 @@ def unpack_optimizer(opt_sd: dict, slots: Dict[str, tuple], trainable_names: Seq
         hi = max(steps, key=steps.get)
         raise ValueError(f"optimizer: the per-parameter `step` entries disagree ({lo}: {steps[lo]}, {hi}: {steps[hi]}); the fused step "
                          "keeps one count for all tensors")
-    g0 = opt_sd["param_groups"][0]
-    for g in opt_sd["param_groups"][1:]:
-        if any(g[key] != g0[key] for key in ("lr", "betas", "eps", "weight_decay")):
-            raise ValueError("optimizer: param groups with different hyper-parameters; the fused step has one set")
+    g0 = pgs[0]
+    for g in pgs[1:]:
+        if any(tuple(g[key]) != tuple(g0[key]) if key == "betas" else g[key] != g0[key] for key in ("betas", "eps")):
+            raise ValueError("optimizer: param groups with different betas / eps; the fused step shares them among its groups (only lr "
+                             "and weight_decay are per group)")
     hyper = {"lr": float(g0["lr"]), "betas": (float(g0["betas"][0]), float(g0["betas"][1])), "eps": float(g0["eps"]),
              "weight_decay": float(g0["weight_decay"])}
+    keyed = any(float(g.get("lr_mult", 1.0)) != 1.0 for g in pgs) or (len(pgs) > 1 and any("lr_mult" in g or "names" in g for g in pgs))
+    if keyed or any(g[key] != g0[key] for g in pgs[1:] for key in ("lr", "weight_decay")):
+        if len(pgs) > 16:
+            raise ValueError(f"optimizer: {len(pgs)} param groups of their own, the fused step carries at most 16")
+        if base_lr is None:
+            lm0 = float(g0.get("lr_mult", 1.0))
+            base_lr = float(g0["lr"]) / lm0 if lm0 != 0.0 else float(g0["lr"])
+        base_lr = float(base_lr)
+        groups, pos = [], 0
+        for g in pgs:
+            if "lr_mult" in g:
+                lm = float(g["lr_mult"])
+            elif base_lr != 0.0:
+                lm = float(g["lr"]) / base_lr
+            else:
+                raise ValueError("optimizer: param groups with different lr and no `lr_mult` keys, and the base learning rate is 0: the "
+                                 "groups' multipliers lr / base are undefined (give the first group a non-zero lr, or save `lr_mult`)")
+            groups.append({"names": order[pos:pos + len(g["params"])], "lr_mult": lm, "weight_decay": float(g["weight_decay"])})
+            pos += len(g["params"])
+        hyper["lr"], hyper["groups"] = base_lr, groups
     return m, v, (next(iter(steps.values())) if steps else 0), hyper
 
 
@@ -229,7 +283,7 @@ def flat_buffers(sd: dict, slots: Dict[str, tuple], n_flat: int):
     """(flat, m, v, step, hyper) of a checkpoint dict as zero-padded CPU buffers in the engine's layout."""
     names = list(slots)
     flat = _flat_from(sd["model"], slots, n_flat, "model")
-    m, v, step, hyper = unpack_optimizer(sd["optimizer"], slots, names, n_flat)
+    m, v, step, hyper = unpack_optimizer(sd["optimizer"], slots, names, n_flat, base_lr=sd["lr"] if "format" in sd else None)
     return flat, m, v, step, hyper
 
 

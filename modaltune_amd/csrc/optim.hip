@@ -82,6 +82,121 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// adamw_kernel with PARAMETER GROUPS: the flat buffer is a run of segments (tensors of one group that lie next to each other), a
+// segment's group supplies lr_mult and weight_decay; everything else -- betas, eps, bias corrections, grad_mult / *scale, the found_inf
+// skip -- is shared.  Per element the arithmetic is adamw_kernel's, expression for expression (adamw_elem below).
+//   lr_g = (float)((double)lr_f32 * lr_mult)  (rounded once: lr_mult == 1.0 gives the base bits),  decay_g = (float)(1 - (double)lr_g * wd_g)
+// Indices are ABSOLUTE (index_base + i: pieces of one buffer compose as in checksum64_partials_kernel).  Segment ends are multiples of
+// 4 and a float4 starts on an absolute multiple of 4, so a vector never straddles two segments: one lookup per vector at most.  Every
+// workgroup owns a CONTIGUOUS range of vectors (whole 256-vector rows); a thread walks it in steps of 256 vectors, two vectors in flight, finds the segment of its first vector by
+// one binary search and from then on only moves forward, keeping the segment's end and its two values in registers -- a vector
+// inside the same segment costs one compare, no memory read.  The group table travels as kernel arguments (no upload).  Workgroup 0
+// takes the `head` scalars in front of the first vector and the tail behind the last (grad_sumsq_partials_kernel's form).  No LDS, no
+// atomics.
+constexpr int ADAMG_THREADS = 256, ADAMG_MAX_WGS = 8192, ADAMG_MAX_GROUPS = MT_ADAM_MAX_GROUPS;
+static_assert((ADAMG_MAX_GROUPS & (ADAMG_MAX_GROUPS - 1)) == 0, "group ids are masked into the table");
+struct AdamGroupTab { double lr_mult[ADAMG_MAX_GROUPS]; double wd[ADAMG_MAX_GROUPS]; };
+
+struct AdamShared { float b1, b2, omb1, omb2, eps, bc1, bc2s, inv_scale; };
+
+// adamw_kernel's loop body is written as plain expressions and compiled under the build's default -ffp-contract=fast, which fuses ONE
+// of them: m = fma(1 - beta1, g, beta1 * m); the two products of v are rounded and then added, p * decay and the quotient are
+// rounded and then subtracted.  Which expressions a compiler fuses depends on the code around them (the float4 form fused v as
+// well), so the roundings are spelled out here: contraction off, the one FMA explicit.  tests/test_adamw_groups_gpu.py holds the two
+// kernels to the same bits.
+MT_DEVINL void adamw_elem(float& p, float g, float& m, float& v, float lr, float decay, const AdamShared& c) {
+#pragma clang fp contract(off)
+  const float gi = g * c.inv_scale;
+  float pi = p * decay;
+  const float mi = fmaf(c.omb1, gi, c.b1 * m);
+  const float vi = c.b2 * v + (c.omb2 * gi) * gi;
+  const float step = (lr / c.bc1) * mi;
+  const float den = sqrtf(vi) / c.bc2s + c.eps;
+  pi = pi - step / den;
+  p = pi; m = mi; v = vi;
+}
+
+// the segment of absolute index a: the first s with a < seg_end[s] (an index behind the last end stays in the last segment)
+MT_DEVINL int adamg_find(const int* __restrict__ seg_end, int nseg, long a) {
+  int lo = 0, hi = nseg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a < (long)seg_end[mid]) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+MT_DEVINL void adamg_values(const AdamGroupTab& tab, const unsigned char* __restrict__ seg_group, int s, float lr, float& lr_g,
+                            float& decay_g) {
+  const int gid = (int)seg_group[s] & (ADAMG_MAX_GROUPS - 1);
+  lr_g = (float)((double)lr * tab.lr_mult[gid]);
+  decay_g = (float)(1.0 - (double)lr_g * tab.wd[gid]);
+}
+
+__global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                     float* __restrict__ v, long n, long base, int head, long nvec, long per,
+                                                                     const int* __restrict__ seg_end,
+                                                                     const unsigned char* __restrict__ seg_group, int nseg,
+                                                                     AdamGroupTab tab, float lr, float b1, float b2, float omb1, float omb2,
+                                                                     float eps, float bc1, float bc2s, double b1d, double b2d, float grad_mult,
+                                                                     const float* __restrict__ scale, const int* __restrict__ found_inf,
+                                                                     const int* __restrict__ step_dev, const float* __restrict__ lr_dev) {
+  if (found_inf && *found_inf) return;
+  if (lr_dev) lr = *lr_dev;
+  if (step_dev) {                            // (adamw_kernel: the bias corrections in double from the device's step count)
+    const double st = (double)(*step_dev + 1);
+    bc1 = (float)(1.0 - pow(b1d, st));
+    bc2s = (float)sqrt(1.0 - pow(b2d, st));
+  }
+  const AdamShared c = {b1, b2, omb1, omb2, eps, bc1, bc2s, grad_mult * (scale ? 1.0f / *scale : 1.0f)};
+  const int tid = threadIdx.x;
+  const long vbase = base + head;            // absolute index of the first element of vector 0 (a multiple of 4: the launcher checked)
+  f32x4* __restrict__ pv = reinterpret_cast<f32x4*>(p + head);
+  const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
+  f32x4* __restrict__ mv = reinterpret_cast<f32x4*>(m + head);
+  f32x4* __restrict__ vv = reinterpret_cast<f32x4*>(v + head);
+  const long v0 = (long)blockIdx.x * per, v1 = v0 + per < nvec ? v0 + per : nvec;      // (per: a multiple of the workgroup size)
+  long i = v0 + tid;
+  if (i < v1) {
+    int s = adamg_find(seg_end, nseg, vbase + 4 * i);
+    long end = (long)seg_end[s];
+    float lr_g, decay_g;
+    adamg_values(tab, seg_group, s, lr, lr_g, decay_g);
+    auto update = [&](long iv, f32x4 p4, f32x4 g4, f32x4 m4, f32x4 v4) {
+      const long a = vbase + 4 * iv;
+      if (a >= end && s + 1 < nseg) {        // (forward only; behind the last end: the last segment)
+        do { ++s; end = (long)seg_end[s]; } while (a >= end && s + 1 < nseg);
+        adamg_values(tab, seg_group, s, lr, lr_g, decay_g);
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = p4[e], me = m4[e], ve = v4[e];
+        adamw_elem(pe, g4[e], me, ve, lr_g, decay_g, c);
+        p4[e] = pe; m4[e] = me; v4[e] = ve;
+      }
+      pv[iv] = p4; mv[iv] = m4; vv[iv] = v4;
+    };
+    for (; i + ADAMG_THREADS < v1; i += 2 * ADAMG_THREADS) {      // two vectors per thread: eight 16-byte loads in flight
+      const long k = i + ADAMG_THREADS;
+      const f32x4 pa = pv[i], ga = gv[i], ma = mv[i], va = vv[i], pb = pv[k], gb = gv[k], mb = mv[k], vb = vv[k];
+      update(i, pa, ga, ma, va);
+      update(k, pb, gb, mb, vb);
+    }
+    if (i < v1) update(i, pv[i], gv[i], mv[i], vv[i]);
+  }
+  if (blockIdx.x == 0) {
+    const long tail0 = head + 4 * nvec;
+    long j = -1;
+    if (tid < head) j = tid;
+    else if (tid >= 4 && tail0 + (tid - 4) < n) j = tail0 + (tid - 4);      // (head <= 3, n - tail0 <= 3: threads 0..2 and 4..6)
+    if (j >= 0) {
+      float lr_g, decay_g;
+      adamg_values(tab, seg_group, adamg_find(seg_end, nseg, base + j), lr, lr_g, decay_g);
+      adamw_elem(p[j], g[j], m[j], v[j], lr_g, decay_g, c);
+    }
+  }
+}
+
 __global__ void check_finite_kernel(const float* __restrict__ g, long n, int* __restrict__ found_inf) {
   bool bad = false;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
@@ -417,6 +532,42 @@ extern "C" int mt_adamw_step(float* p, const float* g, float* m, float* v, long 
   return MT_OK;
 }
 
+extern "C" int mt_adamw_step_groups(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                                    const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr,
+                                    double beta1, double beta2, double eps, int step_count, const int* step_dev, float grad_mult,
+                                    const float* scale, int* found_inf, const float* lr_dev, mt_stream_t stream) {
+  if (!p || !g || !m || !v || !seg_end || !seg_group || !groups || nseg < 1 || n < 1 || index_base < 0 || (step_count < 1 && !step_dev))
+    return MT_ERR_BAD_ARG;
+  if (ngroups < 1 || ngroups > MT_ADAM_MAX_GROUPS) return MT_ERR_UNSUPPORTED;
+  // a float4 starts on an absolute multiple of 4 AND on a 16-byte address, in all four buffers: the piece must lie in its buffer as
+  // index_base says (p = flat + index_base with a 16-byte aligned flat)
+  const uintptr_t want = (uintptr_t)(index_base & 3);
+  for (const void* q : {(const void*)p, (const void*)g, (const void*)m, (const void*)v})
+    if (((uintptr_t)q & 3) || (((uintptr_t)q >> 2) & 3) != want) return MT_ERR_BAD_ARG;
+  AdamGroupTab tab;
+  for (int i = 0; i < MT_ADAM_MAX_GROUPS; ++i) {
+    tab.lr_mult[i] = groups[i < ngroups ? i : 0].lr_mult;
+    tab.wd[i] = groups[i < ngroups ? i : 0].weight_decay;
+  }
+  if (step_count < 1) step_count = 1;
+  const float bc1 = (float)(1.0 - pow(beta1, (double)step_count));
+  const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step_count));
+  long head = (long)((4 - (index_base & 3)) & 3);
+  if (head > n) head = n;
+  const long nvec = (n - head) / 4;
+  // a workgroup's contiguous range: a whole number of workgroup-wide rows (no partly idle last row), at least two (the loop's two
+  // vectors in flight), and as many more as the cap on the workgroups asks for; the grid covers nvec with ranges of that size
+  long rows = (nvec + (long)ADAMG_THREADS * ADAMG_MAX_WGS - 1) / ((long)ADAMG_THREADS * ADAMG_MAX_WGS);
+  if (rows < 2) rows = 2;
+  const long per = rows * ADAMG_THREADS;
+  const int grid = (int)(nvec > 0 ? (nvec + per - 1) / per : 1);
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid), dim3(ADAMG_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, index_base, (int)head,
+                     nvec, per, seg_end, seg_group, nseg, tab, (float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                     (float)eps, bc1, bc2s, beta1, beta2, grad_mult, scale, (const int*)found_inf, step_dev, lr_dev);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
 extern "C" int mt_check_finite(const float* g, long n, int* found_inf, mt_stream_t stream) {
   if (!g || !found_inf || n <= 0) return MT_ERR_BAD_ARG;
   const int grid = (int)((n + 1023) / 1024 > 2048 ? 2048 : (n + 1023) / 1024);
@@ -530,7 +681,7 @@ extern "C" int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_st
   return MT_OK;
 }
 
-extern "C" int mt_version(void) { return 330; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64; the binary itself is identified by mt_build_id(), not by this number)
+extern "C" int mt_version(void) { return 340; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64, 3.4: mt_adamw_step_groups; the binary itself is identified by mt_build_id(), not by this number)
 
 extern "C" const char* mt_status_string(int status) {
   switch (status) {

@@ -13,16 +13,148 @@ same layout, so the whole update is one `mt_adamw_step` launch (csrc/optim.hip) 
 
 It IS a `torch.optim.AdamW` (schedulers, `state_dict()`, `zero_grad()`, param groups behave as before).  Gradients that are not
 views of one flat buffer (autograd cloned them, a DDP reducer owns them) are gathered by one multi-tensor copy first; whenever the
-fused precondition does not hold at all -- parameters of some other module, a parameter without a gradient, amsgrad / maximize /
-per-group hyper-parameters that differ -- the step is torch's own, on the same state.
+fused precondition does not hold at all -- parameters of some other module, a parameter without a gradient, amsgrad / maximize,
+param groups that differ in betas or eps, more than 16 groups -- the step is torch's own, on the same state.
+
+Param groups may differ in `lr` and `weight_decay` (no decay on biases and LayerNorm affines, a smaller rate for the gene encoder, a
+sub-module held still): the step is then ONE `mt_adamw_step_groups` launch, which reads each tensor's two values from a segment table
+(segment_table below) -- `no_decay_groups` and `groups_by_name` build such group lists for any optimiser.
 """
 from __future__ import annotations
 
-from typing import List, Optional
+import re
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
+
+
+MAX_GROUPS = 16                # include/modaltune_hip.h: MT_ADAM_MAX_GROUPS
+NO_DECAY_KINDS = ("b", "lnb", "lnw", "gamma", "tok")      # synth.param_specs kinds that conventionally take no weight decay
+_TOKEN_PARAMS = ("gene_pe", "gene_cls")
+
+
+# ------------------------------------------------------------------------------------------------ parameter groups (host only)
+def segment_table(entries: Sequence[Tuple[int, int, int]], max_groups: int = MAX_GROUPS) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The table mt_adamw_step_groups reads, as CPU tensors (seg_end int32, seg_group uint8), from [(offset, numel, group)] of the
+    tensors of one flat buffer in address order (offsets in elements from the buffer's 16-byte aligned start).  A segment is a run of
+    neighbouring tensors of one group; it ends where the next segment's first tensor starts (the slot padding behind a tensor belongs
+    to it), the last one at the end of the last slot.  Raises when a tensor does not start on a 16-byte slot or overlaps the one before
+    it, when a group id lies outside 0 .. max_groups - 1, and for more than max_groups distinct groups."""
+    if not entries:
+        raise ValueError("segment_table: no tensors")
+    ids = sorted({int(g) for _, _, g in entries})
+    if len(ids) > max_groups:
+        raise ValueError(f"segment_table: {len(ids)} parameter groups, the fused step carries at most {max_groups}")
+    if ids[0] < 0 or ids[-1] >= max_groups:
+        raise ValueError(f"segment_table: group ids must lie in 0 .. {max_groups - 1} (got {ids[0]} .. {ids[-1]})")
+    ends, groups, cur = [], [], 0
+    for i, (o, n, g) in enumerate(entries):
+        o, n, g = int(o), int(n), int(g)
+        if o % 4 or n < 1 or o < cur:
+            raise ValueError(f"segment_table: tensor {i} (offset {o}, {n} elements) does not start on a 16-byte slot behind the tensor "
+                             f"before it (which ends at {cur})")
+        if groups and groups[-1] == g:
+            ends.pop(); groups.pop()          # the same group as its neighbour: one segment
+        elif ends:
+            ends[-1] = o                      # the segment before ends where this tensor starts
+        cur = o + n
+        ends.append((cur + 3) // 4 * 4)
+        groups.append(g)
+    if ends[-1] >= 2 ** 31:
+        raise ValueError(f"segment_table: the buffer ends at element {ends[-1]}, the table holds 32-bit indices")
+    return torch.tensor(ends, dtype=torch.int32), torch.tensor(groups, dtype=torch.uint8)
+
+
+def resolve_param_groups(named_kinds: Sequence[Tuple[str, str]], rules: Optional[Sequence[dict]], weight_decay: float):
+    """TrainStep(param_groups=rules): rules are {"match": regex on the state_dict name and / or "kinds": (...), "lr_mult": 1.0,
+    "weight_decay": <the default>}; the first rule that matches a tensor takes it (`match` is re.search; with both keys both must hold),
+    unmatched tensors form the default group (lr_mult 1, `weight_decay`).  named_kinds: [(name, kind)] of the trainable tensors in
+    buffer order.  Returns (groups, group_of): groups = [{"names", "lr_mult", "weight_decay"}] -- the default group first when it
+    has tensors, then the rules in order -- and {name: index into groups}.  A rule that matches nothing, an unknown rule key and more
+    than MAX_GROUPS groups raise."""
+    rules = list(rules or [])
+    compiled = []
+    for i, r in enumerate(rules):
+        unknown = set(r) - {"match", "kinds", "lr_mult", "weight_decay"}
+        if unknown or not ("match" in r or "kinds" in r):
+            raise ValueError(f"param_groups[{i}]: needs `match` and / or `kinds`; unknown keys {sorted(unknown)}")
+        kinds = r.get("kinds")
+        kinds = None if kinds is None else ((kinds,) if isinstance(kinds, str) else tuple(kinds))
+        lm, wd = float(r.get("lr_mult", 1.0)), float(r.get("weight_decay", weight_decay))
+        if not (lm >= 0.0 and wd >= 0.0):
+            raise ValueError(f"param_groups[{i}]: lr_mult and weight_decay must be >= 0 (got {lm}, {wd})")
+        compiled.append((re.compile(r["match"]) if "match" in r else None, kinds, lm, wd))
+    default, taken = [], [[] for _ in rules]
+    for name, kind in named_kinds:
+        for i, (rx, kinds, _, _) in enumerate(compiled):
+            if (rx is None or rx.search(name)) and (kinds is None or kind in kinds):
+                taken[i].append(name)
+                break
+        else:
+            default.append(name)
+    for i, names in enumerate(taken):
+        if not names:
+            raise ValueError(f"param_groups[{i}] ({ {k: rules[i][k] for k in ('match', 'kinds') if k in rules[i]} }) matches no trainable tensor")
+    groups = ([{"names": default, "lr_mult": 1.0, "weight_decay": float(weight_decay)}] if default else []) + \
+             [{"names": names, "lr_mult": lm, "weight_decay": wd} for names, (_, _, lm, wd) in zip(taken, compiled)]
+    if len(groups) > MAX_GROUPS:
+        raise ValueError(f"param_groups resolve to {len(groups)} groups, the fused step carries at most {MAX_GROUPS}")
+    return groups, {n: i for i, g in enumerate(groups) for n in g["names"]}
+
+
+def _named_trainable(model) -> List[Tuple[str, torch.Tensor]]:
+    pairs = model.named_parameters() if hasattr(model, "named_parameters") else model
+    return [(k, p) for k, p in pairs if getattr(p, "requires_grad", True)]
+
+
+def takes_no_decay(name: str, param) -> bool:
+    """Biases, LayerNorm affines, the Injector gamma (everything with ndim <= 1) and the token parameters gene_pe / gene_cls: the
+    kinds b, lnw, lnb, gamma and tok of synth.param_specs."""
+    return param.ndim <= 1 or name.rsplit(".", 1)[-1] in _TOKEN_PARAMS
+
+
+def groups_by_name(model, rules: Sequence[dict]) -> List[dict]:
+    """torch-style param groups for any optimiser from rules {"match": regex on the parameter name, <hyper-parameters: lr,
+    weight_decay, ...>}: the first rule that matches (re.search) takes the tensor, unmatched tensors form a leading group with the
+    optimiser's defaults.  `model`: an nn.Module or (name, parameter) pairs; frozen parameters are left out.  Every group carries its
+    tensor names under "names" (torch keeps unknown group keys through state_dict() / load_state_dict(); checkpoint.unpack_optimizer
+    maps the state by them).  A rule that matches nothing raises."""
+    rules = list(rules)
+    rx = [re.compile(r["match"]) for r in rules]
+    default, taken = [], [[] for _ in rules]
+    for k, p in _named_trainable(model):
+        for i, r in enumerate(rx):
+            if r.search(k):
+                taken[i].append((k, p))
+                break
+        else:
+            default.append((k, p))
+    for i, t in enumerate(taken):
+        if not t:
+            raise ValueError(f"groups_by_name: rule {i} ({rules[i]['match']!r}) matches no trainable parameter")
+    out = [{"params": [p for _, p in default], "names": [k for k, _ in default]}] if default else []
+    for r, t in zip(rules, taken):
+        out.append({**{k: v for k, v in r.items() if k != "match"}, "params": [p for _, p in t], "names": [k for k, _ in t]})
+    return out
+
+
+def no_decay_groups(model, weight_decay: float, rules: Optional[Sequence[dict]] = None) -> List[dict]:
+    """The usual fine-tuning recipe as torch-style param groups: weight_decay on the matrices, 0 on biases, LayerNorm affines, the
+    Injector gamma and the token parameters (takes_no_decay).  With `rules` (groups_by_name's) every rule's group -- a smaller `lr` for
+    the gene encoder, say -- is split the same way; a rule's own weight_decay replaces `weight_decay` for its matrices."""
+    base = groups_by_name(model, rules) if rules else [{"params": [p for _, p in _named_trainable(model)],
+                                                        "names": [k for k, _ in _named_trainable(model)]}]
+    out = []
+    for g in base:
+        pairs = list(zip(g["names"], g["params"]))
+        hyper = {k: v for k, v in g.items() if k not in ("params", "names", "weight_decay")}
+        for wd, part in ((float(g.get("weight_decay", weight_decay)), [q for q in pairs if not takes_no_decay(*q)]),
+                         (0.0, [q for q in pairs if takes_no_decay(*q)])):
+            if part:
+                out.append({**hyper, "weight_decay": wd, "params": [p for _, p in part], "names": [k for k, _ in part]})
+    return out
 
 
 def _param_span(ps):
@@ -142,6 +274,30 @@ class AdamW(torch.optim.AdamW):
         return all(all(g[k] == g0[k] for k in keys) for g in self.param_groups) and not g0["amsgrad"] and not g0["maximize"] \
             and not torch.is_tensor(g0["lr"])
 
+    def _grouped(self) -> bool:
+        """The groups differ, but in `lr` / `weight_decay` only, and there are at most MAX_GROUPS of them: mt_adamw_step_groups' case."""
+        gs = self.param_groups
+        g0 = gs[0]
+        return 1 < len(gs) <= MAX_GROUPS and all(all(g[k] == g0[k] for k in ("betas", "eps", "amsgrad", "maximize")) for g in gs) \
+            and not g0["amsgrad"] and not g0["maximize"] and not any(torch.is_tensor(g["lr"]) or torch.is_tensor(g["weight_decay"]) for g in gs)
+
+    def _segment_table(self, fl):
+        """The device table of the bound parameters (rebuilt when the groups' membership changed), or None when they do not sit in
+        16-byte slots of a 16-byte aligned span: the step is then torch's own, as for every other unmet precondition."""
+        key = tuple(len(g["params"]) for g in self.param_groups)
+        if fl.get("seg_key") != key:
+            if fl["lo"] % 16:      # (views into a buffer of the user's that starts between two 16-byte lines: the kernel's vectors need them)
+                fl["seg"], fl["seg_key"] = None, key
+                return None
+            ents = sorted(((p.data_ptr() - fl["lo"]) // 4, p.numel(), gi) for gi, g in enumerate(self.param_groups) for p in g["params"])
+            try:
+                end, grp = segment_table(ents)
+                fl["seg"] = (end.to(fl["p"].device), grp.to(fl["p"].device))
+            except ValueError:
+                fl["seg"] = None
+            fl["seg_key"] = key
+        return fl["seg"]
+
     def _bind_flat(self):
         """Do all parameters live in one contiguous fp32 buffer (gaps allowed: ParamStore pads slots to 16 bytes with zeros that
         AdamW leaves at zero)?  If so, build the flat moment buffers and make every parameter's optimiser state a VIEW of them, so
@@ -217,7 +373,8 @@ class AdamW(torch.optim.AdamW):
                 loss = closure()
         grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         fl = None
-        if not self._flat_failed and self._uniform_groups():
+        uniform = self._uniform_groups()
+        if not self._flat_failed and (uniform or self._grouped()):
             if self._flat is not None and self._flat["ids"] != tuple(id(p) for p in self._all_params()):
                 self._sync_steps()            # param_groups were edited in place: the cached views describe another parameter set
                 self._flat = None
@@ -226,14 +383,28 @@ class AdamW(torch.optim.AdamW):
                 self._flat_failed = self._flat is None
             fl = self._flat
         g = self._flat_grad(fl) if fl is not None else None
+        seg = None
+        if fl is not None and not uniform:
+            seg = self._segment_table(fl)
+            if seg is None:
+                fl = g = None
+            elif g is not None and g.data_ptr() % 16:      # (the grouped kernel's vectors sit on 16-byte addresses in all four buffers)
+                g = None
         if g is None and fl is not None:
             g = self._gathered_grad(fl)
         if g is not None:
             grp = self.param_groups[0]
             b1, b2 = grp["betas"]
             # found_inf: GradScaler's 0.0 / 1.0 float, read by the kernel as a word that is zero or not; grad_scale: its fp32 scale
-            ops.adamw_step(fl["p"], g, fl["m"], fl["v"], fl["n"], float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
-                           float(grp["weight_decay"]), 0, scale=grad_scale, found_inf=found_inf, step_dev=fl["step_dev"])
+            if uniform:
+                ops.adamw_step(fl["p"], g, fl["m"], fl["v"], fl["n"], float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
+                               float(grp["weight_decay"]), 0, scale=grad_scale, found_inf=found_inf, step_dev=fl["step_dev"])
+            else:
+                # base lr 1.0 and lr_mult = the group's lr: (float)(1.0f * lr) is what mt_adamw_step forms from the same value; the
+                # values are kernel arguments read at every step, so a scheduler that edits group["lr"] costs nothing
+                ops.adamw_step_groups(fl["p"], g, fl["m"], fl["v"], fl["n"], 0, seg[0], seg[1],
+                                      [(float(q["lr"]), float(q["weight_decay"])) for q in self.param_groups], 1.0, float(b1), float(b2),
+                                      float(grp["eps"]), 0, scale=grad_scale, found_inf=found_inf, step_dev=fl["step_dev"])
             if found_inf is not None:
                 fl["step_dev"].add_((found_inf == 0).to(torch.int32).reshape(1))
             else:

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import dp, ops, pass_groups
+from . import dp, ops, optim, pass_groups
 from ._lib import rowmap
 from .engine import Engine, F32, flatten_genes
 from .graph_cache import GraphCache
@@ -41,7 +41,7 @@ class TrainStep:
                  eps: float = 1e-8, init_scale: float = 2.0 ** 15, growth_interval: int = 2000,
                  process_group=None, task_ids: Sequence[int] = (0, 1, 2), text_rows: Sequence[int] = (0, 1, 3),
                  graph_cache_size: int = 8, capture_after: int = 2, split_passes="auto", accumulate: int = 1,
-                 max_grad_norm: Optional[float] = None, verify_every: int = 0):
+                 max_grad_norm: Optional[float] = None, verify_every: int = 0, param_groups: Optional[Sequence[dict]] = None):
         self.engine, self.dev = engine, engine.device
         # Replica canary (data parallel): every `verify_every`-th boundary call ends with verify_replicas() -- the 8-byte checksum of the
         # flat parameter buffer, MIN- and MAX-reduced over the group, raises on every rank when the replicas differ.  The count of
@@ -104,6 +104,17 @@ class TrainStep:
             self._sumsq = torch.zeros(len(self.reducer.norm_pieces(n)[0]), dtype=torch.float64, device=self.dev)
             self._sumsq_ws = torch.empty(ops.grad_sumsq_partials_elems(n), dtype=torch.float64, device=self.dev)
         self._gcache = GraphCache(graph_cache_size, capture_after)      # the captured bag geometries: key -> _Captured
+        # Parameter groups: per-group lr multiplier and weight decay (optim.resolve_param_groups has the rule format).  The resolved
+        # groups are STATE (host values, saved with a checkpoint); the device table mt_adamw_step_groups reads (segment ends and group
+        # ids of the flat buffer, optim.segment_table) is derived from them and lives in two buffers sized once for the worst case (one
+        # segment per tensor), so a change lands in place.  lr_mult / weight_decay are launch arguments, baked into a capture like
+        # weight_decay always was: set_group() and a load that changes them drop the captures.  The learning rate stays the ONE device
+        # scalar (set_lr): every group trains at lr x lr_mult.  None -- and rules that resolve to lr_mult 1 and one weight_decay
+        # everywhere -- is the one mt_adamw_step launch per piece as ever.
+        self._pgroups, self._group_of, self._seg_end, self._seg_group, self._nseg = None, None, None, None, 0
+        if param_groups is not None:
+            kinds = {k: kind for k, _, kind, train in engine.store.specs if train}
+            self._set_groups(optim.resolve_param_groups([(k, kinds[k]) for k in engine.store.slots], param_groups, weight_decay)[0])
         self._opt_graph, self._opt_gen = None, -1      # world > 1: the optimiser's graph and the generation it was captured under
         self._cap, self._cap_buckets = None, []      # the graph_cache.Capture of a step in progress, the bucket behind each of its cuts
         self._static_key = None
@@ -165,6 +176,75 @@ class TrainStep:
         and replays of already captured graphs both train with it from the next step on."""
         self._lr = float(lr)
         self.lr_dev.fill_(float(lr))
+
+    # ------------------------------------------------------------------ parameter groups
+    @property
+    def param_groups(self):
+        """The resolved groups, [{"names", "lr_mult", "weight_decay"}]: the default group (unmatched tensors) first when it has tensors,
+        then the constructor's rules in order.  Without rules: the one group of all trainable tensors."""
+        if self._pgroups is None:
+            return [{"names": list(self.engine.store.slots), "lr_mult": 1.0, "weight_decay": float(self.wd)}]
+        return [dict(g, names=list(g["names"])) for g in self._pgroups]
+
+    @property
+    def group_of(self) -> Dict[str, int]:
+        """{tensor name: index into param_groups}."""
+        return dict(self._group_of) if self._pgroups is not None else {k: 0 for k in self.engine.store.slots}
+
+    def _grouped(self) -> bool:
+        """The optimiser launch is mt_adamw_step_groups: some group has another lr_mult than 1 or another weight_decay than the rest."""
+        gs = self._pgroups
+        return gs is not None and not all(g["lr_mult"] == 1.0 and g["weight_decay"] == gs[0]["weight_decay"] for g in gs)
+
+    def _baked_groups(self):
+        """What a capture holds of the groups: which entry point, its values, the segment count (the table itself is read in place)."""
+        return (tuple((g["lr_mult"], g["weight_decay"]) for g in self._pgroups), self._nseg) if self._grouped() else None
+
+    def _drop_captures(self):
+        self._gcache.clear()
+        self._opt_graph = None
+
+    def _set_groups(self, groups: Optional[Sequence[dict]]):
+        """Install resolved groups ([{"names", "lr_mult", "weight_decay"}] covering every trainable tensor once, or None): the host list,
+        the device table in place, self.wd when the groups are uniform; captures that hold other values are dropped."""
+        slots = self.engine.store.slots
+        was = self._baked_groups(), self.wd
+        table_was = None if self._seg_end is None else (self._seg_end[:self._nseg].clone(), self._seg_group[:self._nseg].clone())
+        if groups is None:
+            self._pgroups, self._group_of = None, None
+        else:
+            groups = [{"names": list(g["names"]), "lr_mult": float(g["lr_mult"]), "weight_decay": float(g["weight_decay"])} for g in groups]
+            group_of = {k: i for i, g in enumerate(groups) for k in g["names"]}
+            if len(groups) > optim.MAX_GROUPS or sorted(k for g in groups for k in g["names"]) != sorted(slots):
+                raise ValueError(f"param groups: {len(groups)} groups over {sum(len(g['names']) for g in groups)} tensors; at most "
+                                 f"{optim.MAX_GROUPS} groups, and every one of the {len(slots)} trainable tensors in exactly one")
+            end, grp = optim.segment_table([(o, n, group_of[k]) for k, (o, n, _) in slots.items()])
+            if self._seg_end is None:      # (sized for one segment per tensor: later tables land in place)
+                self._seg_end = torch.zeros(len(slots), dtype=torch.int32, device=self.dev)
+                self._seg_group = torch.zeros(len(slots), dtype=torch.uint8, device=self.dev)
+            self._nseg = int(end.numel())
+            self._seg_end[:self._nseg].copy_(end)
+            self._seg_group[:self._nseg].copy_(grp)
+            self._pgroups, self._group_of = groups, group_of
+            if not self._grouped():
+                self.wd = groups[0]["weight_decay"]
+        same_table = table_was is not None and self._pgroups is not None and table_was[0].numel() == self._nseg and \
+            torch.equal(table_was[0], self._seg_end[:self._nseg]) and torch.equal(table_was[1], self._seg_group[:self._nseg])
+        if was != (self._baked_groups(), self.wd) or (self._grouped() and not same_table):
+            self._drop_captures()
+
+    def set_group(self, index: int, lr_mult: Optional[float] = None, weight_decay: Optional[float] = None):
+        """Change a group's lr multiplier and / or weight decay from the next step on (lr_mult = 0 with weight_decay = 0 holds its
+        tensors still: the parameter bits do not move, the moments keep updating).  They are launch arguments: captures that hold the
+        old values are dropped and the recurring geometries are captured again."""
+        groups = self.param_groups
+        g = groups[index]
+        lm = g["lr_mult"] if lr_mult is None else float(lr_mult)
+        wd = g["weight_decay"] if weight_decay is None else float(weight_decay)
+        if not (lm >= 0.0 and wd >= 0.0):
+            raise ValueError(f"set_group: lr_mult and weight_decay must be >= 0 (got {lm}, {wd})")
+        g["lr_mult"], g["weight_decay"] = lm, wd
+        self._set_groups(groups)
 
     # frozen random text projector (train_modaltune.py:44-59,114-116)
     def set_projector(self, state: Dict[str, "np.ndarray | torch.Tensor"]):
@@ -397,7 +477,14 @@ class TrainStep:
             ops.grad_clip_coef(self._sumsq, self._sumsq.numel(), grad_mult, self.scale, self.max_grad_norm, self.found_inf, self._clip_out)
             scale = self._clip_scale      # = scale / coef (scale itself, bit for bit, when nothing is clipped)
         p, g = eng.store.flat, eng.store.flat_grad
+        grouped = self._grouped()
+        hp = [(q["lr_mult"], q["weight_decay"]) for q in self._pgroups] if grouped else None
         for o, k in self.reducer.adam_pieces(n):      # one launch, or: everything but the sharded bucket + this rank's shards
+            if grouped:      # (the piece's absolute position picks its segments out of the one table)
+                ops.adamw_step_groups(p[o:o + k], g[o:o + k], self.m[o:o + k], self.v[o:o + k], k, o, self._seg_end, self._seg_group, hp,
+                                      self._lr, self.betas[0], self.betas[1], self.eps, 0, scale=scale, found_inf=self.found_inf,
+                                      grad_mult=grad_mult, step_dev=self.step_dev, lr_dev=self.lr_dev, nseg=self._nseg)
+                continue
             ops.adamw_step(p[o:o + k], g[o:o + k], self.m[o:o + k], self.v[o:o + k], k, self._lr, self.betas[0], self.betas[1], self.eps,
                            self.wd, 0, scale=scale, found_inf=self.found_inf, grad_mult=grad_mult, step_dev=self.step_dev,
                            lr_dev=self.lr_dev)
@@ -733,7 +820,7 @@ class TrainStep:
         hyper = {"lr": self._lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd}
         return {"format": checkpoint.FORMAT,
                 "model": {k: store.tensors[k].detach().cpu().clone() for k in keys},
-                "optimizer": checkpoint.pack_optimizer(self.m, self.v, int(self.step_dev), store.slots, names, hyper),
+                "optimizer": checkpoint.pack_optimizer(self.m, self.v, int(self.step_dev), store.slots, names, hyper, groups=self._pgroups),
                 "scaler": checkpoint.pack_scaler(float(self.scale), int(self.tracker), self.growth_interval),
                 "rng": eng.rng.detach().cpu().clone(), "stochastic": bool(eng.stochastic), "lr": float(self._lr), "window": window,
                 "schedule": {"split_decisions": {int(k): bool(v) for k, v in self.split_decisions.items()}},
@@ -798,6 +885,9 @@ class TrainStep:
         if baked != (tuple(self.betas), self.eps, self.wd, self.growth_interval):
             self._gcache.clear()          # (these are launch arguments: captured graphs carry the old values)
             self._opt_graph = None
+        # the checkpoint's groups win over the constructor's, as its hyper-parameters do (a uniform checkpoint: no groups); the table
+        # lands in place, captures are dropped when what they hold of the groups differs
+        self._set_groups(hyper.get("groups"))
         self.set_lr(sd["lr"] if full else hyper["lr"])
         self.found_inf.zero_()
         self.window_pos = 0
