@@ -52,7 +52,7 @@ typedef struct {
 
 /* major * 100 + minor * 10.  3.0: the optional inputs of a launcher travel in MtLaunchOpts; the suffixed twin entries (_eps, _det, _grid,
  * _live) of 2.x are gone, so a 2.x caller does not link against this library.  3.1: + mt_token_mha_fwd_drop / _bwd_drop.  3.2: + mt_patch_points_fwd / mt_patch_ig_accumulate.
- * 3.3: + mt_checksum64.  3.4: + mt_adamw_step_groups. */
+ * 3.3: + mt_checksum64.  3.4: + mt_adamw_step_groups.  3.5: + mt_adamw_step_groups_ema, mt_swap_f32. */
 int mt_version(void);
 const char* mt_status_string(int status);
 /* Build provenance: sha256 (hex) over the kernel sources, this header and the compiler flags the library was built from
@@ -603,6 +603,23 @@ int mt_adamw_step_groups(float* p, const float* g, float* m, float* v, long n, l
                          const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr, double beta1,
                          double beta2, double eps, int step_count, const int* step_dev, float grad_mult, const float* scale,
                          int* found_inf, const float* lr_dev, mt_stream_t stream);
+/* mt_adamw_step_groups that also keeps an EXPONENTIAL MOVING AVERAGE of the parameters, in the same launch: `ema` is one more flat fp32
+ * buffer laid out and indexed like `p` (the same piece of its own 16-byte aligned buffer, overlapping none of p, g, m, v: else
+ * MT_ERR_BAD_ARG).  Behind the AdamW update of an element, with p_new its new parameter and contraction off:
+ *   d = p_new - e;   t = w * d;   e = e + t          three fp32 operations, each rounded once, no FMA
+ * so an element held still (lr_mult = 0, weight_decay = 0) whose average equals it keeps every bit.  w is one value per launch, formed
+ * in double from the 1-based optimiser step t = *step_dev + 1 (step_dev NULL: step_count):
+ *   decay_t = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay;   w = (float)(1.0 - decay_t)
+ * A set *found_inf skips the average with the update.  p, m and v get mt_adamw_step_groups's bits.  ema == NULL: mt_adamw_step_groups
+ * itself (ema_decay and ema_warmup are not read); otherwise ema_decay outside [0, 1): MT_ERR_BAD_ARG. */
+int mt_adamw_step_groups_ema(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                             const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr, double beta1,
+                             double beta2, double eps, int step_count, const int* step_dev, float grad_mult, const float* scale,
+                             int* found_inf, const float* lr_dev, float* ema, double ema_decay, int ema_warmup, mt_stream_t stream);
+/* a[i] <-> b[i] for i < n: two fp32 buffers exchanged as 32-bit patterns (NaN payloads and -0.0 survive).  Both 4-byte aligned, any
+ * n >= 1; the ranges must not overlap (MT_ERR_BAD_ARG, as for a null pointer or n <= 0).  16-byte loads and stores when a and b sit
+ * alike in their 16-byte lines, 4-byte ones otherwise. */
+int mt_swap_f32(float* a, float* b, long n, mt_stream_t stream);
 /* GradScaler.update on device (TM:237): *found_inf ? scale *= backoff : (every `interval` clean steps scale *= growth,
  * unless the product is not finite: then the scale stays, as in torch._amp_update_scale_); *found_inf is cleared */
 int mt_scaler_update(float* scale, int* growth_tracker, int* found_inf, int* step_dev /* ++ on a clean step, or NULL */,

@@ -152,6 +152,8 @@ SIGNATURES = {
     "mt_distill_loss": [P, P, I, I, F, P, P, P, P],
     "mt_adamw_step": [P, P, P, P, L, D, D, D, D, D, I, P, F, P, P, P, P],
     "mt_adamw_step_groups": [P, P, P, P, L, L, P, P, I, C.POINTER(MtAdamGroup), I, D, D, D, D, I, P, F, P, P, P, P],
+    "mt_adamw_step_groups_ema": [P, P, P, P, L, L, P, P, I, C.POINTER(MtAdamGroup), I, D, D, D, D, I, P, F, P, P, P, P, D, I, P],
+    "mt_swap_f32": [P, P, L, P],
     "mt_scaler_update": [P, P, P, P, F, F, I, P],
     "mt_check_finite": [P, L, P, P],
     "mt_grad_sumsq": [P, L, P, L, P, P, P],

@@ -20,6 +20,9 @@ read back with `torch.load(..., weights_only=True)`):
     checksums   {"flat", "m", "v"}: mt_checksum64 of the three flat buffers (slot padding included, which is zero) as Python ints
     build_id    of the library that wrote it;  world: the data-parallel world size it was written at
     config      the ModelConfig fields and the pathway group sizes: the shape check, and what verify_file lays the flat buffers out by
+    ema         OPTIONAL, only from a TrainStep(ema_decay=...): {"decay", "warmup", "model": {key: tensor}} -- the exponential moving
+                average of the trainable tensors under the names of `model`; `checksums` then carries "ema" as well.  REQUIRED_KEYS and
+                `format` are what they were: a step without an average writes and reads today's key set exactly
 
 The slot padding of the flat buffers (slots are 16-byte aligned) is not stored; a load zeroes it.
 """
@@ -229,6 +232,29 @@ def unpack_optimizer(opt_sd: dict, slots: Dict[str, tuple], trainable_names: Seq
     return m, v, (next(iter(steps.values())) if steps else 0), hyper
 
 
+# ------------------------------------------------------------------------------------------------ EMA of the weights
+def pack_ema(ema_flat: torch.Tensor, slots: Dict[str, tuple], decay: float, warmup: bool) -> dict:
+    """The optional `ema` entry: {"decay", "warmup", "model": {name: tensor}} -- the flat average per tensor, in slot (= specs) order,
+    under the names of `model`; slot padding is not stored."""
+    ema_flat = ema_flat.detach().to("cpu")
+    return {"decay": float(decay), "warmup": bool(warmup),
+            "model": {k: ema_flat[o:o + n].clone().view(shape) for k, (o, n, shape) in slots.items()}}
+
+
+def unpack_ema(ema_sd: dict, slots: Dict[str, tuple], n_flat: int) -> Tuple[torch.Tensor, float, bool]:
+    """pack_ema's inverse: (zero-padded flat CPU buffer, decay, warm-up flag); KeyError / ValueError naming what is wrong."""
+    for k in ("decay", "warmup", "model"):
+        if not isinstance(ema_sd, dict) or k not in ema_sd:
+            raise KeyError(f"ema: `{k}` is missing")
+    decay = float(ema_sd["decay"])
+    if not 0.0 <= decay < 1.0:
+        raise ValueError(f"ema: decay {decay} is outside [0, 1)")
+    for k in ema_sd["model"]:
+        if k not in slots:
+            raise KeyError(f"ema: unexpected tensor {k}")
+    return _flat_from(ema_sd["model"], slots, n_flat, "ema"), decay, bool(ema_sd["warmup"])
+
+
 # ------------------------------------------------------------------------------------------------ scaler
 def pack_scaler(scale: float, growth_tracker: int, growth_interval: int, growth_factor: float = GROWTH_FACTOR,
                 backoff_factor: float = BACKOFF_FACTOR) -> dict:
@@ -288,15 +314,20 @@ def flat_buffers(sd: dict, slots: Dict[str, tuple], n_flat: int):
 
 
 def verify_file(path: str) -> dict:
-    """Read a checkpoint file (weights_only) and recompute its three checksums on the CPU from what it stores; RuntimeError naming the
-    buffer on a mismatch.  Returns the checkpoint."""
+    """Read a checkpoint file (weights_only) and recompute its three checksums (four with an `ema` entry) on the CPU from what it
+    stores; RuntimeError naming the buffer on a mismatch.  Returns the checkpoint."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
     if not check_format(sd):
         raise ValueError(f"{path}: not a TrainStep checkpoint (no `format`)")
     cfg, sizes = config_from_dict(sd["config"])
     slots, n_flat = slots_of(param_specs(cfg, sizes))
     flat, m, v, _, _ = flat_buffers(sd, slots, n_flat)
-    for name, buf in (("flat", flat), ("m", m), ("v", v)):
+    bufs = [("flat", flat), ("m", m), ("v", v)]
+    if "ema" in sd:      # (optional: a step that keeps an average)
+        if "ema" not in sd["checksums"]:
+            raise KeyError(f"{path}: `ema` is stored without its checksum")
+        bufs.append(("ema", unpack_ema(sd["ema"], slots, n_flat)[0]))
+    for name, buf in bufs:
         have, want = checksum64_reference(buf), as_unsigned(sd["checksums"][name])
         if have != want:
             raise RuntimeError(f"{path}: checksum of `{name}` is {have:#018x}, the file records {want:#018x}")

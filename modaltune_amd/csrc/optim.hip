@@ -3,6 +3,9 @@
 
 namespace {
 
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64;
+
 // One workgroup: R <= 8 rows of O <= 1024 logits.  train_modaltune.py:225-233:
 //   z = logit / ||logit||; loss = 10 * sum_r sum_j p_rj (log p_rj - log_softmax(z_r)_j), p = softmax(target_r)
 // d loss / d z_rj = 10 * (softmax(z_r)_j - p_rj)   (sum_j p_rj = 1);  d/d logit = (dz - z (z . dz)) / ||logit||
@@ -116,6 +119,30 @@ MT_DEVINL void adamw_elem(float& p, float g, float& m, float& v, float lr, float
   p = pi; m = mi; v = vi;
 }
 
+// Exponential moving average of the parameters, inside the AdamW launch (EMA = true): one more flat buffer `ema`, indexed like `p`,
+// moved towards the NEW parameter by the launch's one weight w = 1 - decay_t.  Three fp32 operations, each rounded once, no FMA -- the
+// difference form: a tensor held still whose average equals it (d = 0) keeps every bit, which decay * e + (1 - decay) * p would not.
+MT_DEVINL void ema_elem(float& e, float p_new, float w) {
+#pragma clang fp contract(off)
+  const float d = p_new - e;
+  const float t = w * d;
+  e = e + t;
+}
+
+// w of optimiser step t (1-based), in double, on the host (step_count) and on the device (*step_dev + 1) alike:
+//   decay_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay,   w = (float)(1 - decay_t)
+__host__ __device__ inline float ema_weight(double decay, int warmup, double t) {
+  double d = decay;
+  if (warmup) { const double r = (1.0 + t) / (10.0 + t); d = r < d ? r : d; }
+  return (float)(1.0 - d);
+}
+
+template <bool EMA>
+MT_DEVINL f32x4 ema_load(const f32x4* __restrict__ ev, long i) {
+  if constexpr (EMA) return ev[i];
+  else return f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // the segment of absolute index a: the first s with a < seg_end[s] (an index behind the last end stays in the last segment)
 MT_DEVINL int adamg_find(const int* __restrict__ seg_end, int nseg, long a) {
   int lo = 0, hi = nseg - 1;
@@ -133,6 +160,7 @@ MT_DEVINL void adamg_values(const AdamGroupTab& tab, const unsigned char* __rest
   decay_g = (float)(1.0 - (double)lr_g * tab.wd[gid]);
 }
 
+template <bool EMA>
 __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                      float* __restrict__ v, long n, long base, int head, long nvec, long per,
                                                                      const int* __restrict__ seg_end,
@@ -140,13 +168,16 @@ __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __re
                                                                      AdamGroupTab tab, float lr, float b1, float b2, float omb1, float omb2,
                                                                      float eps, float bc1, float bc2s, double b1d, double b2d, float grad_mult,
                                                                      const float* __restrict__ scale, const int* __restrict__ found_inf,
-                                                                     const int* __restrict__ step_dev, const float* __restrict__ lr_dev) {
-  if (found_inf && *found_inf) return;
+                                                                     const int* __restrict__ step_dev, const float* __restrict__ lr_dev,
+                                                                     float* __restrict__ ema, float ema_w, double ema_decay,
+                                                                     int ema_warmup) {
+  if (found_inf && *found_inf) return;       // (EMA: a skipped step moves nothing and does not count)
   if (lr_dev) lr = *lr_dev;
   if (step_dev) {                            // (adamw_kernel: the bias corrections in double from the device's step count)
     const double st = (double)(*step_dev + 1);
     bc1 = (float)(1.0 - pow(b1d, st));
     bc2s = (float)sqrt(1.0 - pow(b2d, st));
+    if constexpr (EMA) ema_w = ema_weight(ema_decay, ema_warmup, st);
   }
   const AdamShared c = {b1, b2, omb1, omb2, eps, bc1, bc2s, grad_mult * (scale ? 1.0f / *scale : 1.0f)};
   const int tid = threadIdx.x;
@@ -155,6 +186,7 @@ __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __re
   const f32x4* __restrict__ gv = reinterpret_cast<const f32x4*>(g + head);
   f32x4* __restrict__ mv = reinterpret_cast<f32x4*>(m + head);
   f32x4* __restrict__ vv = reinterpret_cast<f32x4*>(v + head);
+  f32x4* __restrict__ ev = reinterpret_cast<f32x4*>(ema + head);      // (EMA = false: never dereferenced)
   const long v0 = (long)blockIdx.x * per, v1 = v0 + per < nvec ? v0 + per : nvec;      // (per: a multiple of the workgroup size)
   long i = v0 + tid;
   if (i < v1) {
@@ -162,7 +194,7 @@ __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __re
     long end = (long)seg_end[s];
     float lr_g, decay_g;
     adamg_values(tab, seg_group, s, lr, lr_g, decay_g);
-    auto update = [&](long iv, f32x4 p4, f32x4 g4, f32x4 m4, f32x4 v4) {
+    auto update = [&](long iv, f32x4 p4, f32x4 g4, f32x4 m4, f32x4 v4, f32x4 e4) {
       const long a = vbase + 4 * iv;
       if (a >= end && s + 1 < nseg) {        // (forward only; behind the last end: the last segment)
         do { ++s; end = (long)seg_end[s]; } while (a >= end && s + 1 < nseg);
@@ -173,16 +205,19 @@ __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __re
         float pe = p4[e], me = m4[e], ve = v4[e];
         adamw_elem(pe, g4[e], me, ve, lr_g, decay_g, c);
         p4[e] = pe; m4[e] = me; v4[e] = ve;
+        if constexpr (EMA) { float ee = e4[e]; ema_elem(ee, pe, ema_w); e4[e] = ee; }
       }
       pv[iv] = p4; mv[iv] = m4; vv[iv] = v4;
+      if constexpr (EMA) ev[iv] = e4;
     };
-    for (; i + ADAMG_THREADS < v1; i += 2 * ADAMG_THREADS) {      // two vectors per thread: eight 16-byte loads in flight
+    for (; i + ADAMG_THREADS < v1; i += 2 * ADAMG_THREADS) {      // two vectors per thread: eight 16-byte loads in flight (EMA: ten)
       const long k = i + ADAMG_THREADS;
       const f32x4 pa = pv[i], ga = gv[i], ma = mv[i], va = vv[i], pb = pv[k], gb = gv[k], mb = mv[k], vb = vv[k];
-      update(i, pa, ga, ma, va);
-      update(k, pb, gb, mb, vb);
+      const f32x4 ea = ema_load<EMA>(ev, i), eb = ema_load<EMA>(ev, k);
+      update(i, pa, ga, ma, va, ea);
+      update(k, pb, gb, mb, vb, eb);
     }
-    if (i < v1) update(i, pv[i], gv[i], mv[i], vv[i]);
+    if (i < v1) update(i, pv[i], gv[i], mv[i], vv[i], ema_load<EMA>(ev, i));
   }
   if (blockIdx.x == 0) {
     const long tail0 = head + 4 * nvec;
@@ -193,7 +228,33 @@ __global__ __launch_bounds__(ADAMG_THREADS) void adamw_groups_kernel(float* __re
       float lr_g, decay_g;
       adamg_values(tab, seg_group, adamg_find(seg_end, nseg, base + j), lr, lr_g, decay_g);
       adamw_elem(p[j], g[j], m[j], v[j], lr_g, decay_g, c);
+      if constexpr (EMA) ema_elem(ema[j], p[j], ema_w);
     }
+  }
+}
+
+// a[i] <-> b[i] over two fp32 buffers that do not overlap, moved as 32-bit PATTERNS (NaN payloads, -0.0 survive).  Both 4-byte aligned:
+// when they sit alike in their 16-byte lines everything between the `head` scalars in front of the first boundary and the tail behind
+// the last whole vector goes as 16-byte loads and stores (grad_sumsq_partials_kernel's form, two vectors of each buffer in flight); else
+// the launcher hands over nvec = 0 and every word goes through the scalar loop.  A grid-stride loop over a fixed cap of workgroups.
+constexpr int SWAP_THREADS = 256, SWAP_MAX_WGS = 2048;
+
+__global__ __launch_bounds__(SWAP_THREADS) void swap_f32_kernel(unsigned* __restrict__ a, unsigned* __restrict__ b, long n, int head,
+                                                                long nvec) {
+  u32x4* __restrict__ av = reinterpret_cast<u32x4*>(a + head);
+  u32x4* __restrict__ bv = reinterpret_cast<u32x4*>(b + head);
+  const long stride = (long)gridDim.x * SWAP_THREADS, first = (long)blockIdx.x * SWAP_THREADS + threadIdx.x;
+  long v = first;
+  for (; v + stride < nvec; v += 2 * stride) {
+    const u32x4 a0 = av[v], b0 = bv[v], a1 = av[v + stride], b1 = bv[v + stride];
+    av[v] = b0; bv[v] = a0; av[v + stride] = b1; bv[v + stride] = a1;
+  }
+  if (v < nvec) { const u32x4 a0 = av[v], b0 = bv[v]; av[v] = b0; bv[v] = a0; }
+  const long tail0 = head + 4 * nvec, loose = head + (n - tail0);      // the words outside the vectors: [0, head) and [tail0, n)
+  for (long j = first; j < loose; j += stride) {
+    const long i = j < head ? j : tail0 + (j - head);
+    const unsigned x = a[i], y = b[i];
+    a[i] = y; b[i] = x;
   }
 }
 
@@ -278,8 +339,6 @@ __global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_final_kernel(const d
 // ordering rules.  The multiplier is odd (a single-word change always moves the sum) and depends on the position (swapped words move
 // it); the + 1 makes runs of zeros of different lengths differ; index_base makes pieces compose.  The cross-wave step goes through LDS
 // as 8-byte words only (one LDS banking class, common.h).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
 
 MT_DEVINL u64 cs_mix(u64 j) {
   u64 z = j + 0x9E3779B97F4A7C15ull;
@@ -532,18 +591,23 @@ extern "C" int mt_adamw_step(float* p, const float* g, float* m, float* v, long 
   return MT_OK;
 }
 
-extern "C" int mt_adamw_step_groups(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
-                                    const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr,
-                                    double beta1, double beta2, double eps, int step_count, const int* step_dev, float grad_mult,
-                                    const float* scale, int* found_inf, const float* lr_dev, mt_stream_t stream) {
+// the one body of mt_adamw_step_groups and mt_adamw_step_groups_ema (ema == NULL: the EMA = false instantiation)
+static int adamw_groups_launch(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                               const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr, double beta1,
+                               double beta2, double eps, int step_count, const int* step_dev, float grad_mult, const float* scale,
+                               int* found_inf, const float* lr_dev, float* ema, double ema_decay, int ema_warmup, mt_stream_t stream) {
   if (!p || !g || !m || !v || !seg_end || !seg_group || !groups || nseg < 1 || n < 1 || index_base < 0 || (step_count < 1 && !step_dev))
     return MT_ERR_BAD_ARG;
+  if (ema && !(ema_decay >= 0.0 && ema_decay < 1.0)) return MT_ERR_BAD_ARG;
   if (ngroups < 1 || ngroups > MT_ADAM_MAX_GROUPS) return MT_ERR_UNSUPPORTED;
-  // a float4 starts on an absolute multiple of 4 AND on a 16-byte address, in all four buffers: the piece must lie in its buffer as
+  // a float4 starts on an absolute multiple of 4 AND on a 16-byte address, in all buffers: the piece must lie in its buffer as
   // index_base says (p = flat + index_base with a 16-byte aligned flat)
   const uintptr_t want = (uintptr_t)(index_base & 3);
-  for (const void* q : {(const void*)p, (const void*)g, (const void*)m, (const void*)v})
+  for (const void* q : {(const void*)p, (const void*)g, (const void*)m, (const void*)v, (const void*)(ema ? ema : p)})
     if (((uintptr_t)q & 3) || (((uintptr_t)q >> 2) & 3) != want) return MT_ERR_BAD_ARG;
+  if (ema)      // the average is a buffer of its own: [ema, ema + n) meets none of the other four
+    for (const float* q : {(const float*)p, g, (const float*)m, (const float*)v})
+      if ((uintptr_t)ema < (uintptr_t)(q + n) && (uintptr_t)q < (uintptr_t)(ema + n)) return MT_ERR_BAD_ARG;
   AdamGroupTab tab;
   for (int i = 0; i < MT_ADAM_MAX_GROUPS; ++i) {
     tab.lr_mult[i] = groups[i < ngroups ? i : 0].lr_mult;
@@ -552,6 +616,7 @@ extern "C" int mt_adamw_step_groups(float* p, const float* g, float* m, float* v
   if (step_count < 1) step_count = 1;
   const float bc1 = (float)(1.0 - pow(beta1, (double)step_count));
   const float bc2s = (float)sqrt(1.0 - pow(beta2, (double)step_count));
+  const float ema_w = ema ? ema_weight(ema_decay, ema_warmup, (double)step_count) : 0.f;
   long head = (long)((4 - (index_base & 3)) & 3);
   if (head > n) head = n;
   const long nvec = (n - head) / 4;
@@ -561,9 +626,45 @@ extern "C" int mt_adamw_step_groups(float* p, const float* g, float* m, float* v
   if (rows < 2) rows = 2;
   const long per = rows * ADAMG_THREADS;
   const int grid = (int)(nvec > 0 ? (nvec + per - 1) / per : 1);
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid), dim3(ADAMG_THREADS), 0, (hipStream_t)stream, p, g, m, v, n, index_base, (int)head,
-                     nvec, per, seg_end, seg_group, nseg, tab, (float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
-                     (float)eps, bc1, bc2s, beta1, beta2, grad_mult, scale, (const int*)found_inf, step_dev, lr_dev);
+  hipLaunchKernelGGL(ema ? adamw_groups_kernel<true> : adamw_groups_kernel<false>, dim3(grid), dim3(ADAMG_THREADS), 0, (hipStream_t)stream,
+                     p, g, m, v, n, index_base, (int)head, nvec, per, seg_end, seg_group, nseg, tab, (float)lr, (float)beta1, (float)beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, bc1, bc2s, beta1, beta2, grad_mult, scale,
+                     (const int*)found_inf, step_dev, lr_dev, ema, ema_w, ema_decay, ema_warmup);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" int mt_adamw_step_groups(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                                    const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr,
+                                    double beta1, double beta2, double eps, int step_count, const int* step_dev, float grad_mult,
+                                    const float* scale, int* found_inf, const float* lr_dev, mt_stream_t stream) {
+  return adamw_groups_launch(p, g, m, v, n, index_base, seg_end, seg_group, nseg, groups, ngroups, lr, beta1, beta2, eps, step_count,
+                             step_dev, grad_mult, scale, found_inf, lr_dev, nullptr, 0.0, 0, stream);
+}
+
+extern "C" int mt_adamw_step_groups_ema(float* p, const float* g, float* m, float* v, long n, long index_base, const int* seg_end,
+                                        const unsigned char* seg_group, int nseg, const MtAdamGroup* groups, int ngroups, double lr,
+                                        double beta1, double beta2, double eps, int step_count, const int* step_dev, float grad_mult,
+                                        const float* scale, int* found_inf, const float* lr_dev, float* ema, double ema_decay,
+                                        int ema_warmup, mt_stream_t stream) {
+  return adamw_groups_launch(p, g, m, v, n, index_base, seg_end, seg_group, nseg, groups, ngroups, lr, beta1, beta2, eps, step_count,
+                             step_dev, grad_mult, scale, found_inf, lr_dev, ema, ema_decay, ema_warmup, stream);
+}
+
+extern "C" int mt_swap_f32(float* a, float* b, long n, mt_stream_t stream) {
+  if (!a || !b || n <= 0) return MT_ERR_BAD_ARG;
+  if (((uintptr_t)a & 3) || ((uintptr_t)b & 3)) return MT_ERR_BAD_ARG;
+  if ((uintptr_t)a < (uintptr_t)(b + n) && (uintptr_t)b < (uintptr_t)(a + n)) return MT_ERR_BAD_ARG;      // (overlapping ranges)
+  long head = 0, nvec = 0;
+  if ((((uintptr_t)a ^ (uintptr_t)b) & 15) == 0) {      // alike in their 16-byte lines: the vector form
+    head = (long)(((16 - ((uintptr_t)a & 15)) & 15) / 4);
+    if (head > n) head = n;
+    nvec = (n - head) / 4;
+  }
+  const long work = nvec > 0 ? (nvec + 1) / 2 : n;      // threads that have something to do
+  const long wgs = (work + SWAP_THREADS - 1) / SWAP_THREADS;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3((int)(wgs > SWAP_MAX_WGS ? SWAP_MAX_WGS : wgs)), dim3(SWAP_THREADS), 0, (hipStream_t)stream,
+                     (unsigned*)a, (unsigned*)b, n, (int)head, nvec);
   MT_CHECK_LAUNCH();
   return MT_OK;
 }
@@ -681,7 +782,7 @@ extern "C" int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_st
   return MT_OK;
 }
 
-extern "C" int mt_version(void) { return 340; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64, 3.4: mt_adamw_step_groups; the binary itself is identified by mt_build_id(), not by this number)
+extern "C" int mt_version(void) { return 350; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64, 3.4: mt_adamw_step_groups, 3.5: mt_adamw_step_groups_ema / mt_swap_f32; the binary itself is identified by mt_build_id(), not by this number)
 
 extern "C" const char* mt_status_string(int status) {
   switch (status) {

@@ -621,6 +621,22 @@ def adamw_step_groups(p, g, m, v, n, index_base, seg_end, seg_group, groups, lr,
                                            _p(step_dev), float(grad_mult), _p(scale), _p(found_inf), _p(lr_dev), _s()), "adamw_step_groups")
 
 
+def adamw_step_groups_ema(p, g, m, v, n, index_base, seg_end, seg_group, groups, lr, beta1, beta2, eps, step_count, ema, ema_decay,
+                          ema_warmup=False, scale=None, found_inf=None, grad_mult=1.0, step_dev=None, lr_dev=None, nseg=None):
+    """adamw_step_groups that moves the flat buffer `ema` (the same piece as `p`) towards the new parameters in the same launch
+    (include/modaltune_hip.h: mt_adamw_step_groups_ema).  ema None: adamw_step_groups' launch."""
+    tab = (_lib.MtAdamGroup * max(len(groups), 1))(*[(float(a), float(b)) for a, b in groups])
+    check(_lib.load().mt_adamw_step_groups_ema(_p(p), _p(g), _p(m), _p(v), n, index_base, _p(seg_end), _p(seg_group),
+                                               seg_end.numel() if nseg is None else nseg, tab, len(groups), lr, beta1, beta2, eps,
+                                               step_count, _p(step_dev), float(grad_mult), _p(scale), _p(found_inf), _p(lr_dev), _p(ema),
+                                               float(ema_decay), int(bool(ema_warmup)), _s()), "adamw_step_groups_ema")
+
+
+def swap_f32(a, b, n=None):
+    """a[:n] <-> b[:n] as 32-bit patterns (include/modaltune_hip.h: mt_swap_f32)."""
+    check(_lib.load().mt_swap_f32(_p(a), _p(b), a.numel() if n is None else n, _s()), "swap_f32")
+
+
 def absmax_scale(x, s, target=1024.0, n=None):
     """s[0] = target / max|x|, s[1] = 1 / s[0] on the device (include/modaltune_hip.h: mt_absmax_scale)."""
     check(_lib.load().mt_absmax_scale(_p(x), n if n is not None else x.numel(), float(target), _p(s), _s()), "absmax_scale")
@@ -764,6 +780,7 @@ _DETAIL = bool(os.environ.get("MT_TIMER_DETAIL"))
 sgemm_multi = _timed(lambda problems: ("sgemm[" + "+".join(f"{q.M}x{q.N}x{q.K}b{q.batch}" for q in problems) + "]" if _DETAIL else "token_side"))(sgemm_multi)
 adamw_step = _timed(lambda *a, **k: "adamw")(adamw_step)
 adamw_step_groups = _timed(lambda *a, **k: "adamw_groups")(adamw_step_groups)
+adamw_step_groups_ema = _timed(lambda *a, **k: "adamw_groups_ema")(adamw_step_groups_ema)
 # the rest of the token side (T <= ~200 rows: adds, copies, DropPath rows, T x T attention, pathway networks, loss head) -- until round 5
 # these launches were outside the table (it listed 184 of the ~220 token-side launches of a step)
 _small = lambda n: "token_side" if n <= (1 << 20) else "elementwise"

@@ -10,6 +10,7 @@ for just before AdamW -- the collectives of the upper blocks run under the backw
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional, Sequence
 
@@ -41,8 +42,20 @@ class TrainStep:
                  eps: float = 1e-8, init_scale: float = 2.0 ** 15, growth_interval: int = 2000,
                  process_group=None, task_ids: Sequence[int] = (0, 1, 2), text_rows: Sequence[int] = (0, 1, 3),
                  graph_cache_size: int = 8, capture_after: int = 2, split_passes="auto", accumulate: int = 1,
-                 max_grad_norm: Optional[float] = None, verify_every: int = 0, param_groups: Optional[Sequence[dict]] = None):
+                 max_grad_norm: Optional[float] = None, verify_every: int = 0, param_groups: Optional[Sequence[dict]] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = False):
         self.engine, self.dev = engine, engine.device
+        # Exponential moving average of the trainable weights (every step is taken on ONE slide: the weights at an epoch's end are a noisy
+        # sample of the trajectory, the average is what to evaluate and save).  `ema` is one more flat fp32 buffer laid out like the
+        # parameters, a copy of them at construction, moved INSIDE the AdamW launch (mt_adamw_step_groups_ema: e += w * (p_new - e)
+        # with w = 1 - decay, or 1 - min(decay, (1 + t) / (10 + t)) at optimiser step t with ema_warmup) -- so it moves exactly when
+        # the parameters do: at a window's boundary, not at micro-steps, not at a skipped step; in eager steps, replays and the world
+        # > 1 optimiser graph alike; with a sharded last bucket a rank averages its own shard only (completed where it is read:
+        # state_dict(), ema_weights()).  ema_decay / ema_warmup are launch arguments (set_ema_decay drops the captures).  A step without
+        # parameter groups goes through the grouped kernel with a one-segment table (lr_mult 1, the step's weight_decay): the bits of
+        # mt_adamw_step.  None (the default): nothing is allocated, nothing is launched differently.
+        self.ema_decay, self.ema_warmup = _valid_ema_decay(ema_decay), bool(ema_warmup)
+        self.ema, self._ema_seg, self._ema_swapped = None, None, False
         # Replica canary (data parallel): every `verify_every`-th boundary call ends with verify_replicas() -- the 8-byte checksum of the
         # flat parameter buffer, MIN- and MAX-reduced over the group, raises on every rank when the replicas differ.  The count of
         # boundary calls is HOST state.  0 (the default): nothing is launched, allocated or synchronised for it.
@@ -103,6 +116,9 @@ class TrainStep:
         if self.max_grad_norm is not None:      # (allocated here: never inside a capture)
             self._sumsq = torch.zeros(len(self.reducer.norm_pieces(n)[0]), dtype=torch.float64, device=self.dev)
             self._sumsq_ws = torch.empty(ops.grad_sumsq_partials_elems(n), dtype=torch.float64, device=self.dev)
+        if self.ema_decay is not None:      # (allocated here: never inside a capture; a fresh engine has no parameter gather in flight)
+            self.ema = engine.store.flat.detach().clone()
+            self._ema_seg = (torch.full((1,), n, dtype=torch.int32, device=self.dev), torch.zeros(1, dtype=torch.uint8, device=self.dev))
         self._gcache = GraphCache(graph_cache_size, capture_after)      # the captured bag geometries: key -> _Captured
         # Parameter groups: per-group lr multiplier and weight decay (optim.resolve_param_groups has the rule format).  The resolved
         # groups are STATE (host values, saved with a checkpoint); the device table mt_adamw_step_groups reads (segment ends and group
@@ -245,6 +261,69 @@ class TrainStep:
             raise ValueError(f"set_group: lr_mult and weight_decay must be >= 0 (got {lm}, {wd})")
         g["lr_mult"], g["weight_decay"] = lm, wd
         self._set_groups(groups)
+
+    # ------------------------------------------------------------------ EMA of the trainable weights
+    def _not_averaged(self, what: str):
+        """Inside ema_weights() the parameter buffer holds the average: nothing that trains, saves or loads may run there."""
+        if getattr(self, "_ema_swapped", False):
+            raise RuntimeError(f"{what} inside ema_weights(): the parameter buffer holds the averaged weights -- leave the context first")
+
+    def _need_ema(self, what: str):
+        if getattr(self, "ema", None) is None:
+            raise RuntimeError(f"{what}: this TrainStep keeps no average (construct it with ema_decay=...)")
+
+    def set_ema_decay(self, decay: float, warmup: Optional[bool] = None):
+        """Change the EMA's decay (and warm-up flag) from the next step on.  Launch arguments: captures that hold the old values are
+        dropped and the recurring geometries are captured again."""
+        self._need_ema("set_ema_decay")
+        decay = _valid_ema_decay(decay)
+        if decay is None:
+            raise ValueError("set_ema_decay: a decay in [0, 1) is expected (the average cannot be switched off after construction)")
+        warmup = self.ema_warmup if warmup is None else bool(warmup)
+        if (decay, warmup) != (self.ema_decay, self.ema_warmup):
+            self.ema_decay, self.ema_warmup = decay, warmup
+            self._drop_captures()
+
+    def ema_reset(self):
+        """The average starts again from the current parameters."""
+        self._need_ema("ema_reset")
+        self._not_averaged("ema_reset()")
+        if self.engine.store.sync is not None:
+            self.engine.store.sync()
+        self.ema.copy_(self.engine.store.flat)
+
+    def ema_state(self) -> Dict[str, torch.Tensor]:
+        """{name: view into the average} under the reference's state_dict names, for load_state_dict(..., strict=False) into the module
+        path or the reference.  Data parallel with a sharded last bucket: complete after state_dict() or inside / behind ema_weights()
+        (they gather the shards); between steps a rank holds its own shard's average only."""
+        self._need_ema("ema_state")
+        return {k: self.ema[o:o + n].view(shape) for k, (o, n, shape) in self.engine.store.slots.items()}
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: on entry the parameter buffer and the average are exchanged in place (mt_swap_f32) and the
+        fp16 operand caches refreshed, on exit they are exchanged back and refreshed again.  No address changes, so captured graphs --
+        an EmbeddingExtractor's included -- stay valid and simply see the average.  Data parallel: a COLLECTIVE on entry (the shards of
+        the average are gathered), every rank enters at the same position.  Inside, step / step_graphed / finish_window / state_dict /
+        load_state_dict raise; so do nesting and entering inside an open accumulation window."""
+        self._need_ema("ema_weights")
+        self._not_averaged("ema_weights()")
+        if self.window_pos > 0:
+            raise RuntimeError(f"ema_weights() inside an open accumulation window ({self.window_pos} of {self.accumulate} micro-steps): "
+                               "call finish_window() first, or evaluate at a boundary")
+        eng, store = self.engine, self.engine.store
+        if store.sync is not None:
+            store.sync()                          # a parameter gather in flight writes into the buffer about to be exchanged
+        self.reducer.gather_shards_(self.ema)
+        ops.swap_f32(store.flat, self.ema, store.n_flat)
+        self._ema_swapped = True
+        try:
+            eng.refresh_trainable_caches()
+            yield self
+        finally:
+            ops.swap_f32(store.flat, self.ema, store.n_flat)
+            self._ema_swapped = False
+            eng.refresh_trainable_caches()
 
     # frozen random text projector (train_modaltune.py:44-59,114-116)
     def set_projector(self, state: Dict[str, "np.ndarray | torch.Tensor"]):
@@ -479,7 +558,17 @@ class TrainStep:
         p, g = eng.store.flat, eng.store.flat_grad
         grouped = self._grouped()
         hp = [(q["lr_mult"], q["weight_decay"]) for q in self._pgroups] if grouped else None
+        ema = self.ema
+        if ema is not None:      # the grouped kernel's EMA form; without groups: a one-segment table, the bits of mt_adamw_step
+            seg_end, seg_group, nseg = (self._seg_end, self._seg_group, self._nseg) if grouped else (*self._ema_seg, 1)
+            hp = hp if grouped else [(1.0, self.wd)]
         for o, k in self.reducer.adam_pieces(n):      # one launch, or: everything but the sharded bucket + this rank's shards
+            if ema is not None:
+                ops.adamw_step_groups_ema(p[o:o + k], g[o:o + k], self.m[o:o + k], self.v[o:o + k], k, o, seg_end, seg_group, hp, self._lr,
+                                          self.betas[0], self.betas[1], self.eps, 0, ema[o:o + k], self.ema_decay, self.ema_warmup,
+                                          scale=scale, found_inf=self.found_inf, grad_mult=grad_mult, step_dev=self.step_dev,
+                                          lr_dev=self.lr_dev, nseg=nseg)
+                continue
             if grouped:      # (the piece's absolute position picks its segments out of the one table)
                 ops.adamw_step_groups(p[o:o + k], g[o:o + k], self.m[o:o + k], self.v[o:o + k], k, o, self._seg_end, self._seg_group, hp,
                                       self._lr, self.betas[0], self.betas[1], self.eps, 0, scale=scale, found_inf=self.found_inf,
@@ -530,6 +619,7 @@ class TrainStep:
         """One train step on one slide, eager launches.  Returns the (device) loss scalar; no host sync happens here.  With
         accumulate > 1 the call is a micro-step or the boundary of its window (see __init__); update=False (gradients only, nothing
         else moves) has no meaning inside a window and raises there."""
+        self._not_averaged("step()")
         if self.accumulate > 1 and not update:
             raise ValueError("step(update=False) is not defined with accumulate > 1: micro-steps accumulate by themselves")
         first, boundary = self._window_role()
@@ -551,6 +641,7 @@ class TrainStep:
     def finish_window(self):
         """Apply a partial window (an epoch ended inside it): the boundary's reduce, check, clip and AdamW over the MEAN of the
         micro-steps seen, eagerly.  A no-op on an empty window.  Data parallel: every rank calls it at the same position."""
+        self._not_averaged("finish_window()")
         if self.window_pos == 0:
             return
         seen, self.window_pos = self.window_pos, 0
@@ -564,6 +655,7 @@ class TrainStep:
         host calls); up to `graph_cache_size` geometries stay captured (LRU).  Inputs are uploaded into static buffers
         first.  With world_size > 1 the capture is cut where a gradient bucket becomes final: the reducer starts that
         bucket's all-reduce between two replays, and the optimiser graph runs after the wait."""
+        self._not_averaged("step_graphed()")
         eng = self.engine
         if not eng._caches_ready:
             eng._build_caches()
@@ -683,7 +775,7 @@ class TrainStep:
         import time
         eng = self.engine
         saved = [(t, t.clone()) for t in (eng.store.flat, self.m, self.v, self.step_dev, self.scale, self.tracker, self.found_inf, eng.rng,
-                                          self._clip_out)]
+                                          self._clip_out) + (() if self.ema is None else (self.ema,))]
         was_auto, self.auto_split = self.auto_split, False
         timer, self.step_timer = self.step_timer, None      # (the trial's replays are not steps of the epoch)
         k_window = self.accumulate
@@ -798,6 +890,7 @@ class TrainStep:
         the same position, the moments of the sharded bucket are all-gathered from their owners, every rank returns the same complete
         dict (rank 0 writes it); inside an open window it raises there (micro-step gradients are rank-local): finish_window() first."""
         from . import _lib, checkpoint
+        self._not_averaged("state_dict()")
         eng, store = self.engine, self.engine.store
         world = self._world()
         if world > 1 and self.window_pos > 0:
@@ -807,8 +900,12 @@ class TrainStep:
             store.sync()
         self.reducer.gather_shards_(self.m)
         self.reducer.gather_shards_(self.v)
-        sums = torch.empty(3, dtype=torch.int64, device=self.dev)
-        for i, t in enumerate((store.flat, self.m, self.v)):
+        sealed = (store.flat, self.m, self.v)
+        if self.ema is not None:      # (the average of the sharded bucket lives with its owners, like the moments)
+            self.reducer.gather_shards_(self.ema)
+            sealed += (self.ema,)
+        sums = torch.empty(len(sealed), dtype=torch.int64, device=self.dev)
+        for i, t in enumerate(sealed):
             self._checksum_into(t, sums[i:i + 1])
         sums = [checkpoint.as_unsigned(c) for c in sums.cpu().tolist()]
         names = list(store.slots)
@@ -818,13 +915,16 @@ class TrainStep:
             window = {"pos": int(self.window_pos), "accumulate": int(self.accumulate), "grad_scale": float(self.grad_scale),
                       "grad": store.flat_grad.detach().cpu()}
         hyper = {"lr": self._lr, "betas": self.betas, "eps": self.eps, "weight_decay": self.wd}
-        return {"format": checkpoint.FORMAT,
+        extra = {}
+        if self.ema is not None:      # ONE optional key (and its checksum): without an average the key set is what it always was
+            extra["ema"] = checkpoint.pack_ema(self.ema, store.slots, self.ema_decay, self.ema_warmup)
+        return {**extra, "format": checkpoint.FORMAT,
                 "model": {k: store.tensors[k].detach().cpu().clone() for k in keys},
                 "optimizer": checkpoint.pack_optimizer(self.m, self.v, int(self.step_dev), store.slots, names, hyper, groups=self._pgroups),
                 "scaler": checkpoint.pack_scaler(float(self.scale), int(self.tracker), self.growth_interval),
                 "rng": eng.rng.detach().cpu().clone(), "stochastic": bool(eng.stochastic), "lr": float(self._lr), "window": window,
                 "schedule": {"split_decisions": {int(k): bool(v) for k, v in self.split_decisions.items()}},
-                "checksums": {"flat": sums[0], "m": sums[1], "v": sums[2]},
+                "checksums": {"flat": sums[0], "m": sums[1], "v": sums[2], **({"ema": sums[3]} if self.ema is not None else {})},
                 "build_id": _lib.build_info()["build_id"], "world": int(world),
                 "config": checkpoint.config_dict(eng.cfg, store.group_sizes)}
 
@@ -840,6 +940,7 @@ class TrainStep:
         every rank loads the complete state (a rank never reads the moments outside its shard)."""
         import warnings
         from . import _lib, checkpoint
+        self._not_averaged("load_state_dict()")
         eng, store = self.engine, self.engine.store
         full = checkpoint.check_format(sd)
         names = list(store.slots)
@@ -847,6 +948,7 @@ class TrainStep:
         flat, m, v, step, hyper = checkpoint.flat_buffers(sd, store.slots, store.n_flat)
         scaler = checkpoint.unpack_scaler(sd["scaler"]) if len(sd["scaler"]) else None      # ({}: a disabled GradScaler -- the scaler stays)
         window = sd["window"] if full else None
+        ema_in = checkpoint.unpack_ema(sd["ema"], store.slots, store.n_flat) if "ema" in sd else None      # (flat, decay, warm-up)
         if full and bool(sd["stochastic"]) != bool(eng.stochastic):
             raise ValueError(f"checkpoint: written with stochastic={bool(sd['stochastic'])}, this engine runs stochastic={bool(eng.stochastic)} "
                              "(Engine.set_stochastic): the Philox state would mean something else")
@@ -888,6 +990,16 @@ class TrainStep:
         # the checkpoint's groups win over the constructor's, as its hyper-parameters do (a uniform checkpoint: no groups); the table
         # lands in place, captures are dropped when what they hold of the groups differs
         self._set_groups(hyper.get("groups"))
+        # the average: the checkpoint's, with its decay and warm-up flag (they win like the hyper-parameters; captures that hold others
+        # are dropped); a checkpoint without one starts the average at the loaded parameters; a step without one ignores it
+        if self.ema is not None and ema_in is not None:
+            self.ema.copy_(ema_in[0])      # (zero slot padding, like the moments)
+            self.set_ema_decay(ema_in[1], ema_in[2])
+        elif self.ema is not None:
+            warnings.warn("checkpoint: no `ema` entry (written by a step without an average): the average starts at the loaded parameters")
+            self.ema.copy_(store.flat)
+        elif ema_in is not None:
+            warnings.warn("checkpoint: its `ema` entry is ignored, this TrainStep keeps no average (ema_decay=None)")
         self.set_lr(sd["lr"] if full else hyper["lr"])
         self.found_inf.zero_()
         self.window_pos = 0
@@ -903,10 +1015,13 @@ class TrainStep:
         else:
             eng.refresh_trainable_caches()
         if full and verify:
-            sums = torch.empty(3, dtype=torch.int64, device=self.dev)
-            for i, t in enumerate((store.flat, self.m, self.v)):
+            sealed = {"flat": store.flat, "m": self.m, "v": self.v}
+            if self.ema is not None and ema_in is not None and "ema" in sd["checksums"]:
+                sealed["ema"] = self.ema
+            sums = torch.empty(len(sealed), dtype=torch.int64, device=self.dev)
+            for i, t in enumerate(sealed.values()):
                 self._checksum_into(t, sums[i:i + 1])
-            for name, have in zip(("flat", "m", "v"), sums.cpu().tolist()):
+            for name, have in zip(sealed, sums.cpu().tolist()):
                 have, want = checkpoint.as_unsigned(have), checkpoint.as_unsigned(sd["checksums"][name])
                 if have != want:
                     raise RuntimeError(f"checkpoint: checksum of `{name}` on the device is {have:#018x} after the load, the checkpoint "
@@ -929,6 +1044,15 @@ class TrainStep:
         not its mean), and it is never clipped: max_grad_norm acts inside AdamW, the buffer keeps the raw gradient."""
         s = float(self.grad_scale)
         return {k: g / s for k, g in self.engine.store.grads.items()}
+
+
+def _valid_ema_decay(decay) -> Optional[float]:
+    """None (no average) or the decay as a float in [0, 1) -- mt_adamw_step_groups_ema's range; anything else: ValueError."""
+    if decay is None:
+        return None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) < 1.0:
+        raise ValueError(f"ema_decay must be None or a number in [0, 1) (got {decay!r})")
+    return float(decay)
 
 
 def ops_l2norm_rows(h: torch.Tensor, out: torch.Tensor, rows: Sequence[int]):

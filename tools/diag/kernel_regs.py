@@ -7,7 +7,8 @@ existing kernels as they were:
 
 A kernel that gained a trailing defaulted `bool` template parameter (`template <..., bool DET = false>`) is matched with its old symbol:
 the `false` instantiation IS the old kernel -- also when the new forms bring trailing kernel parameters along (`DropArgs drop` of the
-prompt self-attention's DROP forms), which the `false` instantiation never reads."""
+prompt self-attention's DROP forms), which the `false` instantiation never reads -- and when the kernel was no template before
+(`adamw_groups_kernel<EMA>`: its qualified name is compared, the template argument list renumbers the parameter list's substitutions)."""
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 
@@ -39,6 +40,18 @@ def load(path):
     return {(l.split()[0], l.split()[1]): l.split()[2:] for l in open(path) if l.strip() and not l.startswith("#")}
 
 
+def nested_name(sym):
+    """`_ZN<len><id>...` of a mangled symbol up to the end of its last length-prefixed identifier (None: not a nested name)."""
+    if not sym.startswith("_ZN"):
+        return None
+    i = 3
+    while True:
+        m = re.match(r"\d+", sym[i:])
+        if not m:
+            return sym[:i] if i > 3 else None
+        i += len(m.group(0)) + int(m.group(0))
+
+
 def diff(old_path, new_path):
     old, new = load(old_path), load(new_path)
 
@@ -52,6 +65,11 @@ def diff(old_path, new_path):
         for c in new:         # ... and with it trailing kernel parameters that only the `true` form reads (their mangled types follow the old list)
             if c[0] == f and "Lb0EE" in c[1] and c[1].replace("Lb0EE", "E", 1).startswith(n):
                 return c
+        q = nested_name(n)    # ... and a kernel that was NO template before: its new template argument list renumbers the substitutions
+        if q is not None and n[len(q)] == "E":      # (S0_ -> S1_) of the parameter list, so only the qualified name is compared
+            for c in new:
+                if c[0] == f and c[1].startswith(q + "ILb0EEEv"):
+                    return c
         return None
     pairs = {k: twin(k) for k in old}
     gone = [k for k, t in pairs.items() if t is None]
