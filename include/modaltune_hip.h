@@ -52,7 +52,7 @@ typedef struct {
 
 /* major * 100 + minor * 10.  3.0: the optional inputs of a launcher travel in MtLaunchOpts; the suffixed twin entries (_eps, _det, _grid,
  * _live) of 2.x are gone, so a 2.x caller does not link against this library.  3.1: + mt_token_mha_fwd_drop / _bwd_drop.  3.2: + mt_patch_points_fwd / mt_patch_ig_accumulate.
- * 3.3: + mt_checksum64.  3.4: + mt_adamw_step_groups.  3.5: + mt_adamw_step_groups_ema, mt_swap_f32. */
+ * 3.3: + mt_checksum64.  3.4: + mt_adamw_step_groups.  3.5: + mt_adamw_step_groups_ema, mt_swap_f32.  3.6: + mt_layernorm_pool_fwd. */
 int mt_version(void);
 const char* mt_status_string(int status);
 /* Build provenance: sha256 (hex) over the kernel sources, this header and the compiler flags the library was built from
@@ -203,6 +203,34 @@ int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype
  * h (fp32, != x) receives the new residual stream, stats the (mean, rstd) rows.  D = 768.  opt: eps. */
 int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const MtDropout* drop, const float* w, const float* b,
                          float* h, mt_half* y, float* stats, int M, int D, const MtLaunchOpts* opt, mt_stream_t stream);
+
+/* Pooled read-out of the plain slide encoder, LayerNorm on either side of a row mean:
+ *   out[b, :] = LN_post( 1 / (r1 - r0) * sum_{r in [r0, r1)} LN_pre( x[b, r, :] ) )
+ * x fp32 [B][rows_per_pass][D] with row stride ldx >= D (ldx % 4 == 0, 16-byte aligned), [r0, r1) a row range inside every pass, out
+ * fp32 [B, D].  LN_pre (pre_w, pre_b: both or neither; pre_eps) and LN_post (post_w, post_b: both or neither; post_eps) are each
+ * optional; an eps of 0 is the reference's 1e-5, a negative or NaN one MT_ERR_BAD_ARG.  The two epsilons are plain arguments -- one
+ * MtLaunchOpts.eps could not carry both, and nothing else of MtLaunchOpts applies -- so this entry takes no options pointer.
+ * D = 768 (else MT_ERR_UNSUPPORTED).  The four read-outs of LongNetViT.forward
+ * (gigapath/slide_encoder.py:277-285) over Encoder.layer_forward's two results are this one launch:
+ *   encoder_out (torchscale/architecture/encoder.py:425-426, SE:279-285)  cls:  rows [0, 1), pre = encoder.layer_norm, post = norm
+ *                                                                          pool: rows [1, N), pre = encoder.layer_norm, post = norm
+ *   encoder_states (ENC:400-422; all_layer_embed, no encoder.layer_norm)   cls:  rows [0, 1), post = norm;  pool: rows [1, N), post = norm
+ * `norm` carries eps 1e-6 (SE:368-377), encoder.layer_norm the encoder's 1e-5.
+ * The selected rows are read once and nothing outside [r0, r1) is read.  Precision: the row statistics are those of mt_layernorm_fwd
+ * (fp32 mean, centred second moment, one wave per row); each normalised row is added to DOUBLE column sums, waves and workgroups are
+ * added in double too, and the mean is rounded to fp32 once -- so against fp64 the pooled vector carries the error of one fp32
+ * LayerNorm row (averaged, not accumulated, over the rows) and LN_post adds that of one more fp32 LayerNorm.  The summation order is a
+ * function of (r1 - r0, D) alone and no floating-point atomic executes: the same input gives the same bits.
+ * Workspace: ranges of more than 64 rows are split over workgroups (64 rows each); every workgroup stores its column sums to its own
+ * slot of `partials` (device doubles, 8-byte aligned, at least mt_layernorm_pool_partials_elems(B, r1 - r0, D) of them, no
+ * initialisation needed) and one workgroup per pass adds the slots in ascending order.  A short workspace: MT_ERR_BAD_ARG before any
+ * launch; partials may be NULL where the query returns 0. */
+int mt_layernorm_pool_fwd(const float* x, long ldx, int B, int rows_per_pass, int r0, int r1, const float* pre_w, const float* pre_b,
+                          float pre_eps, const float* post_w, const float* post_b, float post_eps, float* out, double* partials,
+                          long partials_elems, int D, mt_stream_t stream);
+/* host arithmetic: the doubles mt_layernorm_pool_fwd needs for B passes of `rows` = r1 - r0 rows (0: one workgroup per pass, no
+ * workspace); negative MtStatus for B < 1, rows < 1 or a width it does not serve */
+long mt_layernorm_pool_partials_elems(int B, int rows, int D);
 
 /* dx (+)= LN backward.  dy fp16 or fp32 [M,D]; x as in forward (gelu_in: also backprop through the GELU).
  * dx_dtype F32 with accumulate=1 adds into the fp32 residual-gradient stream (ENC:137-154 backward);

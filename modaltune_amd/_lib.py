@@ -102,6 +102,8 @@ SIGNATURES = {
     "mt_layernorm_fwd": [P, L, RM, I, I, P, P, P, I, P, L, RM, I, P, I, I, OP, P],
     "mt_add_layernorm_fwd": [P, P, DR, P, P, P, P, P, I, I, OP, P],
     "mt_layernorm_bwd": [P, L, RM, I, P, L, RM, I, I, P, P, P, L, RM, I, I, P, P, P, DR, I, I, OP, P],
+    "mt_layernorm_pool_fwd": [P, L, I, I, I, I, P, P, F, P, P, F, P, P, L, I, P],
+    "mt_layernorm_pool_partials_elems": [I, I, I],
     # (OP = the options pointer, directly in front of the stream: include/modaltune_hip.h says which fields each launcher honours)
     "mt_droppath_live": [P, P, I, I, P, P, P],
     "mt_dilated_attn_fwd": [P, PL, P, P, OP, P],
@@ -194,7 +196,7 @@ SIGNATURES = {
 }
 _RESTYPE = {"mt_status_string": C.c_char_p, "mt_build_id": C.c_char_p, "mt_dilated_attn_bwd_workspace_bytes": C.c_long, "mt_pool_attn_workspace_floats": C.c_long,
              "mt_alibi_dist_halves": C.c_long, "mt_grad_sumsq_partials_elems": C.c_long,
-             "mt_checksum64_partials_elems": C.c_long,
+             "mt_checksum64_partials_elems": C.c_long, "mt_layernorm_pool_partials_elems": C.c_long,
              **{n + "_det_elems": C.c_long for n in ("mt_gemm_tn_f16", "mt_colsum_f16", "mt_layernorm_bwd", "mt_inject_resid_bwd",
                                                      "mt_inject_attn_bwd_hd", "mt_extract_attn_bwd_hd")}}
 

@@ -498,6 +498,17 @@ class LongNetGeneAdapter(Aggregator):
             logits, maps = ex[1](x, coords, self._gene_list(genes), clinical if self.CLINICAL else None)
         return {"logits": logits, "tokens": token_legend(self.cfg), "maps": maps}
 
+    def slide_encoder(self, global_pool: Optional[bool] = None, return_feats: bool = False, **kwargs):
+        """The plain Prov-GigaPath slide encoder (slide_encoder.LongNetViT, in eval mode) over THIS model's frozen backbone tensors --
+        the same storage and fp16 weight caches, no second copy -- so the linear-probe baseline embedding and the ModalTune embedding
+        of a slide come from one process.  global_pool None: the config's; **kwargs: graphed, capture_after, graph_cache_size."""
+        from .slide_encoder import LongNetViT
+        cfg = self.cfg
+        return LongNetViT(in_chans=cfg.in_chans, embed_dim=cfg.embed_dim, depth=cfg.depth, slide_ngrids=cfg.slide_ngrids,
+                          tile_size=cfg.tile_size, max_wsi_size=cfg.max_wsi_size, global_pool=cfg.global_pool if global_pool is None else global_pool,
+                          dropout=cfg.dropout, drop_path_rate=cfg.drop_path_rate, return_feats=return_feats, mlp_ratio=cfg.mlp_ratio,
+                          engine=self.engine, **kwargs).eval()
+
     def integrated_gradients(self, x, coords, genes, target, task_ids=(0, 1, 2), steps: int = 64, baseline=None, clinical=None,
                              inputs: str = "genes", patch_baseline=None) -> Dict[str, Any]:
         """Integrated Gradients of F_t = <target_t, logits_t> over the gene inputs of one slide (README Figure 3 of the reference:

@@ -19,6 +19,7 @@ import numpy as np
 BACKBONE_HEADS = 16
 DILATED_RATIOS = (1, 2, 4, 8, 16)
 LN_EPS = 1e-5  # torchscale EncoderConfig.layernorm_eps (architecture/config.py:43); nn.LayerNorm default too
+GEOMETRY_MSG = "the HIP path is built for the Prov-GigaPath geometry (768-d, 16 heads x 48)"
 
 
 # model_configs/modaltune_gigapath_config.json:1-30 -- the configuration the reference trainer passes to the constructor
@@ -130,7 +131,7 @@ class ModelConfig:
             raise ValueError(f"prompt_dropout={self.prompt_dropout}: a dropout probability in [0, 1) (nn.Dropout refuses values outside "
                              "[0, 1], and 1 leaves nothing to scale)")
         if self.embed_dim != 768 or self.head_dim != 48:
-            raise ValueError("the HIP path is built for the Prov-GigaPath geometry (768-d, 16 heads x 48)")
+            raise ValueError(GEOMETRY_MSG)
         if self.prompt_agg not in ("avg", "cls") or self.token_agg not in ("sum", "cat"):
             raise NotImplementedError("prompt_agg must be 'avg' or 'cls'; token_agg 'sum' or 'cat' (the reference raises for anything else too)")
         if not self.add_prompt_feature:

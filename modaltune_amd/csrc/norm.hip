@@ -135,6 +135,139 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(AddLnArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- pooled read-out -------------------
+// out[b, :] = LN_post( 1 / (r1 - r0) * sum_{r in [r0, r1)} LN_pre( x[b, r, :] ) )  (mt_layernorm_pool_fwd, include/modaltune_hip.h).
+// Stage 1, grid (G, B): workgroup g of pass b owns the rows r0 + [g * POOL_WG_ROWS, (g + 1) * POOL_WG_ROWS) of the range; wave w walks
+// the rows w, w + 4, ... of that share in ascending order -- LN_pre as in ln_fwd_kernel (one wave per row, fp32 mean, centred second
+// moment), then the row is added to the lane's twelve DOUBLE column accumulators.  The four waves are added in ascending order through
+// LDS (doubles only: one LDS banking class, common.h).  G == 1: the workgroup finishes the pass itself; else it stores its D sums to
+// its own slot of the workspace and stage 2, one workgroup per pass, adds the G slots in ascending order.  Which rows a lane adds, and
+// in which order, is a function of (r1 - r0, D) alone; no atomic executes.
+constexpr int POOL_WG_ROWS = 64, POOL_D = 768;
+
+struct LnPoolArgs {
+  const float* x; long ldx; int rows_per_pass, r0, n;      // n = r1 - r0
+  const float* pre_w; const float* pre_b; float pre_eps;
+  const float* post_w; const float* post_b; float post_eps;
+  float* out; double* partials; int G;
+};
+
+// sum over the workgroup, every thread gets it; `red`: 4 doubles of LDS.  Two barriers: `red` may be reused right after.
+MT_DEVINL float pool_block_sum(float v, double* red) {
+  const float w = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = (double)w;
+  __syncthreads();
+  const float s = (float)red[0] + (float)red[1] + (float)red[2] + (float)red[3];
+  __syncthreads();
+  return s;
+}
+
+// colsum: the D column sums of pass b in LDS (complete, barrier passed).  Thread t owns the columns t, t + 256, t + 512: the mean is rounded to
+// fp32 once, LN_post (optional) takes the statistics of the fp32 vector the way ln_fwd_kernel does.
+MT_DEVINL void pool_finish(const LnPoolArgs& a, int b, const double* colsum, double* red) {
+  constexpr int D = POOL_D, NJ = D / 256;
+  const double inv_n = 1.0 / (double)a.n;
+  float p[NJ];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) { p[j] = (float)(colsum[threadIdx.x + 256 * j] * inv_n); s += p[j]; }
+  float* out = a.out + (long)b * D;
+  if (!a.post_w) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) out[threadIdx.x + 256 * j] = p[j];
+    return;
+  }
+  const float mean = pool_block_sum(s, red) * (1.0f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) { const float d = p[j] - mean; q += d * d; }
+  const float rstd = rsqrtf(pool_block_sum(q, red) * (1.0f / D) + a.post_eps);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int col = threadIdx.x + 256 * j;
+    out[col] = (p[j] - mean) * rstd * a.post_w[col] + a.post_b[col];
+  }
+}
+
+template <bool PRE>
+__global__ __launch_bounds__(256) void ln_pool_rows_kernel(LnPoolArgs a) {
+  constexpr int D = POOL_D, NC = D / 256;
+  __shared__ double acc_lds[4][D];
+  __shared__ double red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, g = blockIdx.x;
+  f32x4 wr[NC], br[NC];
+  if (PRE) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      wr[c] = Vec4<float>::load(a.pre_w + c * 256 + lane * 4);
+      br[c] = Vec4<float>::load(a.pre_b + c * 256 + lane * 4);
+    }
+  }
+  double acc[NC][4];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[c][e] = 0.0;
+  const int i_end = min(a.n, (g + 1) * POOL_WG_ROWS);
+  for (int i = g * POOL_WG_ROWS + wave; i < i_end; i += 4) {
+    const float* x = a.x + ((long)b * a.rows_per_pass + a.r0 + i) * a.ldx;
+    f32x4 v[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = Vec4<float>::load(x + c * 256 + lane * 4);
+    if (PRE) {
+      float s = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
+      const float mean = wave_sum(s) * (1.0f / D);
+      float q = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
+      const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + a.pre_eps);
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[c][e] = (v[c][e] - mean) * rstd * wr[c][e] + br[c][e];
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[c][e] += (double)v[c][e];
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc_lds[wave][c * 256 + lane * 4 + e] = acc[c][e];
+  __syncthreads();
+  for (int i = threadIdx.x; i < D; i += 256) {
+    const double t = ((acc_lds[0][i] + acc_lds[1][i]) + acc_lds[2][i]) + acc_lds[3][i];
+    if (a.G > 1) a.partials[((long)b * a.G + g) * D + i] = t;
+    else acc_lds[0][i] = t;          // (column i is read and written by this thread alone)
+  }
+  if (a.G > 1) return;               // (uniform over the grid)
+  __syncthreads();
+  pool_finish(a, b, acc_lds[0], red);
+}
+
+__global__ __launch_bounds__(256) void ln_pool_final_kernel(LnPoolArgs a) {
+  constexpr int D = POOL_D;
+  __shared__ double colsum[D];
+  __shared__ double red[4];
+  const int b = blockIdx.x;
+  const double* slot = a.partials + (long)b * a.G * D;
+  for (int i = threadIdx.x; i < D; i += 256) {
+    double t = slot[i];
+    for (int g = 1; g < a.G; ++g) t += slot[(long)g * D + i];
+    colsum[i] = t;
+  }
+  __syncthreads();
+  pool_finish(a, b, colsum, red);
+}
+
+int ln_pool_groups(int n) { return cdiv(n, POOL_WG_ROWS); }
+
 struct LnBwdArgs {
   const void* dy; long lddy; RowMap dymap;
   const void* x; long ldx; RowMap xmap;
@@ -713,6 +846,35 @@ extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const
   AddLnArgs a{x, (const h16*)branch, make_drop(drop), w, b, h, (h16*)y, stats, M, mt_opt_eps(opt)};
   hipLaunchKernelGGL((add_ln_fwd_kernel<768>), dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, a);
   MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+extern "C" long mt_layernorm_pool_partials_elems(int B, int rows, int D) {
+  if (B < 1 || rows < 1 || D != POOL_D) return MT_ERR_BAD_ARG;
+  const int G = ln_pool_groups(rows);
+  return G > 1 ? (long)B * G * D : 0;
+}
+
+extern "C" int mt_layernorm_pool_fwd(const float* x, long ldx, int B, int rows_per_pass, int r0, int r1, const float* pre_w,
+                                     const float* pre_b, float pre_eps, const float* post_w, const float* post_b, float post_eps,
+                                     float* out, double* partials, long partials_elems, int D, mt_stream_t stream) {
+  if (!x || !out || B < 1 || B > 65535 || rows_per_pass < 1 || r0 < 0 || r1 <= r0 || r1 > rows_per_pass || ldx < D || (ldx & 3) ||
+      ((uintptr_t)x & 15) || ((uintptr_t)pre_w & 15) || ((uintptr_t)pre_b & 15) || (!pre_w) != (!pre_b) ||
+      (!post_w) != (!post_b) || !(pre_eps >= 0.f) || !(post_eps >= 0.f) || partials_elems < 0)
+    return MT_ERR_BAD_ARG;
+  if (D != POOL_D) return MT_ERR_UNSUPPORTED;
+  const int n = r1 - r0, G = ln_pool_groups(n);
+  if (G > 1 && (!partials || ((uintptr_t)partials & 7) || partials_elems < (long)B * G * D)) return MT_ERR_BAD_ARG;
+  LnPoolArgs a{x, ldx, rows_per_pass, r0, n, pre_w, pre_b, pre_eps != 0.f ? pre_eps : 1e-5f, post_w, post_b, post_eps != 0.f ? post_eps : 1e-5f,
+               out, partials, G};
+  hipStream_t s = (hipStream_t)stream;
+  if (pre_w) hipLaunchKernelGGL(ln_pool_rows_kernel<true>, dim3(G, B), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ln_pool_rows_kernel<false>, dim3(G, B), dim3(256), 0, s, a);
+  MT_CHECK_LAUNCH();
+  if (G > 1) {
+    hipLaunchKernelGGL(ln_pool_final_kernel, dim3(B), dim3(256), 0, s, a);
+    MT_CHECK_LAUNCH();
+  }
   return MT_OK;
 }
 

@@ -782,7 +782,7 @@ extern "C" int mt_row_absmax_f32(const float* x, float* out, int M, int D, mt_st
   return MT_OK;
 }
 
-extern "C" int mt_version(void) { return 350; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64, 3.4: mt_adamw_step_groups, 3.5: mt_adamw_step_groups_ema / mt_swap_f32; the binary itself is identified by mt_build_id(), not by this number)
+extern "C" int mt_version(void) { return 360; }      // (3.0: MtLaunchOpts, 3.1: the _drop forms of mt_token_mha_*, 3.2: mt_patch_points_fwd / mt_patch_ig_accumulate, 3.3: mt_checksum64, 3.4: mt_adamw_step_groups, 3.5: mt_adamw_step_groups_ema / mt_swap_f32, 3.6: mt_layernorm_pool_fwd; the binary itself is identified by mt_build_id(), not by this number)
 
 extern "C" const char* mt_status_string(int status) {
   switch (status) {

@@ -35,9 +35,9 @@ class ParamStore:
     buffer (16-byte aligned slots, state_dict order) with a matching flat gradient buffer, so AdamW and the
     data-parallel gradient all-reduce are one launch / one collective each."""
 
-    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device):
+    def __init__(self, cfg: ModelConfig, group_sizes: Sequence[int], device, specs=None):
         self.cfg, self.group_sizes, self.device = cfg, list(group_sizes), device
-        self.specs = param_specs(cfg, group_sizes)
+        self.specs = param_specs(cfg, group_sizes) if specs is None else list(specs)
         off = 0
         self.slots: Dict[str, tuple] = {}
         for k, shape, kind, train in self.specs:
@@ -193,6 +193,7 @@ class Engine:
     ROWS_FROM_STAGING = False         # the row count of a slide is only known behind stage_slide()'s read-back (else: its patch count)
     PASS_GROUPS = True                # pass groups are a schedule of this engine's callers (False: only TrainStep's, and only when forced)
     MODULE_REPLAY = True              # module_graph.ModuleReplay can capture this engine's calls (it stages with stage_inputs)
+    PARAM_SPECS = staticmethod(param_specs)      # (cfg, group_sizes) -> the tensors of the store (slide_encoder.BackboneEngine: the frozen ones alone)
 
     @property
     def replayable(self) -> bool:
@@ -213,7 +214,7 @@ class Engine:
         cfg.validate()
         self.cfg, self.device = cfg, torch.device(device)
         self.group_sizes = list(group_sizes)
-        self.store = ParamStore(cfg, group_sizes, self.device)
+        self.store = ParamStore(cfg, group_sizes, self.device, specs=self.PARAM_SPECS(cfg, group_sizes))
         self.tape = Tape(self.device)
         self._fresh_arenas = {"need": 0, "pool": []}      # gradient arenas of the per-call tapes (module API), see Tape.__init__
         self.tape.on_realloc = self._bump_generation

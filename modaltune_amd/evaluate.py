@@ -187,7 +187,8 @@ def attention_to_grid(weights, coords, tile: float = 256.0) -> np.ndarray:
 
 
 def get_features(extractor: EmbeddingExtractor, slides: Iterable[Dict]) -> Tuple[np.ndarray, List]:
-    """Host-side collection as TM:262-327 does per split: returns (features [n, tasks, O], case ids)."""
+    """Host-side collection as TM:262-327 does per split: returns (features [n, tasks, O], case ids).  `extractor`: an
+    EmbeddingExtractor, or slide_encoder.BaselineFeatures for the plain slide encoder's features [n, 768] of the same slide dicts."""
     feats, ids = [], []
     for s in slides:
         feats.append(extractor(s["x"], s["coords"], s["genes"], s.get("clinical")).float().cpu().numpy())

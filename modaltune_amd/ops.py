@@ -190,6 +190,28 @@ def add_layernorm_fwd(x, branch, w, b, h, y, stats, M, D, drop=None, eps=1e-5):
                                            _opts("add_layernorm_fwd", eps=eps), _s()), "add_layernorm_fwd")
 
 
+def layernorm_pool_partials_elems(B: int, rows: int, D: int = 768) -> int:
+    """float64 elements of workspace layernorm_pool_fwd needs for B passes of `rows` = r1 - r0 selected rows (0: none)."""
+    n = int(_lib.load().mt_layernorm_pool_partials_elems(B, rows, D))
+    if n < 0:
+        check(n, "layernorm_pool_partials_elems")
+    return n
+
+
+def layernorm_pool_fwd(x, B, rows_per_pass, r0, r1, out, *, pre=None, post=None, pre_eps=1e-5, post_eps=1e-5, partials=None,
+                       ldx=None, D=768):
+    """out[b] = LN_post(mean over the rows [r0, r1) of pass b of LN_pre(x[b, r])) (include/modaltune_hip.h: mt_layernorm_pool_fwd).
+    x fp32 [B * rows_per_pass, ldx]; pre / post: (weight, bias) or None; partials: float64 workspace of at least
+    layernorm_pool_partials_elems(B, r1 - r0) elements (None where that is 0)."""
+    pw, pb = pre if pre is not None else (None, None)
+    qw, qb = post if post is not None else (None, None)
+    if not (pre_eps > 0 and post_eps > 0):      # (0 would read as "the default" over there)
+        check(-1, "layernorm_pool_fwd")
+    check(_lib.load().mt_layernorm_pool_fwd(_p(x), ldx if ldx is not None else D, B, rows_per_pass, r0, r1, _p(pw), _p(pb), float(pre_eps), _p(qw),
+                                            _p(qb), float(post_eps), _p(out), _p(partials), 0 if partials is None else partials.numel(), D,
+                                            _s()), "layernorm_pool_fwd")
+
+
 def layernorm_bwd(dy, x, w, stats, dx, M, D, *, lddy=None, dymap=None, ldx=None, xmap=None, lddx=None, dxmap=None,
                   gelu_in=False, accumulate=False, dw=None, db=None, dx16=None, dx16_drop=None, det=None, live=None, live_rows=0):
     if live is not None and dw is not None:
@@ -367,6 +389,7 @@ def struct_of(cls, **tensors):
 # are filled in; a pair is (key without, key with) the entry's variant -- forward: `pend` given, backward: `dh16_valid` -- and None
 # a step that does not run then; LayerNorms over <= 1024 rows file under "token_side" like their per-op wrappers do.
 LAYER_ALL = 0x7FFFFFFF
+LNF_ATTENTION, LNF_FFN = 0x00F, 0x1C0      # mt_longnet_layer_fwd: LN1 | QKV | ATTN | MIX (up to out_proj's operand) and FC1 | FFN_LN | FC2
 LAYER_STEPS = {
     "longnet_layer_fwd": (("layernorm_fwd[{D}]", "add_layernorm_fwd[{D}]"), "gemm_nt[{M}x{Q}x{D}]", "dilated_attn_fwd", "dilated_mix_ln_fwd",
                           "gemm_nt[{M}x{D}x{D}]", "add_layernorm_fwd[{D}]", "gemm_nt[{M}x{F}x{D}]", "layernorm_fwd[{F}]", "gemm_nt[{M}x{D}x{F}]"),

@@ -104,6 +104,28 @@ def _layernorm_bwd(dy: Tensor, x: Tensor, w: Tensor, stats: Tensor) -> Tensor:
 _op("layernorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor stats) -> Tensor")((_layernorm_bwd, lambda dy, x, w, stats: x.new_empty(x.shape)))
 
 
+# ---- pooled read-out of the plain slide encoder: LN_post(mean over rows [r0, r1) of LN_pre(x)) per pass
+def _layernorm_pool_fwd(x: Tensor, r0: int, r1: int, pre_w: Optional[Tensor], pre_b: Optional[Tensor], pre_eps: float,
+                        post_w: Optional[Tensor], post_b: Optional[Tensor], post_eps: float) -> Tensor:
+    """x fp32 [B, rows, 768]; pre_* / post_*: both tensors of a LayerNorm or neither -> fp32 [B, 768]."""
+    _need(x, F32, "x", 3)
+    B, rows, D = x.shape
+    for t, nm in ((pre_w, "pre_w"), (pre_b, "pre_b"), (post_w, "post_w"), (post_b, "post_b")):
+        if t is not None:
+            _need(t, F32, nm, 1)
+    if (pre_w is None) != (pre_b is None) or (post_w is None) != (post_b is None) or not 0 <= r0 < r1 <= rows:
+        raise RuntimeError("modaltune_hip::layernorm_pool_fwd: weight and bias of a LayerNorm come together, 0 <= r0 < r1 <= rows")
+    out = torch.empty(B, D, dtype=F32, device=x.device)
+    ne = ops.layernorm_pool_partials_elems(B, r1 - r0, D)
+    part = torch.empty(ne, dtype=torch.float64, device=x.device) if ne else None
+    ops.layernorm_pool_fwd(x, B, rows, r0, r1, out, pre=None if pre_w is None else (pre_w, pre_b), post=None if post_w is None else (post_w, post_b),
+                           pre_eps=pre_eps, post_eps=post_eps, partials=part, D=D)
+    return out
+
+
+_op("layernorm_pool_fwd(Tensor x, int r0, int r1, Tensor? pre_w, Tensor? pre_b, float pre_eps, Tensor? post_w, Tensor? post_b, "
+    "float post_eps) -> Tensor")((_layernorm_pool_fwd, lambda x, *a: x.new_empty((x.shape[0], x.shape[2]))))
+
 # ---- LongNet dilated attention: all branches, branch mix + inner LayerNorm (DA:146-262)
 def _dilated_attention_fwd(qkv_hm: Tensor, N: int, B: int, seg: List[int], ratio: List[int], ln_w: Tensor, ln_b: Tensor):
     """qkv_hm: fp16 head-major [3][16][B*N][48] with q pre-scaled by MT_QK_SCALE_LOG2.  Returns (y fp16 [B*N, 768], o_br, lse_br,
