@@ -193,7 +193,7 @@ int mt_sgemm_multi(const MtSgemm* probs, int n, mt_stream_t stream);
  * opt: eps, live.  eps: the default is the reference's 1e-5 (ENC / AM / GE LayerNorms); the TITAN ViT's LayerNorms carry their own, e.g.
  * timm's 1e-6 (the backward needs none: it reads the saved rstd).  live (live_rows rows per pass): only the rows of the live passes, for
  * the fp16 GELU form (D = 3072: the FFN's sub-LayerNorm, a LayerNorm INSIDE a branch); every other form with a table:
- * MT_ERR_UNSUPPORTED. */
+ * MT_ERR_UNSUPPORTED.  Rows are read and written with 8- and 16-byte vector accesses: ldx % 4 == 0 and ldy % 4 == 0, else MT_ERR_BAD_ARG. */
 int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w,
                      const float* b, const float* add_rows, int add_period, void* y, long ldy, const MtRowMap* ymap,
                      int out_dtype, float* stats, int M, int D, const MtLaunchOpts* opt, mt_stream_t stream);
@@ -242,7 +242,8 @@ long mt_layernorm_pool_partials_elems(int B, int rows, int D);
  * rows per pass): dy of a row outside the live passes counts as ZERO whatever its bytes are -- then an accumulating dx passes through
  * unchanged and dx_f16 is still written, which is what exact-zero dy rows give.  The fp16 GELU form (the FFN's sub-LayerNorm) instead
  * walks the live rows only and leaves the other rows of dx untouched; the other GELU forms and a trainable norm (dw / db) take no
- * table: MT_ERR_UNSUPPORTED.  partials: the deterministic form (end of this header), dw and db required. */
+ * table: MT_ERR_UNSUPPORTED.  partials: the deterministic form (end of this header), dw and db required.
+ * lddy, ldx and lddx are multiples of 4 elements as in the forward (vector accesses per row), else MT_ERR_BAD_ARG. */
 int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap, int dy_dtype, const void* x, long ldx,
                      const MtRowMap* xmap, int in_dtype, int gelu_in, const float* w, const float* stats, void* dx,
                      long lddx, const MtRowMap* dxmap, int dx_dtype, int accumulate, float* dw, float* db,
@@ -588,7 +589,7 @@ int mt_copy_rows_f32(const float* src, long lds, const MtRowMap* smap, float* ds
                      int M, int D, int accumulate, mt_stream_t stream);
 /* Injector residual-path backward (A.1): dres(m,:) += (1 + g) * dy(m,:) for the patch rows; also reduces
  * dgamma[n] += sum_m dy(m,n) * (x(m,n) + proj(m,n)) where proj = a @ Wo^T + bo is recomputed by the caller as
- * fp16 `proj`.  opt: partials. */
+ * fp16 `proj`.  opt: partials.  lddy, ldx, lddx % 4 == 0 (16-byte vector accesses per row), else MT_ERR_BAD_ARG. */
 int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* dymap, const float* x, long ldx,
                         const MtRowMap* xmap, const mt_half* proj, const float* gamma, float* dx, long lddx,
                         const MtRowMap* dxmap, int dx_accumulate, mt_half* dproj, float* dgamma, int M, int D,

@@ -917,7 +917,8 @@ extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap
   const int live_rows = opt ? opt->live_rows : 0;
   float* partials = mt_opt_partials(opt);
   if (live && partials) return MT_ERR_UNSUPPORTED;
-  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (partials && !dw) || (live && live_rows < 1))
+  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (partials && !dw) || (live && live_rows < 1) ||
+      (lddy & 3) || (ldx & 3) || (lddx & 3))      // (8- and 16-byte vector accesses per row, as in mt_layernorm_fwd)
     return MT_ERR_BAD_ARG;
   if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
   if (live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
@@ -1058,7 +1059,7 @@ extern "C" int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* d
                                    int D, const MtLaunchOpts* opt, mt_stream_t stream) {
   if (int rc = mt_opts_check(opt, MT_OPT_PARTIALS)) return rc;
   float* partials = mt_opt_partials(opt);
-  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 ||
+  if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 || (lddy & 3) || (ldx & 3) || (lddx & 3) ||
       (partials && opt->partials_elems < mt_inject_resid_bwd_det_elems(M, D)))
     return MT_ERR_BAD_ARG;
   InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
