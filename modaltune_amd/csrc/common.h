@@ -74,16 +74,20 @@ MT_DEVINL float wave_max(float v) {
 // erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32-level for the fp16-stored activations):
 // erf(z) = 1 - (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z >= 0.  About 14 VALU ops against ~40 for erff();
 // the FFN's GELU (feedforward_network.py:136) and its derivative were the VALU bound of the LN-3072 kernels.
+// The constants of both forms, this scalar one and the packed gelu_pair of norm.hip:
+constexpr float MT_ERF_P = 0.3275911f, MT_ERF_A1 = 0.254829592f, MT_ERF_A2 = -0.284496736f, MT_ERF_A3 = 1.421413741f,
+                MT_ERF_A4 = -1.453152027f, MT_ERF_A5 = 1.061405429f;
+constexpr float MT_RSQRT2 = 0.70710678118654752440f, MT_LOG2E = 1.4426950408889634f, MT_RSQRT_2PI = 0.39894228040143267794f;
 // Returns erf(x / sqrt 2) and e = exp(-x^2 / 2) (shared with the derivative).
 MT_DEVINL float erf_rsqrt2(float x, float& e) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
-  float poly = fmaf(t, 1.061405429f, -1.453152027f);
-  poly = fmaf(poly, t, 1.421413741f);
-  poly = fmaf(poly, t, -0.284496736f);
-  poly = fmaf(poly, t, 0.254829592f);
+  const float z = fabsf(x) * MT_RSQRT2;
+  const float t = __builtin_amdgcn_rcpf(fmaf(MT_ERF_P, z, 1.0f));
+  float poly = fmaf(t, MT_ERF_A5, MT_ERF_A4);
+  poly = fmaf(poly, t, MT_ERF_A3);
+  poly = fmaf(poly, t, MT_ERF_A2);
+  poly = fmaf(poly, t, MT_ERF_A1);
   poly *= t;
-  e = __builtin_amdgcn_exp2f(-z * z * 1.4426950408889634f);
+  e = __builtin_amdgcn_exp2f(-z * z * MT_LOG2E);
   const float r = fmaf(-poly, e, 1.0f);
   return copysignf(r, x);
 }
@@ -91,7 +95,7 @@ MT_DEVINL float gelu_erf(float x) { float e; return 0.5f * x * (1.0f + erf_rsqrt
 MT_DEVINL float gelu_erf_grad(float x) {
   float e;
   const float er = erf_rsqrt2(x, e);
-  return fmaf(x * 0.39894228040143267794f, e, 0.5f * (1.0f + er));   // Phi(x) + x phi(x)
+  return fmaf(x * MT_RSQRT_2PI, e, 0.5f * (1.0f + er));   // Phi(x) + x phi(x)
 }
 
 // ---- counter-based dropout masks (include/modaltune_hip.h: MtDropout)

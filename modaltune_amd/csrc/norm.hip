@@ -1,9 +1,12 @@
 // LayerNorm forward/backward (one wave per row, fp32 statistics) and the elementwise helpers.
 // HBM-bound: every row is read once with 8/16-byte vector loads and written once.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
+// ---------------------------------------------------------------- vector load and store -----------
 template <typename T> struct Vec4;
 template <> struct Vec4<float> {
   static MT_DEVINL f32x4 load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -19,6 +22,62 @@ template <> struct Vec4<h16> {
   }
 };
 
+// ---------------------------------------------------------------- row stages ----------------------
+// The one-wave-per-row kernels (256 threads = 4 waves = 4 rows in flight): lane l owns the columns c * 256 + l * 4 .. + 3 of chunk c,
+// NC = D / 256 chunks per row.  Every kernel below states its row arithmetic through these; the order of the additions is theirs.
+
+// A per-column vector (gamma, beta) into the lane's registers: r[c] = the lane's four columns of chunk c.  A lane always owns the same
+// columns, so the vector stays in registers across rows.
+template <int NC>
+MT_DEVINL void load_cols(const float* p, int lane, f32x4 (&r)[NC]) {
+#pragma unroll
+  for (int c = 0; c < NC; ++c) r[c] = Vec4<float>::load(p + c * 256 + lane * 4);
+}
+
+// Two-pass statistics of one row.  v: the lane's values; s: the lane's own sum of them, added c ascending, within a chunk
+// ((v0 + v1) + v2) + v3.  mean = wave_sum(s) / D; then the centred second moment, q += d * d over c then e, summed over the wave
+// the same way; rstd = rsqrt(q / D + eps).  Every lane gets both.
+template <int NC>
+MT_DEVINL void row_stats(const f32x4 (&v)[NC], float s, float eps, float& mean, float& rstd) {
+  constexpr int D = NC * 256;
+  mean = wave_sum(s) * (1.0f / D);
+  float q = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
+  rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+}
+
+// Normalise and affine of the lane's four columns of one chunk (the expression is contracted as it is written: keep its shape)
+MT_DEVINL f32x4 norm_affine(f32x4 v, float mean, float rstd, f32x4 w, f32x4 b) {
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * rstd * w[e] + b[e];
+  return o;
+}
+
+// Saved statistics of row m: stats[2 m] = mean, stats[2 m + 1] = rstd.  One lane of the row stores; every lane may load.
+MT_DEVINL void store_stats(float* stats, int m, float mean, float rstd) { stats[2 * (long)m] = mean; stats[2 * (long)m + 1] = rstd; }
+MT_DEVINL void load_stats(const float* stats, int m, float& mean, float& rstd) { mean = stats[2 * (long)m]; rstd = stats[2 * (long)m + 1]; }
+
+// Column sums over the workgroup's four waves through LDS, `red[wave][col]` (floats only or doubles only per array: one banking
+// class, common.h).  put_cols: a lane writes its accumulators acc[c][e] to `row` = its wave's row of LDS, at its own columns.  `row`
+// MUST point into a `__shared__` array: the cast names the LDS address space (through a generic pointer the compiler arranges the
+// callers' address arithmetic and loop guards another way), and a pointer to anything else is undefined behaviour behind it.
+// After a barrier, sum_waves gives column i as ((wave 0 + wave 1) + wave 2) + wave 3; thread t takes the columns i = t, t + 256, ...
+template <int NC, typename T, typename A>
+MT_DEVINL void put_cols(T* row, int lane, const A (&acc)[NC]) {
+  auto* lds = (__attribute__((address_space(3))) T*)row;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lds[c * 256 + lane * 4 + e] = acc[c][e];
+}
+template <typename T, int D>
+MT_DEVINL T sum_waves(const T (&red)[4][D], int i) { return red[0][i] + red[1][i] + red[2][i] + red[3][i]; }
+
+// ---------------------------------------------------------------- forward -------------------------
 struct LnFwdArgs {
   const void* x; long ldx; RowMap xmap;
   const float* w; const float* b; const float* add_rows; int add_period;
@@ -32,12 +91,9 @@ template <int D, typename InT, typename OutT, bool GELU>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwdArgs a) {
   constexpr int NC = D / 256;   // 4-element chunks per lane
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  f32x4 wr[NC], br[NC];         // a lane always owns the same columns: affine parameters stay in registers across rows
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    wr[c] = Vec4<float>::load(a.w + c * 256 + lane * 4);
-    br[c] = Vec4<float>::load(a.b + c * 256 + lane * 4);
-  }
+  f32x4 wr[NC], br[NC];
+  load_cols(a.w, lane, wr);
+  load_cols(a.b, lane, br);
   for (int m = blockIdx.x * 4 + wave; m < a.M; m += gridDim.x * 4) {
     const InT* x = reinterpret_cast<const InT*>(a.x) + a.xmap.map(m) * a.ldx;
     f32x4 v[NC];
@@ -51,25 +107,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(LnFwdArgs a) {
       }
       s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + a.eps);
+    float mean, rstd;
+    row_stats(v, s, a.eps, mean, rstd);
     OutT* y = reinterpret_cast<OutT*>(a.y) + a.ymap.map(m) * a.ldy;
     const float* add = a.add_rows ? a.add_rows + (long)(m % a.add_period) * D : nullptr;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int col = c * 256 + lane * 4;
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (v[c][e] - mean) * rstd * wr[c][e] + br[c][e];
+      f32x4 o = norm_affine(v[c], mean, rstd, wr[c], br[c]);
       if (add) { const f32x4 p = Vec4<float>::load(add + col); o += p; }
       Vec4<OutT>::store(y + col, o);
     }
-    if (a.stats && lane == 0) { a.stats[2 * (long)m] = mean; a.stats[2 * (long)m + 1] = rstd; }
+    if (a.stats && lane == 0) store_stats(a.stats, m, mean, rstd);
   }
 }
 
@@ -89,11 +138,8 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(AddLnArgs a) {
   constexpr int NC = D / 256;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   f32x4 wr[NC], br[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    wr[c] = Vec4<float>::load(a.w + c * 256 + lane * 4);
-    br[c] = Vec4<float>::load(a.b + c * 256 + lane * 4);
-  }
+  load_cols(a.w, lane, wr);
+  load_cols(a.b, lane, br);
   const bool dropping = a.drop.active();
   for (int m = blockIdx.x * 4 + wave; m < a.M; m += gridDim.x * 4) {
     const float* x = a.x + (long)m * D;
@@ -116,29 +162,19 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(AddLnArgs a) {
       Vec4<float>::store(hrow + col, v[c]);
       s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float q = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + a.eps);
+    float mean, rstd;
+    row_stats(v, s, a.eps, mean, rstd);
     h16* y = a.y + (long)m * D;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (v[c][e] - mean) * rstd * wr[c][e] + br[c][e];
-      Vec4<h16>::store(y + c * 256 + lane * 4, o);
-    }
-    if (lane == 0) { a.stats[2 * (long)m] = mean; a.stats[2 * (long)m + 1] = rstd; }
+    for (int c = 0; c < NC; ++c) Vec4<h16>::store(y + c * 256 + lane * 4, norm_affine(v[c], mean, rstd, wr[c], br[c]));
+    if (lane == 0) store_stats(a.stats, m, mean, rstd);
   }
 }
 
 // ---------------------------------------------------------------- pooled read-out -------------------
 // out[b, :] = LN_post( 1 / (r1 - r0) * sum_{r in [r0, r1)} LN_pre( x[b, r, :] ) )  (mt_layernorm_pool_fwd, include/modaltune_hip.h).
 // Stage 1, grid (G, B): workgroup g of pass b owns the rows r0 + [g * POOL_WG_ROWS, (g + 1) * POOL_WG_ROWS) of the range; wave w walks
-// the rows w, w + 4, ... of that share in ascending order -- LN_pre as in ln_fwd_kernel (one wave per row, fp32 mean, centred second
+// the rows w, w + 4, ... of that share in ascending order -- LN_pre by the row stages above (one wave per row, fp32 mean, centred second
 // moment), then the row is added to the lane's twelve DOUBLE column accumulators.  The four waves are added in ascending order through
 // LDS (doubles only: one LDS banking class, common.h).  G == 1: the workgroup finishes the pass itself; else it stores its D sums to
 // its own slot of the workspace and stage 2, one workgroup per pass, adds the G slots in ascending order.  Which rows a lane adds, and
@@ -162,8 +198,9 @@ MT_DEVINL float pool_block_sum(float v, double* red) {
   return s;
 }
 
-// colsum: the D column sums of pass b in LDS (complete, barrier passed).  Thread t owns the columns t, t + 256, t + 512: the mean is rounded to
-// fp32 once, LN_post (optional) takes the statistics of the fp32 vector the way ln_fwd_kernel does.
+// colsum: the D column sums of pass b in LDS (complete, barrier passed).  Thread t owns the columns t, t + 256, t + 512 -- not the
+// layout of the row stages, so this LayerNorm is written out here: the mean is rounded to fp32 once, LN_post (optional) takes the
+// statistics of the fp32 vector the way row_stats does, over the workgroup.
 MT_DEVINL void pool_finish(const LnPoolArgs& a, int b, const double* colsum, double* red) {
   constexpr int D = POOL_D, NJ = D / 256;
   const double inv_n = 1.0 / (double)a.n;
@@ -198,11 +235,8 @@ __global__ __launch_bounds__(256) void ln_pool_rows_kernel(LnPoolArgs a) {
   const int b = blockIdx.y, g = blockIdx.x;
   f32x4 wr[NC], br[NC];
   if (PRE) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      wr[c] = Vec4<float>::load(a.pre_w + c * 256 + lane * 4);
-      br[c] = Vec4<float>::load(a.pre_b + c * 256 + lane * 4);
-    }
+    load_cols(a.pre_w, lane, wr);
+    load_cols(a.pre_b, lane, br);
   }
   double acc[NC][4];
 #pragma unroll
@@ -216,33 +250,22 @@ __global__ __launch_bounds__(256) void ln_pool_rows_kernel(LnPoolArgs a) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) v[c] = Vec4<float>::load(x + c * 256 + lane * 4);
     if (PRE) {
-      float s = 0.f;
+      float s = 0.f, mean, rstd;
 #pragma unroll
       for (int c = 0; c < NC; ++c) s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
-      const float mean = wave_sum(s) * (1.0f / D);
-      float q = 0.f;
+      row_stats(v, s, a.pre_eps, mean, rstd);
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
-      const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + a.pre_eps);
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[c][e] = (v[c][e] - mean) * rstd * wr[c][e] + br[c][e];
+      for (int c = 0; c < NC; ++c) v[c] = norm_affine(v[c], mean, rstd, wr[c], br[c]);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc[c][e] += (double)v[c][e];
   }
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc_lds[wave][c * 256 + lane * 4 + e] = acc[c][e];
+  put_cols(acc_lds[wave], lane, acc);
   __syncthreads();
   for (int i = threadIdx.x; i < D; i += 256) {
-    const double t = ((acc_lds[0][i] + acc_lds[1][i]) + acc_lds[2][i]) + acc_lds[3][i];
+    const double t = sum_waves(acc_lds, i);
     if (a.G > 1) a.partials[((long)b * a.G + g) * D + i] = t;
     else acc_lds[0][i] = t;          // (column i is read and written by this thread alone)
   }
@@ -266,8 +289,7 @@ __global__ __launch_bounds__(256) void ln_pool_final_kernel(LnPoolArgs a) {
   pool_finish(a, b, colsum, red);
 }
 
-int ln_pool_groups(int n) { return cdiv(n, POOL_WG_ROWS); }
-
+// ---------------------------------------------------------------- backward ------------------------
 struct LnBwdArgs {
   const void* dy; long lddy; RowMap dymap;
   const void* x; long ldx; RowMap xmap;
@@ -292,12 +314,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
 #pragma unroll
   for (int c = 0; c < NP; ++c) { gw[c] = (f32x4){0.f, 0.f, 0.f, 0.f}; gb[c] = gw[c]; }
   f32x4 wr[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) wr[c] = Vec4<float>::load(a.w + c * 256 + lane * 4);
+  load_cols(a.w, lane, wr);
   for (int m = blockIdx.x * 4 + wave; m < a.M; m += gridDim.x * 4) {
     const DyT* dy = reinterpret_cast<const DyT*>(a.dy) + a.dymap.map(m) * a.lddy;
     const InT* x = reinterpret_cast<const InT*>(a.x) + a.xmap.map(m) * a.ldx;
-    const float mean = a.stats[2 * (long)m], rstd = a.stats[2 * (long)m + 1];
+    float mean, rstd;
+    load_stats(a.stats, m, mean, rstd);
     f32x4 xh[NC], g[NC], raw[GELU ? NC : 1];
     float s1 = 0.f, s2 = 0.f;
     // LIVE: dy of a row outside the live passes is masked to +0 bit by bit behind an UNCONDITIONAL load (a `dead ? 0 : load` select
@@ -357,6 +379,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   }
   if (PARAM) {
     __shared__ float red[2][4][D];
+    // Not put_cols(red[0]..) then put_cols(red[1]..): two calls would change the LDS store opcodes (ds_write_b128 instead of the
+    // ds_write2_b32 of this interleaved dw | db loop), so the loop is kept as it was (profiles/norm_stages.txt).
 #pragma unroll
     for (int c = 0; c < NP; ++c)
 #pragma unroll
@@ -366,47 +390,48 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
       }
     __syncthreads();
     for (int i = threadIdx.x; i < D; i += 256) {
+      const float sw = sum_waves(red[0], i), sb = sum_waves(red[1], i);
       if constexpr (DET) {
         float* slot = a.dw + (long)blockIdx.x * (2 * D);
-        slot[i] = red[0][0][i] + red[0][1][i] + red[0][2][i] + red[0][3][i];
-        slot[D + i] = red[1][0][i] + red[1][1][i] + red[1][2][i] + red[1][3][i];
+        slot[i] = sw;
+        slot[D + i] = sb;
       } else {
-        atomicAdd(&a.dw[i], red[0][0][i] + red[0][1][i] + red[0][2][i] + red[0][3][i]);
-        atomicAdd(&a.db[i], red[1][0][i] + red[1][1][i] + red[1][2][i] + red[1][3][i]);
+        atomicAdd(&a.dw[i], sw);
+        atomicAdd(&a.db[i], sb);
       }
     }
   }
 }
-
 
 // ---------------------------------------------------------------- FFN sub-LayerNorm ---------------
 // y = LN(gelu(a1)) over D = 3072 (feedforward_network.py:136-139) and its backward, fp16 in / fp16 out.  These two
 // launches stream 0.37 / 0.55 GB per layer and were co-bound by the VALU (erf twice per element, scalar fp32 ops, the
 // affine vectors re-read per row): here a lane owns 8 consecutive columns per chunk (16-byte loads/stores), keeps
 // gamma/beta in registers across rows, evaluates erf ONCE for both gelu and gelu', and does the arithmetic with packed
-// fp32 instructions (v_pk_fma/mul/add_f32).
+// fp32 instructions (v_pk_fma/mul/add_f32).  Another column layout than the row stages above, and statistics that cross a wave pair
+// or triple through LDS with barrier counts of their own: of the row stages only the statistics store is shared.
 MT_DEVINL f32x2 pk_fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 MT_DEVINL f32x2 splat2(float v) { return (f32x2){v, v}; }
 
-// gelu(x) and d gelu / dx for two values; A&S 7.1.26 erf as in common.h (|err| <= 1.5e-7)
+// gelu(x) and d gelu / dx for two values; A&S 7.1.26 erf as in common.h (|err| <= 1.5e-7), its constants from there
 template <bool WANT_GRAD>
 MT_DEVINL void gelu_pair(f32x2 x, f32x2& g, f32x2& dg) {
   const f32x2 ax = {fabsf(x[0]), fabsf(x[1])};
-  const f32x2 z = ax * splat2(0.70710678118654752440f);
-  const f32x2 den = pk_fma2(z, splat2(0.3275911f), splat2(1.0f));
+  const f32x2 z = ax * splat2(MT_RSQRT2);
+  const f32x2 den = pk_fma2(z, splat2(MT_ERF_P), splat2(1.0f));
   const f32x2 t = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  f32x2 poly = pk_fma2(t, splat2(1.061405429f), splat2(-1.453152027f));
-  poly = pk_fma2(poly, t, splat2(1.421413741f));
-  poly = pk_fma2(poly, t, splat2(-0.284496736f));
-  poly = pk_fma2(poly, t, splat2(0.254829592f));
+  f32x2 poly = pk_fma2(t, splat2(MT_ERF_A5), splat2(MT_ERF_A4));
+  poly = pk_fma2(poly, t, splat2(MT_ERF_A3));
+  poly = pk_fma2(poly, t, splat2(MT_ERF_A2));
+  poly = pk_fma2(poly, t, splat2(MT_ERF_A1));
   poly = poly * t;
-  const f32x2 ea = z * z * splat2(-1.4426950408889634f);
+  const f32x2 ea = z * z * splat2(-MT_LOG2E);
   const f32x2 e = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
   const f32x2 r = pk_fma2(-poly, e, splat2(1.0f));                 // erf(|x| / sqrt 2)
   const f32x2 er = {copysignf(r[0], x[0]), copysignf(r[1], x[1])};
   const f32x2 h = pk_fma2(er, splat2(0.5f), splat2(0.5f));          // Phi(x)
   g = x * h;
-  if (WANT_GRAD) dg = pk_fma2(x * splat2(0.39894228040143267794f), e, h);   // Phi(x) + x phi(x)
+  if (WANT_GRAD) dg = pk_fma2(x * splat2(MT_RSQRT_2PI), e, h);   // Phi(x) + x phi(x)
 }
 
 MT_DEVINL void cvt8(h16x8 v, f32x2 (&o)[4]) {
@@ -477,7 +502,7 @@ __global__ __launch_bounds__(256) void ln_gelu_fwd_kernel(LnFwdArgs a) {
         for (int i = 0; i < 4; ++i) o[i] = pk_fma2(v[c][i] * rs, wr[c][i], br[c][i]);
         stg8(y + col0 + c * 512, pack8(o));
       }
-      if (a.stats && lane == 0 && half == 0) { a.stats[2 * (long)m] = mean; a.stats[2 * (long)m + 1] = rstd; }
+      if (a.stats && lane == 0 && half == 0) store_stats(a.stats, m, mean, rstd);
     }
   }
 }
@@ -501,7 +526,8 @@ __global__ __launch_bounds__(64 * WPR) void ln_gelu_bwd_kernel(LnBwdArgs a) {
     h16x8 rx[NC], rd[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) { rx[c] = ldg8(x + col0 + c * 512); rd[c] = ldg8(dy + col0 + c * 512); }
-    const float mean = a.stats[2 * (long)m], rstd = a.stats[2 * (long)m + 1];
+    float mean, rstd;
+    load_stats(a.stats, m, mean, rstd);
     const f32x2 rs = splat2(rstd), nmr = splat2(-mean * rstd);
     f32x2 xh[NC][4], g[NC][4], dgl[NC][4];
     f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
@@ -544,60 +570,54 @@ __global__ __launch_bounds__(64 * WPR) void ln_gelu_bwd_kernel(LnBwdArgs a) {
   }
 }
 
-int ln_gelu_grid(int M) { return max(1, min(cdiv(M, 2), 8192)); }
-int ln_grid(int M) { return max(1, min(cdiv(M, 4), 4096)); }
-
-template <int D, typename InT, typename OutT>
-int ln_fwd_dispatch(const LnFwdArgs& a, int gelu, hipStream_t s) {
-  if (gelu) hipLaunchKernelGGL((ln_fwd_kernel<D, InT, OutT, true>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((ln_fwd_kernel<D, InT, OutT, false>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-template <int D>
-int ln_fwd_types(const LnFwdArgs& a, int in_dt, int out_dt, int gelu, hipStream_t s) {
-  if constexpr (D % 1024 == 0) {
-    if (gelu && in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16 && !a.add_rows && !(a.ldx & 7) && !(a.ldy & 7)) {
-      if (a.live) hipLaunchKernelGGL((ln_gelu_fwd_kernel<D, true>), dim3(ln_gelu_grid(a.M)), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((ln_gelu_fwd_kernel<D>), dim3(ln_gelu_grid(a.M)), dim3(256), 0, s, a);
-      MT_CHECK_LAUNCH();
-      return MT_OK;
-    }
-  }
-  if (a.live) return MT_ERR_UNSUPPORTED;      // (only the form above walks a live range)
-  if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, float, h16>(a, gelu, s);
-  if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F32) return ln_fwd_dispatch<D, float, float>(a, gelu, s);
-  if (in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, h16, h16>(a, gelu, s);
-  return MT_ERR_UNSUPPORTED;
-}
-
-int ln_param_grid(int M) { return min(ln_grid(M), 512); }      // workgroups (= partial slots) of the PARAM form
-
-template <int D, typename DyT, typename InT, typename DxT, bool GELU>
-int ln_bwd_launch(const LnBwdArgs& a, hipStream_t s, bool det = false) {
-  if (a.dw) {
-    if constexpr ((!GELU && sizeof(DyT) == 4) || (D <= 768 && !GELU)) {
-      if (det) {
-        hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, true, true>), dim3(ln_param_grid(a.M)), dim3(256), 0, s, a);
-        MT_CHECK_LAUNCH();
-        return MT_OK;
+// ---------------------------------------------------------------- injector residual backward ------
+// y = (1+g) x + g * proj  (A.1), with proj = out(a) recomputed in fp16:
+//   dx (+)= (1+g) dy ; dproj = g * dy (fp16, feeds the dX/dW GEMMs) ; dgamma += sum_m dy * (x + proj)
+struct InjBwdArgs {
+  const float* dy; long lddy; RowMap dymap;
+  const float* x; long ldx; RowMap xmap;
+  const h16* proj; const float* gamma;
+  float* dx; long lddx; RowMap dxmap; int dx_accumulate;
+  h16* dproj; float* dgamma; int M;
+};
+// DET (deterministic mode): a.dgamma is the partial workspace [gridDim.x][D], slot = blockIdx.x, plain stores
+template <int D, bool DET = false>
+__global__ __launch_bounds__(256) void inject_resid_bwd_kernel(InjBwdArgs a) {
+  constexpr int NC = D / 256;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  f32x4 gg[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) gg[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int m = blockIdx.x * 4 + wave; m < a.M; m += gridDim.x * 4) {
+    const float* dy = a.dy + a.dymap.map(m) * a.lddy;
+    const float* x = a.x + a.xmap.map(m) * a.ldx;
+    const h16* pr = a.proj + (long)m * D;
+    float* dx = a.dx + a.dxmap.map(m) * a.lddx;
+    h16* dp = a.dproj + (long)m * D;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int col = c * 256 + lane * 4;
+      const f32x4 d = Vec4<float>::load(dy + col), xv = Vec4<float>::load(x + col), p = Vec4<h16>::load(pr + col);
+      const f32x4 gm = Vec4<float>::load(a.gamma + col);
+      f32x4 o, q;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = (1.0f + gm[e]) * d[e];
+        q[e] = gm[e] * d[e];
+        gg[c][e] += d[e] * (xv[e] + p[e]);
       }
+      if (a.dx_accumulate) o += Vec4<float>::load(dx + col);
+      Vec4<float>::store(dx + col, o);
+      Vec4<h16>::store(dp + col, q);
     }
-    if (det) return MT_ERR_UNSUPPORTED;
-    if constexpr (!GELU && sizeof(DyT) == 4) {            // trainable norms: token side (fp32) ...
-      hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, true>), dim3(min(ln_grid(a.M), 512)), dim3(256), 0, s, a);
-    } else if constexpr (D <= 768 && !GELU) {           // ... and the adapters' 768-wide norms over the patch rows
-      hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, true>), dim3(min(ln_grid(a.M), 512)), dim3(256), 0, s, a);
-    } else {
-      return MT_ERR_UNSUPPORTED;
-    }
-  } else if (a.live) {
-    hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, false, false, true>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL((ln_bwd_kernel<D, DyT, InT, DxT, GELU, false>), dim3(ln_grid(a.M)), dim3(256), 0, s, a);
   }
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  __shared__ float red[4][D];
+  put_cols(red[wave], lane, gg);
+  __syncthreads();
+  for (int i = threadIdx.x; i < D; i += 256) {
+    if constexpr (DET) a.dgamma[(long)blockIdx.x * D + i] = sum_waves(red, i);
+    else atomicAdd(&a.dgamma[i], sum_waves(red, i));
+  }
 }
 
 // ---------------------------------------------------------------- elementwise ---------------------
@@ -705,58 +725,7 @@ __global__ void copy_rows_kernel(const float* src, long lds, RowMap smap, float*
   }
 }
 
-// Injector residual path backward.  y = (1+g) x + g * proj  (A.1), with proj = out(a) recomputed in fp16:
-//   dx (+)= (1+g) dy ; dproj = g * dy (fp16, feeds the dX/dW GEMMs) ; dgamma += sum_m dy * (x + proj)
-struct InjBwdArgs {
-  const float* dy; long lddy; RowMap dymap;
-  const float* x; long ldx; RowMap xmap;
-  const h16* proj; const float* gamma;
-  float* dx; long lddx; RowMap dxmap; int dx_accumulate;
-  h16* dproj; float* dgamma; int M;
-};
-// DET (deterministic mode): a.dgamma is the partial workspace [gridDim.x][D], slot = blockIdx.x, plain stores
-template <int D, bool DET = false>
-__global__ __launch_bounds__(256) void inject_resid_bwd_kernel(InjBwdArgs a) {
-  constexpr int NC = D / 256;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  f32x4 gg[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) gg[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int m = blockIdx.x * 4 + wave; m < a.M; m += gridDim.x * 4) {
-    const float* dy = a.dy + a.dymap.map(m) * a.lddy;
-    const float* x = a.x + a.xmap.map(m) * a.ldx;
-    const h16* pr = a.proj + (long)m * D;
-    float* dx = a.dx + a.dxmap.map(m) * a.lddx;
-    h16* dp = a.dproj + (long)m * D;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int col = c * 256 + lane * 4;
-      const f32x4 d = Vec4<float>::load(dy + col), xv = Vec4<float>::load(x + col), p = Vec4<h16>::load(pr + col);
-      const f32x4 gm = Vec4<float>::load(a.gamma + col);
-      f32x4 o, q;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = (1.0f + gm[e]) * d[e];
-        q[e] = gm[e] * d[e];
-        gg[c][e] += d[e] * (xv[e] + p[e]);
-      }
-      if (a.dx_accumulate) o += Vec4<float>::load(dx + col);
-      Vec4<float>::store(dx + col, o);
-      Vec4<h16>::store(dp + col, q);
-    }
-  }
-  __shared__ float red[4][D];
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) red[wave][c * 256 + lane * 4 + e] = gg[c][e];
-  __syncthreads();
-  for (int i = threadIdx.x; i < D; i += 256) {
-    if constexpr (DET) a.dgamma[(long)blockIdx.x * D + i] = red[0][i] + red[1][i] + red[2][i] + red[3][i];
-    else atomicAdd(&a.dgamma[i], red[0][i] + red[1][i] + red[2][i] + red[3][i]);
-  }
-}
-
+// ---------------------------------------------------------------- weight packers ------------------
 // fp32 [R, C] -> fp16 [R, C] (transpose = 0) or fp16 [C, R] (transpose = 1), 32x32 tiles through LDS
 __global__ __launch_bounds__(256) void pack_f16_kernel(const float* __restrict__ src, int R, int C, h16* __restrict__ dst, int transpose) {
   __shared__ float tile[32][33];
@@ -813,28 +782,121 @@ __global__ __launch_bounds__(256) void pack_group_kernel(const long long* __rest
   }
 }
 
+// ---------------------------------------------------------------- grids and dispatch --------------
+// Every launcher of this file ends here: launch, check, status.
+template <typename K, typename... Args>
+int launch(K kernel, dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+  MT_CHECK_LAUNCH();
+  return MT_OK;
+}
+
+// Workgroups per launch.  Whatever sizes a partial workspace asks the function that the launch asks.
 int ew_grid(long n) { return (int)max(1L, min((n + 1023) / 1024, 4096L)); }
+int ln_grid(int M) { return max(1, min(cdiv(M, 4), 4096)); }       // one wave per row, four rows per workgroup
+int ln_param_grid(int M) { return min(ln_grid(M), 512); }          // PARAM / DET forms of ln_bwd_kernel: workgroups = partial slots [2][D]
+int inj_grid(int M) { return min(cdiv(M, 4), 512); }               // inject_resid_bwd_kernel: workgroups = partial slots [D]
+int ln_gelu_grid(int M) { return max(1, min(cdiv(M, 2), 8192)); }  // packed forward: two rows per workgroup
+int ln_gelu_bwd_grid(int M) { return min(M, 16384); }              // packed backward: one row per workgroup
+int ln_pool_groups(int n) { return cdiv(n, POOL_WG_ROWS); }
+
+// The widths the LayerNorm kernels are built for: f(std::integral_constant<int, D>) at a supported D, MT_ERR_UNSUPPORTED otherwise.
+template <typename F>
+int with_ln_width(int D, F&& f) {
+  switch (D) {
+    case 256: return f(std::integral_constant<int, 256>{});
+    case 768: return f(std::integral_constant<int, 768>{});
+    case 2304: return f(std::integral_constant<int, 2304>{});
+    case 3072: return f(std::integral_constant<int, 3072>{});
+    default: return MT_ERR_UNSUPPORTED;
+  }
+}
+bool ln_width_ok(int D) { return with_ln_width(D, [](auto) { return (int)MT_OK; }) == MT_OK; }
+
+// live / live_rows of the options (MT_OPT_LIVE); a table without its rows per pass is malformed
+struct LiveOpt {
+  const int* live; int rows;
+  bool malformed() const { return live && rows < 1; }
+};
+LiveOpt live_opt(const MtLaunchOpts* o) { return {mt_opt_live(o), o ? o->live_rows : 0}; }
+
+// The packed pair takes D % 1024 == 0 (the `if constexpr` at its callers: no other width instantiates it), fp16 throughout, 16-byte
+// rows -- and what is listed here; the packed form alone walks a live range.
+bool ln_gelu_fwd_ok(const LnFwdArgs& a, int in_dt, int out_dt, int gelu) {
+  return gelu && in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16 && !a.add_rows && !(a.ldx & 7) && !(a.ldy & 7);
+}
+bool ln_gelu_bwd_ok(const LnBwdArgs& a, bool dyh, bool inh, bool dxh) {      // (asked under gelu)
+  return dyh && inh && dxh && !a.dw && !(a.lddy & 7) && !(a.ldx & 7) && !(a.lddx & 7);
+}
+
+template <int D, typename InT, typename OutT>
+int ln_fwd_dispatch(const LnFwdArgs& a, int gelu, hipStream_t s) {
+  return launch(gelu ? ln_fwd_kernel<D, InT, OutT, true> : ln_fwd_kernel<D, InT, OutT, false>, dim3(ln_grid(a.M)), dim3(256), s, a);
+}
+template <int D>
+int ln_fwd_types(const LnFwdArgs& a, int in_dt, int out_dt, int gelu, hipStream_t s) {
+  if constexpr (D % 1024 == 0) {
+    if (ln_gelu_fwd_ok(a, in_dt, out_dt, gelu))
+      return launch(a.live ? ln_gelu_fwd_kernel<D, true> : ln_gelu_fwd_kernel<D>, dim3(ln_gelu_grid(a.M)), dim3(256), s, a);
+  }
+  if (a.live) return MT_ERR_UNSUPPORTED;      // (only the form above walks a live range)
+  if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, float, h16>(a, gelu, s);
+  if (in_dt == MT_OUT_F32 && out_dt == MT_OUT_F32) return ln_fwd_dispatch<D, float, float>(a, gelu, s);
+  if (in_dt == MT_OUT_F16 && out_dt == MT_OUT_F16) return ln_fwd_dispatch<D, h16, h16>(a, gelu, s);
+  return MT_ERR_UNSUPPORTED;
+}
+
+template <int D, typename DyT, typename InT, typename DxT, bool GELU>
+int ln_bwd_launch(const LnBwdArgs& a, hipStream_t s, bool det) {
+  // dw / db exist for the trainable norms: the token side (fp32 dy) and the adapters' 768-wide norms over the patch rows
+  constexpr bool HAS_PARAM = (!GELU && sizeof(DyT) == 4) || (D <= 768 && !GELU);
+  const dim3 block(256);
+  if (a.dw) {
+    if constexpr (HAS_PARAM) {
+      return launch(det ? ln_bwd_kernel<D, DyT, InT, DxT, GELU, true, true> : ln_bwd_kernel<D, DyT, InT, DxT, GELU, true>,
+                    dim3(ln_param_grid(a.M)), block, s, a);
+    } else {
+      return MT_ERR_UNSUPPORTED;
+    }
+  }
+  return launch(a.live ? ln_bwd_kernel<D, DyT, InT, DxT, GELU, false, false, true> : ln_bwd_kernel<D, DyT, InT, DxT, GELU, false>,
+                dim3(ln_grid(a.M)), block, s, a);
+}
+
+template <int D>
+int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int gelu, hipStream_t s, bool det) {
+  const bool dyh = dy_dt == MT_OUT_F16, inh = in_dt == MT_OUT_F16, dxh = dx_dt == MT_OUT_F16;
+  if (gelu) {
+    if constexpr (D % 1024 == 0) {
+      if (ln_gelu_bwd_ok(a, dyh, inh, dxh)) {
+        constexpr int WPR = (D % 1536 == 0) ? 3 : 2;        // 3072 -> three waves per row (16 columns per lane)
+        return launch(a.live ? ln_gelu_bwd_kernel<D, WPR, true> : ln_gelu_bwd_kernel<D, WPR>, dim3(ln_gelu_bwd_grid(a.M)), dim3(64 * WPR),
+                      s, a);
+      }
+    }
+    if (a.live) return MT_ERR_UNSUPPORTED;      // (a GELU input means a LayerNorm INSIDE a branch: only the form above walks a live range)
+    if (dyh && inh && dxh) return ln_bwd_launch<D, h16, h16, h16, true>(a, s, det);
+    return MT_ERR_UNSUPPORTED;
+  }
+  if (dyh && !inh && !dxh) return ln_bwd_launch<D, h16, float, float, false>(a, s, det);
+  if (dyh && !inh && dxh) return ln_bwd_launch<D, h16, float, h16, false>(a, s, det);
+  if (!dyh && !inh && !dxh) return ln_bwd_launch<D, float, float, float, false>(a, s, det);
+  return MT_ERR_UNSUPPORTED;
+}
 
 }  // namespace
 
+// ---------------------------------------------------------------- C entry points ------------------
 extern "C" int mt_layernorm_fwd(const void* x, long ldx, const MtRowMap* xmap, int in_dtype, int gelu_in,
                                 const float* w, const float* b, const float* add_rows, int add_period, void* y,
                                 long ldy, const MtRowMap* ymap, int out_dtype, float* stats, int M, int D,
                                 const MtLaunchOpts* opt, mt_stream_t stream) {
   if (int rc = mt_opts_check(opt, MT_OPT_EPS | MT_OPT_LIVE)) return rc;
-  const int* live = mt_opt_live(opt);
-  const int live_rows = opt ? opt->live_rows : 0;
-  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || (live && live_rows < 1)) return MT_ERR_BAD_ARG;
-  LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M,
-              mt_opt_eps(opt), live, live_rows};
-  hipStream_t s = (hipStream_t)stream;
-  switch (D) {
-    case 256: return ln_fwd_types<256>(a, in_dtype, out_dtype, gelu_in, s);
-    case 768: return ln_fwd_types<768>(a, in_dtype, out_dtype, gelu_in, s);
-    case 2304: return ln_fwd_types<2304>(a, in_dtype, out_dtype, gelu_in, s);
-    case 3072: return ln_fwd_types<3072>(a, in_dtype, out_dtype, gelu_in, s);
-    default: return MT_ERR_UNSUPPORTED;
-  }
+  const LiveOpt lv = live_opt(opt);
+  if (!x || !y || !w || !b || M <= 0 || (ldx & 3) || (ldy & 3) || lv.malformed()) return MT_ERR_BAD_ARG;
+  const LnFwdArgs a{x, ldx, make_rowmap(xmap), w, b, add_rows, add_period > 0 ? add_period : 1, y, ldy, make_rowmap(ymap), stats, M,
+                    mt_opt_eps(opt), lv.live, lv.rows};
+  return with_ln_width(D, [&](auto d) { return ln_fwd_types<d()>(a, in_dtype, out_dtype, gelu_in, (hipStream_t)stream); });
 }
 
 extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const MtDropout* drop, const float* w,
@@ -843,10 +905,8 @@ extern "C" int mt_add_layernorm_fwd(const float* x, const mt_half* branch, const
   if (int rc = mt_opts_check(opt, MT_OPT_EPS)) return rc;
   if (!x || !branch || !w || !b || !h || !y || !stats || M <= 0 || h == x) return MT_ERR_BAD_ARG;
   if (D != 768) return MT_ERR_UNSUPPORTED;
-  AddLnArgs a{x, (const h16*)branch, make_drop(drop), w, b, h, (h16*)y, stats, M, mt_opt_eps(opt)};
-  hipLaunchKernelGGL((add_ln_fwd_kernel<768>), dim3(ln_grid(M)), dim3(256), 0, (hipStream_t)stream, a);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
+  const AddLnArgs a{x, (const h16*)branch, make_drop(drop), w, b, h, (h16*)y, stats, M, mt_opt_eps(opt)};
+  return launch(add_ln_fwd_kernel<768>, dim3(ln_grid(M)), dim3(256), (hipStream_t)stream, a);
 }
 
 extern "C" long mt_layernorm_pool_partials_elems(int B, int rows, int D) {
@@ -864,45 +924,17 @@ extern "C" int mt_layernorm_pool_fwd(const float* x, long ldx, int B, int rows_p
     return MT_ERR_BAD_ARG;
   if (D != POOL_D) return MT_ERR_UNSUPPORTED;
   const int n = r1 - r0, G = ln_pool_groups(n);
-  if (G > 1 && (!partials || ((uintptr_t)partials & 7) || partials_elems < (long)B * G * D)) return MT_ERR_BAD_ARG;
-  LnPoolArgs a{x, ldx, rows_per_pass, r0, n, pre_w, pre_b, pre_eps != 0.f ? pre_eps : 1e-5f, post_w, post_b, post_eps != 0.f ? post_eps : 1e-5f,
-               out, partials, G};
+  if (G > 1 && (!partials || ((uintptr_t)partials & 7) || partials_elems < mt_layernorm_pool_partials_elems(B, n, D))) return MT_ERR_BAD_ARG;
+  const LnPoolArgs a{x, ldx, rows_per_pass, r0, n, pre_w, pre_b, pre_eps != 0.f ? pre_eps : 1e-5f, post_w, post_b,
+                     post_eps != 0.f ? post_eps : 1e-5f, out, partials, G};
   hipStream_t s = (hipStream_t)stream;
-  if (pre_w) hipLaunchKernelGGL(ln_pool_rows_kernel<true>, dim3(G, B), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(ln_pool_rows_kernel<false>, dim3(G, B), dim3(256), 0, s, a);
-  MT_CHECK_LAUNCH();
-  if (G > 1) {
-    hipLaunchKernelGGL(ln_pool_final_kernel, dim3(B), dim3(256), 0, s, a);
-    MT_CHECK_LAUNCH();
-  }
-  return MT_OK;
-}
-
-template <int D>
-static int ln_bwd_types(const LnBwdArgs& a, int dy_dt, int in_dt, int dx_dt, int gelu, hipStream_t s, bool det = false) {
-  const bool dyh = dy_dt == MT_OUT_F16, inh = in_dt == MT_OUT_F16, dxh = dx_dt == MT_OUT_F16;
-  if (gelu) {
-    if constexpr (D % 1024 == 0) {
-      if (dyh && inh && dxh && !a.dw && !(a.lddy & 7) && !(a.ldx & 7) && !(a.lddx & 7)) {
-        constexpr int WPR = (D % 1536 == 0) ? 3 : 2;        // 3072 -> three waves per row (16 columns per lane)
-        if (a.live) hipLaunchKernelGGL((ln_gelu_bwd_kernel<D, WPR, true>), dim3(min(a.M, 16384)), dim3(64 * WPR), 0, s, a);
-        else hipLaunchKernelGGL((ln_gelu_bwd_kernel<D, WPR>), dim3(min(a.M, 16384)), dim3(64 * WPR), 0, s, a);
-        MT_CHECK_LAUNCH();
-        return MT_OK;
-      }
-    }
-    if (a.live) return MT_ERR_UNSUPPORTED;      // (a GELU input means a LayerNorm INSIDE a branch: only the form above walks a live range)
-    if (dyh && inh && dxh) return ln_bwd_launch<D, h16, h16, h16, true>(a, s, det);
-    return MT_ERR_UNSUPPORTED;
-  }
-  if (dyh && !inh && !dxh) return ln_bwd_launch<D, h16, float, float, false>(a, s, det);
-  if (dyh && !inh && dxh) return ln_bwd_launch<D, h16, float, h16, false>(a, s, det);
-  if (!dyh && !inh && !dxh) return ln_bwd_launch<D, float, float, float, false>(a, s, det);
-  return MT_ERR_UNSUPPORTED;
+  const int rc = launch(pre_w ? ln_pool_rows_kernel<true> : ln_pool_rows_kernel<false>, dim3(G, B), dim3(256), s, a);
+  if (rc != MT_OK || G == 1) return rc;
+  return launch(ln_pool_final_kernel, dim3(B), dim3(256), s, a);
 }
 
 extern "C" long mt_layernorm_bwd_det_elems(int M, int D) {
-  if (M <= 0 || (D != 256 && D != 768 && D != 2304 && D != 3072)) return MT_ERR_BAD_ARG;
+  if (M <= 0 || !ln_width_ok(D)) return MT_ERR_BAD_ARG;
   return (long)ln_param_grid(M) * 2 * D;
 }
 
@@ -913,33 +945,25 @@ extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap
                                 int accumulate, float* dw, float* db, mt_half* dx_f16, const MtDropout* dx_f16_drop, int M,
                                 int D, const MtLaunchOpts* opt, mt_stream_t stream) {
   if (int rc = mt_opts_check(opt, MT_OPT_LIVE | MT_OPT_PARTIALS)) return rc;
-  const int* live = mt_opt_live(opt);
-  const int live_rows = opt ? opt->live_rows : 0;
+  const LiveOpt lv = live_opt(opt);
   float* partials = mt_opt_partials(opt);
-  if (live && partials) return MT_ERR_UNSUPPORTED;
-  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (partials && !dw) || (live && live_rows < 1) ||
+  if (lv.live && partials) return MT_ERR_UNSUPPORTED;
+  if (!dy || !x || !w || !stats || !dx || M <= 0 || (!dw) != (!db) || (partials && !dw) || lv.malformed() ||
       (lddy & 3) || (ldx & 3) || (lddx & 3))      // (8- and 16-byte vector accesses per row, as in mt_layernorm_fwd)
     return MT_ERR_BAD_ARG;
   if (dx_f16 && gelu_in) return MT_ERR_UNSUPPORTED;
-  if (live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
+  if (lv.live && dw) return MT_ERR_UNSUPPORTED;      // (dw / db of a trainable norm sum over every row: its forms take no table)
   if (partials) {
     const long need = mt_layernorm_bwd_det_elems(M, D);
     if (need < 0) return MT_ERR_UNSUPPORTED;
     if (opt->partials_elems < need) return MT_ERR_BAD_ARG;
   }
-  LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate,
-              partials ? partials : dw, partials ? partials + D : db, (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M, live,
-              live_rows};
+  const LnBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), w, stats, dx, lddx, make_rowmap(dxmap), accumulate,
+                    partials ? partials : dw, partials ? partials + D : db, (h16*)dx_f16, make_drop(dx_f16 ? dx_f16_drop : nullptr), M,
+                    lv.live, lv.rows};
   hipStream_t s = (hipStream_t)stream;
   const bool det = partials != nullptr;
-  int rc;
-  switch (D) {
-    case 256: rc = ln_bwd_types<256>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
-    case 768: rc = ln_bwd_types<768>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
-    case 2304: rc = ln_bwd_types<2304>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
-    case 3072: rc = ln_bwd_types<3072>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); break;
-    default: return MT_ERR_UNSUPPORTED;
-  }
+  int rc = with_ln_width(D, [&](auto d) { return ln_bwd_types<d()>(a, dy_dtype, in_dtype, dx_dtype, gelu_in, s, det); });
   if (rc != MT_OK || !det) return rc;
   const int slots = ln_param_grid(M);
   rc = mt_det_reduce_launch(partials, slots, 1, D, 2L * D, dw, D, s);
@@ -947,109 +971,9 @@ extern "C" int mt_layernorm_bwd(const void* dy, long lddy, const MtRowMap* dymap
   return mt_det_reduce_launch(partials + D, slots, 1, D, 2L * D, db, D, s);
 }
 
-extern "C" int mt_cast_f32_to_f16(const float* x, mt_half* y, long n, const MtDropout* drop, int D, mt_stream_t stream) {
-  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
-  const DropArgs d = make_drop(drop);
-  if (d.active()) {
-    if ((n & 3) || D <= 0 || (D & 3)) return MT_ERR_BAD_ARG;
-    hipLaunchKernelGGL(cast_drop_f32_f16_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, x, (h16*)y, n, d, D);
-  } else {
-    hipLaunchKernelGGL(cast_f32_f16_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, x, (h16*)y, n);
-  }
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_rng_advance(unsigned* rng, mt_stream_t stream) {
-  if (!rng) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, rng);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_droppath_live(const unsigned* path_sites, const float* path_ps, int n, int B, const unsigned* rng, int* table,
-                                mt_stream_t stream) {
-  if (!path_sites || !path_ps || !rng || !table || n < 1 || n > MT_LIVE_SITES_MAX || B < 1) return MT_ERR_BAD_ARG;
-  LiveSites ls;
-  ls.n = n;
-  for (int i = 0; i < MT_LIVE_SITES_MAX; ++i) { ls.site[i] = i < n ? path_sites[i] : 0u; ls.p[i] = i < n ? path_ps[i] : 0.f; }
-  hipLaunchKernelGGL(droppath_live_kernel, dim3(1), dim3(MT_LIVE_SITES_MAX), 0, (hipStream_t)stream, ls, B, rng, table);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_dropout_f32(const float* x, long ldx, const MtRowMap* xmap, float* y, int M, int D, const MtDropout* drop,
-                              mt_stream_t stream) {
-  if (!x || !y || M <= 0 || D <= 0 || (D & 3) || (ldx & 3)) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(dropout_f32_kernel, dim3(ew_grid((long)M * D / 4 + 1)), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                     make_rowmap(xmap), y, M, D, make_drop(drop));
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_droppath_rows_f32(float* x, int M, int D, const MtDropout* drop, mt_stream_t stream) {
-  if (!x || M <= 0 || D <= 0 || (D & 3)) return MT_ERR_BAD_ARG;
-  const DropArgs d = make_drop(drop);
-  if (!d.active() || d.path_p <= 0.f) return MT_OK;
-  hipLaunchKernelGGL(droppath_rows_kernel, dim3(ew_grid((long)M * D / 4 + 1)), dim3(256), 0, (hipStream_t)stream, x, M, D, d);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_cast_f16_to_f32(const mt_half* x, float* y, long n, mt_stream_t stream) {
-  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(cast_f16_f32_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, (const h16*)x, y, n);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_pack_weight_f16(const float* src, int R, int C, mt_half* dst, int transpose, mt_stream_t stream) {
-  if (!src || !dst || R <= 0 || C <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(pack_f16_kernel, dim3(cdiv(C, 32), cdiv(R, 32)), dim3(256), 0, (hipStream_t)stream, src, R, C, (h16*)dst, transpose);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_pack_weights_f16(const long long* items, int n_items, mt_stream_t stream) {
-  if (!items || n_items <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(pack_group_kernel, dim3(n_items, 48), dim3(256), 0, (hipStream_t)stream, items);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_act_fwd(const float* x, float* y, long n, int act, mt_stream_t stream) {
-  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(act_fwd_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, y, n, act);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_act_bwd(const float* x, const float* dy, float* dx, long n, int act, mt_stream_t stream) {
-  if (!x || !dy || !dx || n <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, n, act);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_axpy(const float* a, const float* b, float alpha, float* y, long n, mt_stream_t stream) {
-  if (!a || !b || !y || n <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(axpy_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, alpha, y, n);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_axpy_bcast(const float* a, const float* b, float alpha, float* y, long n, long period, mt_stream_t stream) {
-  if (!a || !b || !y || n <= 0 || period <= 0) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(axpy_bcast_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, a, b, alpha, y, n, period);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_fold_rows(const float* x, int reps, long period, float* out, mt_stream_t stream) {
-  if (!x || !out || reps < 1 || period <= 0 || (period & 3) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(fold_rows_kernel, dim3(ew_grid(period / 4)), dim3(256), 0, (hipStream_t)stream, x, reps, period, out);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
-extern "C" int mt_copy_rows_f32(const float* src, long lds, const MtRowMap* smap, float* dst, long ldd,
-                                const MtRowMap* dmap, int M, int D, int accumulate, mt_stream_t stream) {
-  if (!src || !dst || M <= 0 || D <= 0 || (D & 3) || (lds & 3) || (ldd & 3)) return MT_ERR_BAD_ARG;
-  hipLaunchKernelGGL(copy_rows_kernel, dim3(ew_grid((long)M * D / 4)), dim3(256), 0, (hipStream_t)stream, src, lds,
-                     make_rowmap(smap), dst, ldd, make_rowmap(dmap), M, D, accumulate);
-  MT_CHECK_LAUNCH();
-  return MT_OK;
-}
 extern "C" long mt_inject_resid_bwd_det_elems(int M, int D) {
   if (M <= 0 || D != 768) return MT_ERR_BAD_ARG;
-  return (long)min(cdiv(M, 4), 512) * D;
+  return (long)inj_grid(M) * D;
 }
 
 // opt->partials: the deterministic form, partials = [slots][D], slots = workgroups
@@ -1062,11 +986,82 @@ extern "C" int mt_inject_resid_bwd(const float* dy, long lddy, const MtRowMap* d
   if (!dy || !x || !proj || !gamma || !dx || !dproj || !dgamma || M <= 0 || D != 768 || (lddy & 3) || (ldx & 3) || (lddx & 3) ||
       (partials && opt->partials_elems < mt_inject_resid_bwd_det_elems(M, D)))
     return MT_ERR_BAD_ARG;
-  InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
-               make_rowmap(dxmap), dx_accumulate, (h16*)dproj, partials ? partials : dgamma, M};
-  const int slots = min(cdiv(M, 4), 512);
-  if (!partials) hipLaunchKernelGGL(inject_resid_bwd_kernel<768>, dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((inject_resid_bwd_kernel<768, true>), dim3(slots), dim3(256), 0, (hipStream_t)stream, a);
-  MT_CHECK_LAUNCH();
-  return partials ? mt_det_reduce_launch(partials, slots, 1, D, D, dgamma, D, (hipStream_t)stream) : MT_OK;
+  const InjBwdArgs a{dy, lddy, make_rowmap(dymap), x, ldx, make_rowmap(xmap), (const h16*)proj, gamma, dx, lddx,
+                     make_rowmap(dxmap), dx_accumulate, (h16*)dproj, partials ? partials : dgamma, M};
+  hipStream_t s = (hipStream_t)stream;
+  const int slots = inj_grid(M);
+  const int rc = launch(partials ? inject_resid_bwd_kernel<768, true> : inject_resid_bwd_kernel<768>, dim3(slots), dim3(256), s, a);
+  if (rc != MT_OK || !partials) return rc;
+  return mt_det_reduce_launch(partials, slots, 1, D, D, dgamma, D, s);
+}
+
+extern "C" int mt_cast_f32_to_f16(const float* x, mt_half* y, long n, const MtDropout* drop, int D, mt_stream_t stream) {
+  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
+  const DropArgs d = make_drop(drop);
+  const dim3 grid(ew_grid(n / 4 + 1)), block(256);
+  if (!d.active()) return launch(cast_f32_f16_kernel, grid, block, (hipStream_t)stream, x, (h16*)y, n);
+  if ((n & 3) || D <= 0 || (D & 3)) return MT_ERR_BAD_ARG;
+  return launch(cast_drop_f32_f16_kernel, grid, block, (hipStream_t)stream, x, (h16*)y, n, d, D);
+}
+extern "C" int mt_cast_f16_to_f32(const mt_half* x, float* y, long n, mt_stream_t stream) {
+  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
+  return launch(cast_f16_f32_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), (hipStream_t)stream, (const h16*)x, y, n);
+}
+extern "C" int mt_rng_advance(unsigned* rng, mt_stream_t stream) {
+  if (!rng) return MT_ERR_BAD_ARG;
+  return launch(rng_advance_kernel, dim3(1), dim3(64), (hipStream_t)stream, rng);
+}
+extern "C" int mt_droppath_live(const unsigned* path_sites, const float* path_ps, int n, int B, const unsigned* rng, int* table,
+                                mt_stream_t stream) {
+  if (!path_sites || !path_ps || !rng || !table || n < 1 || n > MT_LIVE_SITES_MAX || B < 1) return MT_ERR_BAD_ARG;
+  LiveSites ls;
+  ls.n = n;
+  for (int i = 0; i < MT_LIVE_SITES_MAX; ++i) { ls.site[i] = i < n ? path_sites[i] : 0u; ls.p[i] = i < n ? path_ps[i] : 0.f; }
+  return launch(droppath_live_kernel, dim3(1), dim3(MT_LIVE_SITES_MAX), (hipStream_t)stream, ls, B, rng, table);
+}
+extern "C" int mt_dropout_f32(const float* x, long ldx, const MtRowMap* xmap, float* y, int M, int D, const MtDropout* drop,
+                              mt_stream_t stream) {
+  if (!x || !y || M <= 0 || D <= 0 || (D & 3) || (ldx & 3)) return MT_ERR_BAD_ARG;
+  return launch(dropout_f32_kernel, dim3(ew_grid((long)M * D / 4 + 1)), dim3(256), (hipStream_t)stream, x, ldx, make_rowmap(xmap), y, M, D,
+                make_drop(drop));
+}
+extern "C" int mt_droppath_rows_f32(float* x, int M, int D, const MtDropout* drop, mt_stream_t stream) {
+  if (!x || M <= 0 || D <= 0 || (D & 3)) return MT_ERR_BAD_ARG;
+  const DropArgs d = make_drop(drop);
+  if (!d.active() || d.path_p <= 0.f) return MT_OK;
+  return launch(droppath_rows_kernel, dim3(ew_grid((long)M * D / 4 + 1)), dim3(256), (hipStream_t)stream, x, M, D, d);
+}
+extern "C" int mt_pack_weight_f16(const float* src, int R, int C, mt_half* dst, int transpose, mt_stream_t stream) {
+  if (!src || !dst || R <= 0 || C <= 0) return MT_ERR_BAD_ARG;
+  return launch(pack_f16_kernel, dim3(cdiv(C, 32), cdiv(R, 32)), dim3(256), (hipStream_t)stream, src, R, C, (h16*)dst, transpose);
+}
+extern "C" int mt_pack_weights_f16(const long long* items, int n_items, mt_stream_t stream) {
+  if (!items || n_items <= 0) return MT_ERR_BAD_ARG;
+  return launch(pack_group_kernel, dim3(n_items, 48), dim3(256), (hipStream_t)stream, items);
+}
+extern "C" int mt_act_fwd(const float* x, float* y, long n, int act, mt_stream_t stream) {
+  if (!x || !y || n <= 0) return MT_ERR_BAD_ARG;
+  return launch(act_fwd_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, x, y, n, act);
+}
+extern "C" int mt_act_bwd(const float* x, const float* dy, float* dx, long n, int act, mt_stream_t stream) {
+  if (!x || !dy || !dx || n <= 0) return MT_ERR_BAD_ARG;
+  return launch(act_bwd_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, x, dy, dx, n, act);
+}
+extern "C" int mt_axpy(const float* a, const float* b, float alpha, float* y, long n, mt_stream_t stream) {
+  if (!a || !b || !y || n <= 0) return MT_ERR_BAD_ARG;
+  return launch(axpy_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, a, b, alpha, y, n);
+}
+extern "C" int mt_axpy_bcast(const float* a, const float* b, float alpha, float* y, long n, long period, mt_stream_t stream) {
+  if (!a || !b || !y || n <= 0 || period <= 0) return MT_ERR_BAD_ARG;
+  return launch(axpy_bcast_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, a, b, alpha, y, n, period);
+}
+extern "C" int mt_fold_rows(const float* x, int reps, long period, float* out, mt_stream_t stream) {
+  if (!x || !out || reps < 1 || period <= 0 || (period & 3) || ((uintptr_t)x & 15) || ((uintptr_t)out & 15)) return MT_ERR_BAD_ARG;
+  return launch(fold_rows_kernel, dim3(ew_grid(period / 4)), dim3(256), (hipStream_t)stream, x, reps, period, out);
+}
+extern "C" int mt_copy_rows_f32(const float* src, long lds, const MtRowMap* smap, float* dst, long ldd,
+                                const MtRowMap* dmap, int M, int D, int accumulate, mt_stream_t stream) {
+  if (!src || !dst || M <= 0 || D <= 0 || (D & 3) || (lds & 3) || (ldd & 3)) return MT_ERR_BAD_ARG;
+  return launch(copy_rows_kernel, dim3(ew_grid((long)M * D / 4)), dim3(256), (hipStream_t)stream, src, lds, make_rowmap(smap), dst, ldd,
+                make_rowmap(dmap), M, D, accumulate);
 }
